@@ -14,10 +14,15 @@ Other workloads (same JSON contract, parity-test configurations of BASELINE.json
   --workload rollout                               BASELINE config 5 (unet2 C96, 26 channels, bf16, 40-step rollout = 20
                                                    forwards with the state in HBM; one GPU = one independent replica)
 
-Timing: W untimed warm-up steps, then the K steps the contract names are timed between barrier + synchronize pairs; because
-K steps of a ~1 ms step are a ~20 ms window, the run continues with timed BLOCKS (>= 5 blocks of >= 0.5 s each, every one
-bracketed the same way, MAX over ranks) and `value` / `ms_per_step` are the MEDIAN block; the contract's K-step window is
-reported beside it (`k_step_window_ms_per_step`).
+Timing: W untimed warm-up steps, then exactly K timed steps (--steps) between one barrier + synchronize pair (MAX over ranks);
+`ms_per_step` is that window / K and `value` follows from it.  --blocks N times N further blocks of >= --min-block-s each, after
+the K steps, for their spread only (`timing.block_ms_per_step`).
+
+--dump-outputs DIR: after the K timed steps, what the last of them handed its caller is written to DIR/<name>.npy (float32):
+training -- `loss_stats` (the step's [loss, metric] rows) and `weights` (every weight of the model after the step, flattened in
+get_weights() order); rollouts -- the final `state` / the `forecast` series.  Inputs and initial weights are seeded, so the
+same arguments give the same inputs on every run; an array above DUMP_MAX_ELEMENTS is written as a fixed, seeded sample of
+its flattened elements.
 
 Prints ONE JSON line on rank 0: value = whole-job samples/s, plus
   roofline     -- dominant convolution kernel: algorithmic FLOPs and bytes per launch / HIP-event time per launch (library
@@ -67,6 +72,8 @@ PMC_GROUPS = (('FETCH_SIZE',), ('WRITE_SIZE', 'SQ_VALU_MFMA_BUSY_CYCLES', 'SQ_BU
 # read / write / copy kernels -- what a perfect kernel reaches on this hardware, next to the datasheet numbers above
 MEASURED_PEAKS = {'bf16_mfma_tflops': 2460.0, 'fp32_mfma_tflops': 156.0, 'hbm_read_gbs': 6400.0, 'hbm_write_gbs': 5200.0,
                   'hbm_copy_gbs': 4800.0, 'source': 'tools/peaks.hip, profiles/r01_peaks.txt'}
+# --dump-outputs: at most 2 arrays are written, each at most this many float32 elements (16 MB): the dump stays under 64 MB
+DUMP_MAX_ELEMENTS = 1 << 22
 
 
 def conv_plan(workload, c_in, c_out, base):
@@ -409,7 +416,7 @@ def prepare(args, dtype, rank):
         seq = max(1, args.rollout_steps // (X2_ITS * X2_STEPS))
         rows = seq * X2_ITS * X2_STEPS + B + 4
         return {'model': model, 'dx': dx, 'dev': dev, 'train': False, 'x2roll': True, 'seq': seq, 'n_fwd': seq * X2_STEPS,
-                'sol': torch.rand((rows, 6, N, N), dtype=torch.float32, device=dev), 'start': np.arange(B, dtype=np.int64) % 4}
+                'sol': torch.tensor(rng.random((rows, 6, N, N)), dtype=torch.float32, device=dev), 'start': np.arange(B, dtype=np.int64) % 4}
     if args.workload == 'unet2x2':
         c_main, _, co = x2_channels()
         # [main_input, solar_1, constants] as the reference's generator yields them (Azure/train_cs.py:191-194,392-396)
@@ -432,7 +439,7 @@ def prepare(args, dtype, rank):
 
 def run_step(st):
     if st['train']:
-        st['model'].train_on_device_batch(st['dx'], st['dt'])
+        st['last'] = st['model'].train_on_device_batch(st['dx'], st['dt'])
         return
     if st.get('x2roll'):
         st['last'] = st['model'].rollout_with_forcing(st['dx'], st['seq'], insolation=st['sol'], start_index=st['start'], io_time_steps=X2_ITS)
@@ -441,6 +448,24 @@ def run_step(st):
     # predict_timeseries runs (Model.rollout_passes_on_device: one hipGraph replay per rollout when graphs are on; from the second
     # pass on the state travels with its 26 channels padded to 32 -- zero channels -- per pixel)
     st['last'] = st['model'].rollout_passes_on_device(st['dx'][0], st['n_fwd'])
+
+
+def dump_outputs(st, out_dir):
+    """--dump-outputs: what the last run_step handed its caller, as float32 DIR/<name>.npy (see the module docstring)."""
+    if st['train']:
+        arrays = {'loss_stats': st['last'],
+                  'weights': torch.from_numpy(np.concatenate([w.ravel() for w in st['model'].get_weights()]))}
+    elif st.get('x2roll'):
+        arrays = {'forecast': st['last']}
+    else:
+        arrays = {'state': st['last'][..., :st['dx'][0].shape[-1]]}      # (a bf16 state may carry zero pad channels)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=DUMP_MAX_ELEMENTS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), t.float().cpu().numpy())
 
 
 def roofline_pass(st, steps=3):
@@ -571,9 +596,10 @@ def replicas_in_sync(model, world):
     return info
 
 
-def time_without_exchange(st, timed, per_block):
+def time_without_exchange(st, timed, steps, warmup):
     """Seconds per step of the SAME step form with the all-reduce calls turned into no-ops (the collective is captured inside
-    the step graph, so the graphs are captured anew for this and once more afterwards)."""
+    the step graph, so the graphs are captured anew for this and once more afterwards), timed like the step it is subtracted
+    from: `warmup` untimed steps, then one window of `steps` steps."""
     from DLWP import parallel as _par
     model = st['model']
 
@@ -585,8 +611,9 @@ def time_without_exchange(st, timed, per_block):
     _par.SKIP_EXCHANGE_FOR_TIMING = True
     try:
         recapture()
-        timed(per_block)
-        return float(np.median([timed(per_block) / per_block for _ in range(3)]))
+        for _ in range(warmup):
+            run_step(st)
+        return timed(steps) / steps
     finally:
         _par.SKIP_EXCHANGE_FOR_TIMING = False
         recapture()
@@ -618,7 +645,8 @@ def graph_kernel_nodes(cuda_graph):
 def dp_form_probe(args, dtype, plain_ms):
     """N = 1: the DATA-PARALLEL form of the step on this one GPU -- a process group of one rank over RCCL with
     DLWPCS_EXCHANGE_FORCE=1, so that the step takes exactly the launch sequence it takes at N > 1 (local reduction -> all-reduce,
-    captured in the step graph -> ONE launch that applies the update) -- timed with the same blocks, next to the plain step."""
+    captured in the step graph -> ONE launch that applies the update) -- timed like the plain step (W warm-up steps, one window
+    of K steps), next to it."""
     import socket
     from DLWP import parallel as _par
     own_group = not torch.distributed.is_initialized()
@@ -642,17 +670,15 @@ def dp_form_probe(args, dtype, plain_ms):
                 run_step(st)
             torch.cuda.synchronize()
             return time.perf_counter() - t0
-        for _ in range(5):
+        for _ in range(max(args.warmup, 3)):
             run_step(st)
-        est = timed(50) / 50
-        per_block = max(50, int(np.ceil(0.3 / max(est, 1e-9))))
-        ms = 1e3 * float(np.median([timed(per_block) / per_block for _ in range(3)]))
+        ms = 1e3 * timed(args.steps) / args.steps
         g = next(iter(model._graphs.values())) if model._graphs else None
         graphs = 0 if g is None else 1 + (g.get('bwd_b') is not None) + (g.get('update') is not None)
         nodes = None
         if g is not None and graphs == 1:
             nodes = graph_kernel_nodes(g['fwd_bwd'])
-        noex = 1e3 * time_without_exchange(st, timed, per_block)
+        noex = 1e3 * time_without_exchange(st, timed, args.steps, max(args.warmup, 3))
         return {'ms_per_step': round(ms, 4), 'vs_plain_step': round(ms / plain_ms, 4), 'graphs_per_step': graphs,
                 'launches': None if nodes is None else nodes['kernel'], 'graph_nodes': nodes,
                 'exposed_us': round(1e3 * (ms - noex), 1), 'ms_per_step_without_exchange': round(noex, 4),
@@ -675,10 +701,10 @@ def dp_form_probe(args, dtype, plain_ms):
             torch.distributed.destroy_process_group()
 
 
-def measure(args, dtype, rank, world, with_roofline, with_pmc, pmc_groups=None):
-    """Build the workload in `dtype`, warm up, time the contract's K steps and then >= 5 blocks of >= 0.5 s (each bracketed
-    by barrier + synchronize, MAX over ranks); optionally the per-launch roofline pass and the PMC passes.  Returns the
-    result dict on rank 0, None elsewhere."""
+def measure(args, dtype, rank, world, with_roofline, with_pmc, pmc_groups=None, dump_dir=None):
+    """Build the workload in `dtype`, warm up, time exactly K steps (bracketed by barrier + synchronize, MAX over ranks), dump
+    what the last of them computed when `dump_dir` is given, then the optional --blocks, the per-launch roofline pass and the
+    PMC passes.  Returns the result dict on rank 0, None elsewhere."""
     N, C, base, B = args.face, args.channels, args.base, args.batch
     st = prepare(args, dtype, rank)
     model, dev = st['model'], st['dev']
@@ -688,11 +714,15 @@ def measure(args, dtype, rank, world, with_roofline, with_pmc, pmc_groups=None):
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    def timed(n):
+    def timed(n, events=None):
         barrier()
         t0 = time.perf_counter()
+        if events:
+            events[0].record()
         for _ in range(n):
             run_step(st)
+        if events:
+            events[1].record()
         barrier()
         el = time.perf_counter() - t0
         if world > 1:
@@ -726,30 +756,23 @@ def measure(args, dtype, rank, world, with_roofline, with_pmc, pmc_groups=None):
             for _ in range(4):
                 run_step(st)
     sync = replicas_in_sync(model, world) if st['train'] else None
-    k_elapsed = timed(args.steps)             # the contract's window: exactly K steps
-    est = k_elapsed / args.steps
-    per_block = max(args.steps, int(np.ceil(args.min_block_s / max(est, 1e-9))))
+    # the timed region: exactly K steps.  HIP events on the compute stream around the same steps (device clock) are the
+    # self-check that the timed work ran on the device.
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    k_elapsed = timed(args.steps, (e0, e1))
+    step_s = k_elapsed / args.steps
+    if dump_dir is not None and rank == 0:
+        dump_outputs(st, dump_dir)
+    per_block = max(args.steps, int(np.ceil(args.min_block_s / max(step_s, 1e-9))))
     if world > 1:                             # every rank must run the same number of steps per block
         pb = torch.tensor([per_block], dtype=torch.int64, device=dev)
         torch.distributed.all_reduce(pb, op=torch.distributed.ReduceOp.MAX)
         per_block = int(pb.item())
     blocks = [timed(per_block) / per_block for _ in range(args.blocks)]
-    step_s = float(np.median(blocks))
-    # self-check that the timed work ran on the device: the same steps between two HIP events on the compute stream (device
-    # clock) against the host clock, and the device the process is bound to
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    barrier()
-    t0 = time.perf_counter()
-    e0.record()
-    for _ in range(per_block):
-        run_step(st)
-    e1.record()
-    barrier()
-    wall = time.perf_counter() - t0
     self_check = {'device': torch.cuda.get_device_name(dev), 'arch': getattr(torch.cuda.get_device_properties(dev), 'gcnArchName', ''),
-                  'steps': per_block, 'hip_event_ms_per_step': round(e0.elapsed_time(e1) / per_block, 4),
-                  'host_wall_ms_per_step': round(1e3 * wall / per_block, 4),
-                  'device_busy_fraction': round(min(1.0, e0.elapsed_time(e1) * 1e-3 / wall), 4)}
+                  'steps': args.steps, 'hip_event_ms_per_step': round(e0.elapsed_time(e1) / args.steps, 4),
+                  'host_wall_ms_per_step': round(1e3 * step_s, 4),
+                  'device_busy_fraction': round(min(1.0, e0.elapsed_time(e1) * 1e-3 / k_elapsed), 4)}
     try:
         self_check['smi_utilization_percent'] = int(torch.cuda.utilization(dev))
     except Exception as exc:                  # amdsmi not importable on the box: say so instead of reporting 0
@@ -760,7 +783,7 @@ def measure(args, dtype, rank, world, with_roofline, with_pmc, pmc_groups=None):
     # (DLWP.parallel.SKIP_EXCHANGE_FOR_TIMING: timing only -- the replicas diverge, so this runs after everything that is reported)
     noex_s = None
     if world > 1 and st['train']:
-        noex_s = time_without_exchange(st, timed, per_block)
+        noex_s = time_without_exchange(st, timed, args.steps, max(args.warmup, 3))
     # the roofline pass runs eager optimisation steps (gradient all-reduce included): EVERY rank takes part
     agg = roofline_pass(st) if with_roofline else None
     # (N = 1 only: at N > 1 the captured step holds a collective, and a capture that failed on one rank alone would leave the
@@ -800,10 +823,11 @@ def measure(args, dtype, rank, world, with_roofline, with_pmc, pmc_groups=None):
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': dtype, 'data': 'synthetic',
         'config': {'workload': what, 'global_batch': B * world, 'parallelism': 'dp%d' % world,
                    'hip_graphs': bool(model.use_graphs)},
-        'timing': {'value_from': 'median of %d blocks of %d steps (each >= %.2f s, barrier + synchronize on both sides, '
-                                 'max over ranks)' % (args.blocks, per_block, args.min_block_s),
+        'timing': {'value_from': '%d timed steps (--steps) after %d warm-up steps, barrier + synchronize on both sides, max over '
+                                 'ranks' % (args.steps, max(args.warmup, 3)),
                    'block_ms_per_step': [round(1e3 * b, 4) for b in blocks],
-                   'k_step_window_ms_per_step': round(1e3 * k_elapsed / args.steps, 4)},
+                   'blocks': None if not blocks else '%d further blocks of %d steps after the timed steps (--blocks), not '
+                                                     'part of ms_per_step' % (args.blocks, per_block)},
         'model_tflops': round(flops_step * world / step_s / 1e12, 3),
         'device_self_check': self_check,
     }
@@ -960,8 +984,11 @@ def main():
                     help='activation dtype of the headline number.  bf16 (default; BASELINE config 3 names bf16 compute, '
                          'the reference trains under TF AMP): bf16 activations + bf16 MFMA, fp32 master weights / '
                          'gradients / Adam.  f32: exact-fp32 MFMA everywhere (the 1e-5 parity mode).')
-    ap.add_argument('--blocks', type=int, default=5, help='timed blocks behind the headline value (median)')
-    ap.add_argument('--min-block-s', type=float, default=0.5, help='minimum duration of a timed block')
+    ap.add_argument('--blocks', type=int, default=0,
+                    help='further timed blocks after the K timed steps, reported for their spread (not part of ms_per_step)')
+    ap.add_argument('--min-block-s', type=float, default=0.5, help='minimum duration of a --blocks block')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy (float32, < 64 MB in all)')
     ap.add_argument('--no-companion', action='store_true',
                     help='skip the second measurement in the other dtype (N = 1 only) reported under "f32" / "bf16"')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -978,6 +1005,8 @@ def main():
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--pmc-plan', default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.face is None:
         args.face = 96 if args.workload == 'rollout' else 48
     if args.channels is None:
@@ -1041,7 +1070,7 @@ def main():
                                       ('production_rollout_bf16', 'rollout_x2', x2_channels()[1], 48, 'bf16')):
             a2 = copy.copy(args)
             a2.workload, a2.channels, a2.face, a2.dtype = wl, ch, face, dt
-            a2.blocks, a2.min_block_s, a2.steps, a2.warmup, a2.pmc_out = 3, 0.3, (20 if 'rollout' in wl else 100), 5, None
+            a2.steps, a2.warmup, a2.pmc_out = (20 if 'rollout' in wl else 100), 5, None
             cfg_runs.append((key, a2, dt))
     if single and not args.no_pmc and not args.no_roofline:
         # every counter pass of this line up front: ONE rocprofv3 process per counter group runs all workloads (round 5: one per group
@@ -1058,7 +1087,7 @@ def main():
         from DLWP import parallel as _par
         _par.enable_native_comm(os.environ.get('DLWPCS_BENCH_NATIVE_RCCL', '1') == '1')
     result = measure(args, args.dtype, rank, world, with_roofline=not args.no_roofline,
-                     with_pmc=single and not args.no_pmc)
+                     with_pmc=single and not args.no_pmc, dump_dir=args.dump_outputs)
     if world > 1:
         torch.distributed.barrier()
     if single and not args.no_dp_form and 'rollout' not in args.workload:

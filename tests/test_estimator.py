@@ -15,6 +15,17 @@ from oracle import cs_oracle as orc
 N, V, ITS, K, T = 8, 3, 2, 2, 40
 
 
+@pytest.fixture
+def host_device():
+    """The engine's device is 'cpu' for the test and the process's own device again afterwards: a GPU test that runs later in
+    the same process relies on the default device."""
+    from DLWP.keras import backend
+    prev = backend.device()
+    backend.set_device('cpu')
+    yield
+    backend.set_device(prev)
+
+
 def _data(seed=31):
     rng = np.random.default_rng(seed)
     arr = rng.standard_normal((T, V, 6, N, N)).astype(np.float32)
@@ -62,9 +73,7 @@ def _generator(dlwp, sequence, with_const=True, device=None):
 @pytest.mark.parametrize('n_out', [1, 2])
 @pytest.mark.parametrize('keep', [False, True])
 @pytest.mark.parametrize('steps', [3, 8])
-def test_estimator_host_loop_matches_reference_restatement(n_out, keep, steps):
-    from DLWP.keras import backend
-    backend.set_device('cpu')
+def test_estimator_host_loop_matches_reference_restatement(host_device, n_out, keep, steps):
     from DLWP.model import DLWPFunctional, TimeSeriesEstimator
     dlwp = DLWPFunctional(is_convolutional=True, time_dim=ITS)
     dlwp.build_model(_StubNet(n_out), loss='mse')
@@ -89,9 +98,7 @@ def _as_list(o):
     return list(o) if isinstance(o, (list, tuple)) else [o]
 
 
-def test_estimator_argument_checks():
-    from DLWP.keras import backend
-    backend.set_device('cpu')
+def test_estimator_argument_checks(host_device):
     from DLWP.model import DLWPFunctional, TimeSeriesEstimator
     dlwp = DLWPFunctional(is_convolutional=True, time_dim=ITS)
     dlwp.build_model(_StubNet(2), loss='mse')
@@ -249,10 +256,8 @@ def test_estimator_device_rollout_matches_oracle_and_host_loop(dtype):
 # --------------------------------------------------------------------------------------------------------------------- #
 
 @pytest.mark.parametrize('interval', [1, 2])
-def test_estimator_matches_reference_estimator(golden_dir, interval):
+def test_estimator_matches_reference_estimator(host_device, golden_dir, interval):
     import os
-    from DLWP.keras import backend
-    backend.set_device('cpu')
     from DLWP.model import DLWPFunctional, TimeSeriesEstimator
     from DLWP.model.generators import ArrayDataGenerator
     g = np.load(os.path.join(golden_dir, 'g10_estimator.npz' if interval == 1 else 'g10_estimator_interval2.npz'))

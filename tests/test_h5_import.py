@@ -16,9 +16,12 @@ from oracle import cs_oracle as orc
 
 @pytest.fixture(autouse=True)
 def _cpu_device():
+    # (the process's own device again afterwards: a GPU test that runs later in the same process relies on the default device)
     from DLWP.keras import backend
+    prev = backend.device()
     backend.set_device('cpu')
     yield
+    backend.set_device(prev)
 
 
 def _expected(golden_dir):
