@@ -183,6 +183,10 @@ __device__ __forceinline__ void conv_ws_body(const ConvKParams &P, char *smem, c
     constexpr int XF4 = NTB * KCG * 64;             // ... of one substitute slot
     constexpr int WF4 = EDGE ? WF4M + 3 * XF4 : WF4M;
     constexpr int ITS = 3 * KC / VW;                // input vectors per producer thread per chunk (3*NCT pixels)
+    // one validity bit per input vector: bf16 with 2-B vectors has ITS = 48, whose bits 32..47 a 32-bit mask would fold onto
+    // bits 0..15 (slots >= 32 are used by tiles of more than 512 pixels, e.g. the data gradient on 96-wide faces)
+    using OkMask = typename std::conditional<(ITS > 32), uint64_t, uint32_t>::type;
+    static_assert(ITS <= 64, "one validity bit per input vector");
     constexpr int ITW = (WF4 + NCT - 1) / NCT;
     static_assert(NCT % Q == 0, "thread -> channel-vector mapping must not depend on the item");
     static_assert(KC % CGW == 0 && KC % VW == 0, "chunk must hold whole operand groups and whole vectors");
@@ -412,7 +416,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvKParams &P, char *smem, c
             }
         };
         // issue(): (rarely) the weight fragments -> LDS buffer g & 1, then every load of the chunk's input tile, back to back
-        auto issue = [&](const Geo &gc, int ch, V (&val)[ITS], V (&ymv)[MASK ? ITS : 1], uint32_t &okm) __attribute__((always_inline)) {
+        auto issue = [&](const Geo &gc, int ch, V (&val)[ITS], V (&ymv)[MASK ? ITS : 1], OkMask &okm) __attribute__((always_inline)) {
             // (EDGE: the area also holds the substitute fragments of the tile's triple -- keyed by face and edge-row class)
             const int wkey = (EDGE ? gc.fcls : gc.v) * 1024 + ch;
             const int area = P.wstat ? ch : (g & 1);
@@ -441,11 +445,11 @@ __device__ __forceinline__ void conv_ws_body(const ConvKParams &P, char *smem, c
                 if constexpr (TAIL8) val[i] = *reinterpret_cast<const uint4_a4 *>(sb + oo);
                 else val[i] = *reinterpret_cast<const V *>(sb + oo);
                 if (MASK) ymv[i] = *reinterpret_cast<const V *>(ymb + oo);
-                okm |= (uint32_t)ok << i;
+                okm |= (OkMask)ok << i;
             }
         };
         // commit(): the loaded vectors -> LDS buffer g & 1, barrier B_g
-        auto commit = [&](const Geo &gc, int ch, V (&val)[ITS], V (&ymv)[MASK ? ITS : 1], uint32_t okm) __attribute__((always_inline)) {
+        auto commit = [&](const Geo &gc, int ch, V (&val)[ITS], V (&ymv)[MASK ? ITS : 1], OkMask okm) __attribute__((always_inline)) {
             char *buf = smem + (g & 1) * in_step;
             if constexpr (TAIL8) {
                 const T *sb; int cstride, cs_ld, sh; bool c_ok, up;
@@ -475,7 +479,7 @@ __device__ __forceinline__ void conv_ws_body(const ConvKParams &P, char *smem, c
         // channels, 0.936 -> 1.02 ms per training step.)
         int cur_combo = -1;
         V val[ITS], ymv[MASK ? ITS : 1];
-        uint32_t okm = 0;
+        OkMask okm = 0;
         // (Measured negative: requesting the first two chunks' weight fragments before the first tile's halo-table lookup and
         // its input vectors before the weight stores -- two dependent round trips instead of three at the start of the kernel
         // -- made the training step 3 % SLOWER; the first chunk's fragments alone before the lookup: 1 % slower.  The loads of a
