@@ -24,6 +24,8 @@ MSE_TARGET_F32 = 0x100
 MSE_OVERWRITE = 0x200
 ADAM_ZERO_GRAD = 1
 HEAD_DEFER_STAGE2 = 2
+LOSS_MSE, LOSS_MAE, LOSS_ACC = 0, 1, 2
+REG_NONE, REG_MSE, REG_MAE, REG_GLOBAL = 0, 1, 2, 3
 ACT_NONE = 0
 ACT_LEAKY_CLIP = 1
 CONV_ACCUMULATE_WGRAD = 1
@@ -76,6 +78,14 @@ class LossTail(ctypes.Structure):
     """struct dlwpcs_loss_tail (include/dlwpcs.h)"""
     _fields_ = [('partial', ctypes.c_void_p), ('loss_out', ctypes.c_void_p), ('nblocks', ctypes.c_int32), ('inv_n', ctypes.c_float),
                 ('weight', ctypes.c_float), ('overwrite', ctypes.c_int32)]
+
+
+class LossDesc(ctypes.Structure):
+    """struct dlwpcs_loss_desc (include/dlwpcs.h)"""
+    _fields_ = [('kind', ctypes.c_int32), ('loss_weight', ctypes.c_float), ('weight', ctypes.c_void_p),
+                ('weight_div', ctypes.c_int32), ('weight_period', ctypes.c_int32), ('clim', ctypes.c_void_p),
+                ('clim_div', ctypes.c_int32), ('clim_period', ctypes.c_int32), ('regularize', ctypes.c_int32),
+                ('reverse', ctypes.c_int32), ('overwrite', ctypes.c_int32)]
 
 
 class GConvDesc(ctypes.Structure):
@@ -148,6 +158,10 @@ PROTOTYPES = {
     'dlwpcs_mse_scratch_bytes': (c_size_t, []),
     'dlwpcs_mse_fwd_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_int, c_void_p,
                                    c_void_p]),
+    'dlwpcs_loss_scratch_bytes': (c_size_t, []),
+    'dlwpcs_loss_fwd_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
+    'dlwpcs_head_loss_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int, c_float, c_float, c_void_p]),
     'dlwpcs_adam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,
                                  c_float, c_float, c_float, c_void_p]),
     'dlwpcs_adam_step_fused': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,

@@ -10,7 +10,8 @@ reference module `DLWP/custom.py`, dispatching to hand-written HIP kernels (libd
     CubeSphereConv2D      reference DLWP/custom.py:755-1054
 
 plus the training callbacks the reference scripts pass to `fit` (reference DLWP/custom.py:33-208), re-hosted on the
-TF-free shim in `DLWP.keras`.
+TF-free shim in `DLWP.keras`, and the training losses latitude_weighted_loss / anomaly_correlation(_loss) (reference
+DLWP/custom.py:1543-1676), which Model.compile runs as HIP kernels.
 """
 
 import numpy as np
@@ -20,6 +21,7 @@ from ._native import ACT_LEAKY_CLIP, ACT_NONE
 from .keras import constraints, engine, regularizers
 from .keras.callbacks import Callback, EarlyStopping
 from .keras.engine import Layer
+from .keras.losses import LossSpec, mean_absolute_error, mean_squared_error, spec_of
 
 
 # ==================================================================================================================== #
@@ -472,3 +474,137 @@ class GeneratorEpochEnd(Callback):
 
     def on_epoch_end(self, epoch, logs=None):
         self.generator.on_epoch_end()
+
+
+# ==================================================================================================================== #
+# Keras loss functions (reference DLWP/custom.py:1543-1676)
+# ==================================================================================================================== #
+# Host callables with the reference's semantics (numpy or torch arrays in, keras' loss value out).  Each carries a
+# `_dlwpcs_loss` spec (DLWP.keras.losses.LossSpec): Model.compile reads it and runs the HIP loss kernels (DLWP.ops.loss_stats)
+# in its place -- a callable without one is refused there.
+
+
+def _xp_like(a, ref):
+    """a (numpy / scalar) as an array of ref's kind (torch: same device and dtype)"""
+    if hasattr(ref, 'detach') and not hasattr(a, 'detach'):
+        import torch
+        return torch.as_tensor(np.asarray(a), dtype=ref.dtype, device=ref.device)
+    return a
+
+
+def _mean(x, axis=None):
+    if hasattr(x, 'detach'):
+        return x.mean() if axis is None else x.mean(dim=tuple(axis))
+    return np.mean(x) if axis is None else np.mean(x, axis=tuple(axis))
+
+
+def _sqrt(x):
+    return x.sqrt() if hasattr(x, 'detach') else np.sqrt(x)
+
+
+def _abs(x):
+    return x.abs() if hasattr(x, 'detach') else np.abs(x)
+
+
+def latitude_weighted_loss(loss_function=mean_squared_error, lats=None, output_shape=(), axis=-2, weighting='cosine'):
+    """
+    Create a loss function that weights inputs by a function of latitude before calculating the loss (reference
+    DLWP/custom.py:1543-1578, same signature, defaults and errors).
+
+    The weight field is cos(lat), or cos(lat) + 0.5 sin^2(2 lat) for 'midlatitude', expanded and repeated over
+    output_shape[axis:][1:]; ones(output_shape) without `lats`.  The loss is loss_function(y_true * w, y_pred * w): w enters a
+    mean squared error SQUARED (mean(w^2 (y_pred - y_true)^2)) -- the reference's definition, kept as is.
+
+    On the cubed sphere pass the grid's per-cell latitudes, ds.lat of shape (6, N, N), with output_shape (6, N, N, C) and
+    axis=-2 (channels_last): the field becomes (6, N, N, C).  A channels_first output (C, 6, N, N) takes axis=-1 (field
+    (6, N, N), broadcast over the channels).
+
+    :param loss_function: mean_squared_error / mean_absolute_error (DLWP.keras.losses) or an anomaly-correlation loss of
+        this module -- the forms the DLWP-CS engine runs on the GPU
+    :param lats: ndarray: latitude coordinates (degrees)
+    :param output_shape: tuple: shape of expected model output
+    :param axis: int: latitude axis in model output shape
+    :param weighting: str: 'cosine' (default) or 'midlatitude'
+    :return: callable loss function `lat_loss`
+    """
+    if weighting not in ['cosine', 'midlatitude']:
+        raise ValueError("'weighting' must be one of 'cosine' or 'midlatitude'")
+    if lats is not None:
+        lat = np.asarray(lats[:]).astype(np.float32)
+        weights = np.cos(lat * np.pi / 180.)
+        if weighting == 'midlatitude':
+            weights = weights + 0.5 * np.power(np.sin(lat * 2 * np.pi / 180.), 2.)
+        weight_shape = tuple(output_shape)[axis:]
+        for d in weight_shape[1:]:
+            weights = np.expand_dims(weights, axis=-1)
+            weights = np.repeat(weights, d, axis=-1)
+    else:
+        weights = np.ones(output_shape, dtype=np.float32)
+    weights = weights.astype(np.float32)
+
+    def lat_loss(y_true, y_pred):
+        w = _xp_like(weights, y_pred)
+        return loss_function(y_true * w, y_pred * w)
+
+    inner = spec_of(loss_function)
+    lat_loss._dlwpcs_loss = None if (inner is None or inner.weights is not None) else inner._replace(weights=weights)
+    lat_loss.weights = weights
+    return lat_loss
+
+
+def _acc_value(y_true, y_pred, mean, regularize_mean, reverse):
+    if mean is not None:
+        mean = _xp_like(mean, y_pred)
+        a = (_mean((y_pred - mean) * (y_true - mean))
+             / _sqrt(_mean((y_pred - mean) ** 2) * _mean((y_true - mean) ** 2)))
+    else:
+        a = _mean(y_pred * y_true) / _sqrt(_mean(y_pred ** 2) * _mean(y_true ** 2))
+    if regularize_mean is not None:
+        if regularize_mean == 'global':
+            m = _abs((_mean(y_true) - _mean(y_pred)) / _mean(y_true))
+        elif regularize_mean == 'spatial':
+            m = _mean(_abs((_mean(y_true, axis=[-2, -1]) - _mean(y_pred, axis=[-2, -1])) / _mean(y_true, axis=[-2, -1])))
+        elif regularize_mean == 'mse':
+            m = mean_squared_error(y_true, y_pred)          # (per row, like the reference: keras' reduction averages it)
+        else:
+            m = mean_absolute_error(y_true, y_pred)
+    if reverse:
+        return m - a if regularize_mean is not None else -a
+    return a - m if regularize_mean else a
+
+
+def anomaly_correlation(y_true, y_pred, mean=0., regularize_mean='mse', reverse=True):
+    """
+    Anomaly correlation (reference DLWP/custom.py:1581-1620): `mean` is IGNORED, as in the reference (the climatology is
+    assumed to be 0); regularize_mean in {None, 'global', 'spatial', 'mse', 'mae'}; reverse: -1 is the target score.
+    """
+    if regularize_mean is not None:
+        assert regularize_mean in ['global', 'spatial', 'mse', 'mae']
+    return _acc_value(y_true, y_pred, None, regularize_mean, reverse)
+
+
+anomaly_correlation._dlwpcs_loss = LossSpec('acc', None, None, 'mse', True)
+
+
+def anomaly_correlation_loss(mean=None, regularize_mean='mse', reverse=True):
+    """
+    Keras loss function `acc_loss` for the anomaly correlation (reference DLWP/custom.py:1623-1676).
+
+    :param mean: ndarray or None: climatology, the shape of the prediction with a batch axis of 1
+    :param regularize_mean: None, 'global', 'spatial', 'mse' or 'mae' (with a regulariser, reverse is forced to True).
+        The DLWP-CS engine trains every form but 'spatial' (a per-sample reduction over the layout's last two axes).
+    :param reverse: bool: if True, inverts the loss so that -1 is the (minimized) target score
+    """
+    if mean is not None:
+        assert len(mean.shape) > 1
+        assert mean.shape[0] == 1
+        mean = np.asarray(mean, dtype=np.float32)
+    if regularize_mean is not None:
+        assert regularize_mean in ['global', 'spatial', 'mse', 'mae']
+        reverse = True
+
+    def acc_loss(y_true, y_pred):
+        return _acc_value(y_true, y_pred, mean, regularize_mean, reverse)
+
+    acc_loss._dlwpcs_loss = LossSpec('acc', None, mean, regularize_mean, bool(reverse))
+    return acc_loss

@@ -26,7 +26,7 @@ from .. import ops, parallel
 from ..options import option
 from .. import _native as _nat
 from .._native import ACT_LEAKY_CLIP, ACT_NONE
-from . import backend, callbacks as cbks, optimizers, staging
+from . import backend, callbacks as cbks, losses as klosses, optimizers, staging
 from .engine import KTensor, Layer
 from .layers import AveragePooling3D, Concatenate, InputLayer, ReLU, UpSampling3D
 
@@ -59,6 +59,7 @@ class Model(object):
         self.stop_training = False
         self.optimizer = None
         self.loss = None
+        self._dev_losses = None             # per output: ops.DeviceLoss, or None for plain 'mse' (ops.mse_mae / ops.head_mse)
         self.loss_weights = None
         self.metrics = []
         self.history = None
@@ -477,10 +478,10 @@ class Model(object):
                         and isinstance(lay, CubeSphereConv2D) and len(args) == 1 and lay._is_mfma_config()
                         and self._runs_channels_last(lay) and lay.activation is None and lay.north_pole_kernel is None
                         and ops.head_mse_applicable(args[0], lay.equatorial_kernel, lay.kernel_size[0], ACT_NONE,
-                                                    fuse_targets[out_uid][0])):
-                    tgt, wgt = fuse_targets[out_uid]
+                                                    fuse_targets[out_uid][0], fuse_targets[out_uid][2])):
+                    tgt, wgt, dl = fuse_targets[out_uid]
                     values[out_uid] = ops.head_mse(args[0], tgt, lay.equatorial_kernel, lay.polar_kernel, lay.equatorial_bias,
-                                                   lay.polar_bias, wgt, lay.flip_north_pole, premask=head_pm)
+                                                   lay.polar_bias, wgt, lay.flip_north_pole, premask=head_pm, loss=dl)
                     self._fused_outputs.add(out_uid)
                     continue
                 if head_pm is not None:
@@ -604,10 +605,28 @@ class Model(object):
             self._pack_cache = None
         n_out = len(self.outputs)
         losses = _as_list(loss) if isinstance(loss, (list, tuple)) else [loss] * n_out
+        if len(losses) != n_out:
+            raise ValueError('When passing a list as loss, it should have one entry per model output. The model has %d '
+                             'outputs, but you passed loss=%s' % (n_out, loss))
+        specs = []
         for l in losses:
-            if l not in ('mse', 'mean_squared_error', 'MSE'):
-                raise NotImplementedError("loss %r: the DLWP-CS engine provides 'mse' (reference Azure/train_cs.py:424)"
-                                          % (l,))
+            sp = klosses.spec_of(l) if not isinstance(l, str) or l in ('mse', 'mean_squared_error', 'MSE') else None
+            if sp is None and isinstance(l, str):
+                raise NotImplementedError("loss %r: of the loss names the DLWP-CS engine takes 'mse' (reference "
+                                          "Azure/train_cs.py:424); pass the function for the others, e.g. "
+                                          "DLWP.keras.losses.mean_absolute_error" % (l,))
+            if sp is None:
+                raise NotImplementedError("loss %r: the DLWP-CS engine provides 'mse', 'mae' (DLWP.keras.losses) and the "
+                                          "losses of DLWP.custom: latitude_weighted_loss, anomaly_correlation(_loss)" % (l,))
+            if sp.regularize == 'spatial':
+                raise NotImplementedError("anomaly-correlation regularize_mean='spatial': a per-sample reduction over the layout's "
+                                          "last two axes (reference DLWP/custom.py:1604-1606,1657-1659) the DLWP-CS engine does "
+                                          "not build")
+            if sp.kind == 'acc' and parallel.world()[1] > 1:
+                raise NotImplementedError('the anomaly-correlation loss is a ratio of sums over the WHOLE batch: per-rank values '
+                                          'averaged across %d data-parallel ranks are a different loss (train it on one rank)'
+                                          % parallel.world()[1])
+            specs.append(sp)
         self.loss = loss
         if loss_weights is None:
             self.loss_weights = [1.0] * n_out
@@ -622,6 +641,11 @@ class Model(object):
                 raise NotImplementedError("metric %r: the DLWP-CS engine provides 'mae'" % (m,))
         self.metrics = metrics
         self._flatten_parameters()
+        # loss fields (latitude weights, climatology) on the model's device, once; plain 'mse' keeps its own kernels
+        dev = self._flat_params.device if self._flat_params is not None else torch.device('cpu')
+        self._dev_losses = [None if (sp.kind == 'mse' and sp.weights is None) else
+                            ops.DeviceLoss(sp, tuple(o.shape[1:]), self._cf_model, dev)
+                            for sp, o in zip(specs, self.outputs)]
         self._graphs.clear()
         self._infer_graphs.clear()          # (captured with the parameters' old addresses)
         self._seen_batch.clear()
@@ -630,6 +654,15 @@ class Model(object):
         if parallel.exchange_wanted() and self._flat_params.is_cuda:
             parallel.native_comm()      # (opt-in; agreed on by every rank HERE, outside any capture: see DLWP/parallel.py)
         self._compiled = True
+
+    def _losses_per_output(self):
+        return self._dev_losses if self._dev_losses is not None else [None] * len(self.outputs)
+
+    def _loss_config(self):
+        """compile's `loss` as keras serialises it: names ('mse', 'lat_loss', 'acc_loss', 'mean_squared_error', ...)."""
+        if isinstance(self.loss, (list, tuple)):
+            return [klosses.config_name(l) for l in self.loss]
+        return klosses.config_name(self.loss)
 
     def _metric_names(self):
         """keras log names: 'loss', per-output losses (multi-output only), then metrics."""
@@ -725,7 +758,7 @@ class Model(object):
             targets = [ops.channels_first_to_last(t) if t.dim() == 5 else t for t in targets]
         fuse = None
         if train and self.fuse_head_loss:
-            fuse = {o.uid: (t, w) for o, t, w in zip(self.outputs, targets, self.loss_weights)}
+            fuse = {o.uid: (t, w, dl) for o, t, w, dl in zip(self.outputs, targets, self.loss_weights, self._losses_per_output())}
             ops.DIRECT_PARAM_GRADS = True       # (head_mse_applicable checks it: the fused step needs the flat gradient buffer)
         cutplan = self._plan_exchange() if (train and split) else None
         self._record_cut = cutplan[0] if cutplan else None
@@ -748,8 +781,8 @@ class Model(object):
             if fuse is not None:
                 ops.DIRECT_PARAM_GRADS = False
         fused = getattr(self, '_fused_outputs', set()) if fuse is not None else set()
-        stats = [o if out.uid in fused else ops.mse_mae(o, t, w)
-                 for out, o, t, w in zip(self.outputs, outs, targets, self.loss_weights)]
+        stats = [o if out.uid in fused else (ops.mse_mae(o, t, w) if dl is None else ops.loss_stats(o, t, dl, w))
+                 for out, o, t, w, dl in zip(self.outputs, outs, targets, self.loss_weights, self._losses_per_output())]
         if train:
             dev = stats[0].device
             ones = [ops.unit_seed(dev) for _ in stats]
@@ -1826,7 +1859,7 @@ class Model(object):
         tc = opt_w = None
         if self._compiled:
             ocfg = dict(self.optimizer.get_config())
-            tc = json.dumps({'optimizer_config': {'class_name': 'Adam', 'config': ocfg}, 'loss': self.loss,
+            tc = json.dumps({'optimizer_config': {'class_name': 'Adam', 'config': ocfg}, 'loss': self._loss_config(),
                              'metrics': list(self.metrics), 'weighted_metrics': None, 'sample_weight_mode': None,
                              'loss_weights': self.loss_weights})
             st = self.optimizer.state_dict() if include_optimizer else None
@@ -1859,7 +1892,7 @@ class Model(object):
                 'compile': None, 'compute_dtype': self.compute_dtype, 'n_weights': len(self.weights)}
         arrays = self.get_weights()
         if self._compiled:
-            meta['compile'] = {'loss': self.loss, 'loss_weights': self.loss_weights, 'metrics': self.metrics,
+            meta['compile'] = {'loss': self._loss_config(), 'loss_weights': self.loss_weights, 'metrics': self.metrics,
                                'optimizer': self.optimizer.get_config(), 'optimizer_state': None}
             st = self.optimizer.state_dict() if include_optimizer else None
             if st is not None:
@@ -1965,7 +1998,21 @@ class Model(object):
         print_fn('Fused cubed-sphere convolution launches per forward pass: %d' % self.n_fused)
 
 
-def _compile_from_keras_training_config(model, tc):
+def _resolve_loss(loss, custom_objects):
+    """A saved loss name -> what compile takes: keras' own names as they are, any other through custom_objects (as keras
+    does: 'lat_loss' / 'acc_loss' are the closures of DLWP.custom's factories, rebuilt by the caller)."""
+    if isinstance(loss, (list, tuple)):
+        return [_resolve_loss(l, custom_objects) for l in loss]
+    if loss is None or loss in ('mse', 'mean_squared_error', 'MSE'):
+        return loss
+    if loss in klosses._BY_NAME:
+        return klosses.get(loss)
+    if custom_objects and loss in custom_objects:
+        return custom_objects[loss]
+    raise ValueError('Unknown loss function: %s' % loss)
+
+
+def _compile_from_keras_training_config(model, tc, custom_objects=None):
     opt = tc.get('optimizer_config') or {}
     ocfg = dict(opt.get('config', {}))
     if opt.get('class_name', 'Adam').lower() != 'adam':
@@ -1976,7 +2023,7 @@ def _compile_from_keras_training_config(model, tc):
     for m in (metrics if isinstance(metrics, (list, tuple)) else [metrics]):
         flat += list(m) if isinstance(m, (list, tuple)) else [m]
     metrics = ['mae' if m in ('mae', 'mean_absolute_error') else m for m in flat]
-    model.compile(optimizer=optimizers.Adam(**ocfg), loss=tc.get('loss'), loss_weights=tc.get('loss_weights'),
+    model.compile(optimizer=optimizers.Adam(**ocfg), loss=_resolve_loss(tc.get('loss'), custom_objects), loss_weights=tc.get('loss_weights'),
                   metrics=sorted(set(metrics)) or None)
 
 
@@ -2021,7 +2068,7 @@ def load_model(filepath, custom_objects=None, compile=True):
             model.compute_dtype = hdf5_lite._as_str(cd)                       # (files written by this engine)
         tc = f.attrs.get('training_config')
         if compile and tc is not None:
-            _compile_from_keras_training_config(model, json.loads(hdf5_lite._as_str(tc)))
+            _compile_from_keras_training_config(model, json.loads(hdf5_lite._as_str(tc)), custom_objects)
             if 'optimizer_weights' in f._links:
                 _restore_adam_from_keras(model, f['optimizer_weights'])
         return model
@@ -2034,7 +2081,8 @@ def load_model(filepath, custom_objects=None, compile=True):
     model.set_weights(arrays[:nw])
     cmp = meta.get('compile')
     if compile and cmp:
-        model.compile(optimizer=optimizers.get(cmp['optimizer']), loss=cmp['loss'], loss_weights=cmp['loss_weights'],
+        model.compile(optimizer=optimizers.get(cmp['optimizer']), loss=_resolve_loss(cmp['loss'], custom_objects),
+                      loss_weights=cmp['loss_weights'],
                       metrics=cmp['metrics'])
         st = cmp.get('optimizer_state')
         if st is not None and len(arrays) >= nw + 2:

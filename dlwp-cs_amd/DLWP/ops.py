@@ -7,6 +7,7 @@ and the optimizer state are always float32 -- see the dtype note in include/dlwp
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _native as nat
@@ -1254,12 +1255,128 @@ def mse_mae(y, t, weight=1.0):
     return _MSE.apply(y, t, float(weight))
 
 
+# ---- the other training losses (DLWP.keras.losses / DLWP.custom: 'mae', latitude-weighted, anomaly correlation) ----------
+_KINDS = {'mse': nat.LOSS_MSE, 'mae': nat.LOSS_MAE, 'acc': nat.LOSS_ACC}
+_REGS = {None: nat.REG_NONE, 'mse': nat.REG_MSE, 'mae': nat.REG_MAE, 'global': nat.REG_GLOBAL}
+
+
+def _loss_field(a, sample_shape, channels_first, what):
+    """A weight / climatology field as dlwpcs_loss_desc takes it: broadcast to ONE sample of the model's output, moved to the
+    loss's channels_last layout (the engine forms the loss channels_last), stored per cell when it is constant along the
+    channels -> (flat fp32 array, div, period)."""
+    a = np.asarray(a, dtype=np.float32)
+    while a.ndim > len(sample_shape) and a.shape[0] == 1:
+        a = a[0]
+    try:
+        full = np.broadcast_to(a, tuple(sample_shape))
+    except ValueError:
+        raise ValueError('%s of shape %s does not broadcast to the model output %s' % (what, a.shape, tuple(sample_shape)))
+    if channels_first and full.ndim == 4:
+        full = np.moveaxis(full, 0, -1)
+    c = full.shape[-1] if full.ndim else 1
+    if c > 1 and np.array_equal(full, np.broadcast_to(full[..., :1], full.shape)):
+        return np.array(full[..., 0]).ravel(), c, full.size // c
+    return np.array(full).ravel(), 1, full.size
+
+
+class DeviceLoss(object):
+    """A DLWP.keras.losses.LossSpec made ready for the kernels of one model output: fp32 weight / climatology fields uploaded
+    to the model's device ONCE (Model.compile), in the channels_last layout the loss is formed in."""
+
+    def __init__(self, spec, sample_shape, channels_first, device):
+        if spec.kind not in _KINDS:
+            raise NotImplementedError('loss kind %r' % (spec.kind,))
+        if spec.regularize not in _REGS:
+            raise NotImplementedError("anomaly-correlation regularize_mean=%r: the DLWP-CS engine builds None / 'mse' / 'mae' / "
+                                      "'global' ('spatial' averages over the layout's last two axes per sample: reference "
+                                      "DLWP/custom.py:1604-1606,1657-1659)" % (spec.regularize,))
+        self.spec = spec
+        self.kind, self.reg, self.reverse = _KINDS[spec.kind], _REGS[spec.regularize], bool(spec.reverse)
+        self.w = self.c = None
+        self.wdiv = self.wper = self.cdiv = self.cper = 0
+        if spec.weights is not None:
+            f, self.wdiv, self.wper = _loss_field(spec.weights, sample_shape, channels_first, 'latitude weight field')
+            self.w = torch.as_tensor(f, device=device)
+        if spec.clim is not None and spec.kind == 'acc':
+            f, self.cdiv, self.cper = _loss_field(spec.clim, sample_shape, channels_first, 'climatology')
+            self.c = torch.as_tensor(f, device=device)
+
+    def desc(self, loss_weight, overwrite):
+        L = nat.LossDesc()
+        L.kind, L.loss_weight, L.regularize, L.reverse, L.overwrite = self.kind, float(loss_weight), self.reg, int(self.reverse), overwrite
+        if self.w is not None:
+            L.weight, L.weight_div, L.weight_period = ptr(self.w), self.wdiv, self.wper
+        if self.c is not None:
+            L.clim, L.clim_div, L.clim_period = ptr(self.c), self.cdiv, self.cper
+        return L
+
+    def fused_ok(self, cout, cells):
+        """Does the fused head (dlwpcs_head_loss_step) serve it: 'mse' / 'mae' with no weight or a per-cell one."""
+        return (self.kind in (nat.LOSS_MSE, nat.LOSS_MAE) and self.c is None
+                and (self.w is None or (self.wdiv == cout and self.wper == cells)))
+
+
+_loss_scratch = {}
+
+
+class _Loss(torch.autograd.Function):
+    """returns a (2,) tensor: [loss_weight * loss, mae] (dlwpcs_loss_fwd_bwd); gradient flows through element 0 only."""
+
+    @staticmethod
+    def forward(ctx, y, t, dl, weight):
+        require_device(y, 'loss')
+        require_device(t, 'loss')
+        if y.shape != t.shape:
+            raise ValueError('loss: shapes differ: %s vs %s' % (tuple(y.shape), tuple(t.shape)))
+        tag = nat.dtype_tag(y)
+        if y.dtype != t.dtype:
+            if t.dtype != torch.float32:
+                raise TypeError('loss: prediction is %s but target is %s' % (y.dtype, t.dtype))
+            tag |= nat.MSE_TARGET_F32
+        for f in (dl.w, dl.c):
+            if f is not None and f.device != y.device:
+                raise ValueError('loss: the loss fields live on %s, the prediction on %s' % (f.device, y.device))
+        per = y[0].numel() if y.dim() > 0 else 1
+        for f, div, period in ((dl.w, dl.wdiv, dl.wper), (dl.c, dl.cdiv, dl.cper)):
+            if f is not None and div * period != per:
+                raise ValueError('loss: field of %d x %d elements for samples of %d' % (period, div, per))
+        y, t = _c(y), _c(t)
+        key = str(y.device)
+        scratch = _loss_scratch.get(key)
+        if scratch is None:
+            scratch = torch.empty(lib().dlwpcs_loss_scratch_bytes(), dtype=torch.uint8, device=y.device)
+            _loss_scratch[key] = scratch
+        out = torch.empty(2, dtype=torch.float32, device=y.device)
+        dy = torch.empty_like(y) if ctx.needs_input_grad[0] else None
+        L = dl.desc(weight, 1)
+        check(lib().dlwpcs_loss_fwd_bwd(ctypes.byref(L), ptr(y), ptr(t), ptr(dy), ptr(out), y.numel(), tag, ptr(scratch),
+                                        stream_ptr()), 'dlwpcs_loss_fwd_bwd')
+        ctx.save_for_backward(dy)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (dy,) = ctx.saved_tensors
+        seed = _unit_seeds.get(str(dout.device))          # (as _MSE.backward)
+        if seed is not None and dout.data_ptr() == seed.data_ptr():
+            return dy, None, None, None
+        return (dy.float() * dout[0]).to(dy.dtype), None, None, None
+
+
+def loss_stats(y, t, spec, weight=1.0):
+    """ops.mse_mae for the loss `spec` (a DeviceLoss): the (2,) stats [weight * loss, mae], gradient through entry 0."""
+    return _Loss.apply(y, t, spec, float(weight))
+
+
 _head_scratch = {}
 
 
-def head_mse_applicable(x, w_eq, ksize, act, target):
+def head_mse_applicable(x, w_eq, ksize, act, target, loss=None):
     """True when the fused training tail (dlwpcs_head_mse_step) serves this output layer + loss: bf16 activations, pointwise
-    kernel on 32 input channels, even C_out in 8..32, no activation, fp32 target, weights packed by the model's pack launch."""
+    kernel on 32 input channels, even C_out in 8..32, no activation, fp32 target, weights packed by the model's pack launch.
+    loss: a DeviceLoss (None: 'mse') -- 'mse' / 'mae', unweighted or with a per-cell weight (dlwpcs_head_loss_step)."""
+    if loss is not None and not (x.dim() == 5 and loss.fused_ok(w_eq.shape[3], 6 * x.shape[2] * x.shape[3])):
+        return False
     if not (DIRECT_PARAM_GRADS and x.is_cuda and x.dtype == torch.bfloat16 and ksize == 1 and act == nat.ACT_NONE):
         return False
     packed = PREPACKED.get(id(w_eq))
@@ -1275,7 +1392,7 @@ class _HeadMSE(torch.autograd.Function):
     leaves dy and dx behind (dlwpcs_head_mse_step), the backward only runs the layer's weight gradient."""
 
     @staticmethod
-    def forward(ctx, x, target, w_eq, w_pol, b_eq, b_pol, weight, flip, premask=None):
+    def forward(ctx, x, target, w_eq, w_pol, b_eq, b_pol, weight, flip, premask=None, loss=None):
         x, target = _c(x), _c(target)
         B, _, N, _, C0 = x.shape
         Cout = w_eq.shape[3]
@@ -1292,7 +1409,15 @@ class _HeadMSE(torch.autograd.Function):
         dx = torch.empty_like(x)
         defer = DEFER_LOSS_TAIL and not _pending_tail          # (one scratch buffer per device: one deferred tail at a time)
         ow = 1 | (nat.HEAD_DEFER_STAGE2 if defer else 0)
-        if premask is not None:
+        if loss is not None:
+            L = loss.desc(weight, ow)
+            check(lib().dlwpcs_head_loss_step(ctypes.byref(d), ctypes.byref(L), ptr(x), ptr(packed[1]),
+                                              ptr(packed[2]) if b_eq is not None else 0, ptr(packed[3]), ptr(target), ptr(dy),
+                                              ptr(dx), ptr(out), ptr(scratch), int(premask is not None),
+                                              float(premask[0]) if premask is not None else 0.0,
+                                              float(premask[1]) if premask is not None else 0.0, stream_ptr()),
+                  'dlwpcs_head_loss_step')
+        elif premask is not None:
             check(lib().dlwpcs_head_mse_step_masked(ctypes.byref(d), ptr(x), ptr(packed[1]),
                                                     ptr(packed[2]) if b_eq is not None else 0, ptr(packed[3]), ptr(target),
                                                     float(weight), ptr(dy), ptr(dx), ptr(out), ow, ptr(scratch),
@@ -1331,11 +1456,12 @@ class _HeadMSE(torch.autograd.Function):
         ws = _workspace(nbytes, dev, 'defer%d' % len(_deferred)) if defer else _workspace(nbytes, dev)
         _weight_gradients(d, x, None, dy, None, ctx.params, None, ws, nbytes, True, defer, need[2:6],
                           False, ctx.params[3] is not None, False)
-        return (dx if need[0] else None), None, None, None, None, None, None, None, None
+        return (dx if need[0] else None), None, None, None, None, None, None, None, None, None
 
 
-def head_mse(x, target, w_eq, w_pol, b_eq, b_pol, weight=1.0, flip_north_pole=True, premask=None):
-    return _HeadMSE.apply(x, target, w_eq, w_pol, b_eq, b_pol, float(weight), bool(flip_north_pole), premask)
+def head_mse(x, target, w_eq, w_pol, b_eq, b_pol, weight=1.0, flip_north_pole=True, premask=None, loss=None):
+    """loss: a DeviceLoss the fused head serves (head_mse_applicable), None: 'mse'."""
+    return _HeadMSE.apply(x, target, w_eq, w_pol, b_eq, b_pol, float(weight), bool(flip_north_pole), premask, loss)
 
 
 def adam_step(p, g, m, v, step_dev, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, zero_grads=False):

@@ -164,6 +164,40 @@ __device__ __forceinline__ uint32_t f2bf2(float lo, float hi) {
     const f2 v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf2));
 }
+
+// ---- per-element arithmetic of the elementwise losses (dlwpcs_loss_desc) ----------------------------------------
+// LK = DLWPCS_LOSS_MSE / DLWPCS_LOSS_MAE, W: a weight field w.  d = y - t in fp32.  s0 += the loss term ((w d)^2 or |w d|),
+// s1 += |d| (the unweighted 'mae' metric); returns dy = gscale * w^2 d (MSE) or gscale * w sign(w d) (MAE, sign(0) = 0 as in
+// TF).  mse_stage1_kernel / mse_stage1_vec_kernel and the fused head (pw_head_train_kernel) all call it: the fused and
+// unfused dy are the same bits.  <MSE, false> is the plain 'mse' arithmetic.
+template <int LK, bool W>
+__device__ __forceinline__ float loss_elem(float d, float w, float gscale, float &s0, float &s1) {
+    if constexpr (LK == DLWPCS_LOSS_MSE && !W) {
+        (void)w;
+        s0 += d * d;
+        s1 += fabsf(d);
+        return gscale * d;
+    } else if constexpr (LK == DLWPCS_LOSS_MSE) {
+        const float wd = w * d;
+        s0 += wd * wd;
+        s1 += fabsf(d);
+        return gscale * (w * wd);
+    } else {
+        const float wd = W ? w * d : d;
+        s0 += fabsf(wd);
+        s1 += fabsf(d);
+        const float sg = wd > 0.f ? 1.f : (wd < 0.f ? -1.f : 0.f);
+        return W ? gscale * (w * sg) : gscale * sg;
+    }
+}
+// a dlwpcs_loss_desc field: value at flat element e = p[(e / div) % per]
+struct LossField {
+    const float *p;
+    uint32_t div, per;
+    __device__ __forceinline__ float at(uint32_t e) const { return p[(e / div) % per]; }
+    __device__ __forceinline__ float at_or(uint32_t e, float dflt) const { return p ? at(e) : dflt; }
+};
+
 static inline size_t dtype_size(int dtype) { return dtype == DLWPCS_BF16 ? 2 : 4; }
 static inline bool dtype_ok(int dtype) { return dtype == DLWPCS_F32 || dtype == DLWPCS_BF16; }
 

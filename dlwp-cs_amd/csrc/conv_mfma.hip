@@ -1203,8 +1203,10 @@ struct HeadParams {
     float m_alpha, m_vmax;
 };
 
-template <int MT>
-__global__ void __launch_bounds__(256) pw_head_train_kernel(HeadParams H) {
+// LK / W: the loss (loss_elem, shared with mse_stage1_kernel): <MT, DLWPCS_LOSS_MSE, false> is pw_head_train_kernel<MT>.
+// W: per-cell loss weight, w of pixel p = wfield[p % wper]
+template <int MT, int LK, bool W>
+__device__ __forceinline__ void pw_head_train_body(const HeadParams &H, const float *__restrict__ wfield, uint32_t wper) {
     const PwParams &P = H.f;
     const int lane = threadIdx.x & 63, n = lane & 15, q = lane >> 4;
     const bf16_t *wlane = P.wpk + (q * 32 + n) * 8;
@@ -1235,6 +1237,7 @@ __global__ void __launch_bounds__(256) pw_head_train_kernel(HeadParams H) {
         uint4 xv[PW_U];
         uint2 xm[PW_U][2];
         float2 tv[PW_U][MT][2];
+        float tw[PW_U];
 #pragma unroll
         for (int u = 0; u < PW_U; ++u) {
             const int g = r.g + u < r.end ? r.g + u : r.end - 1;
@@ -1252,6 +1255,7 @@ __global__ void __launch_bounds__(256) pw_head_train_kernel(HeadParams H) {
                 tv[u][t][0] = co0 + 2 <= Cout ? *reinterpret_cast<const float2 *>(tp) : make_float2(0.f, 0.f);
                 tv[u][t][1] = co0 + 4 <= Cout ? *reinterpret_cast<const float2 *>(tp + 2) : make_float2(0.f, 0.f);
             }
+            tw[u] = W ? wfield[((unsigned)g * 16u + (unsigned)n) % wper] : 1.f;
         }
 #pragma unroll
         for (int u = 0; u < PW_U; ++u) {
@@ -1279,12 +1283,14 @@ __global__ void __launch_bounds__(256) pw_head_train_kernel(HeadParams H) {
                     const float e0 = bf_lo(y01) - tv[u][t][0].x, e1 = bf_hi(y01) - tv[u][t][0].y;
                     const float e2 = bf_lo(y23) - tv[u][t][1].x, e3 = bf_hi(y23) - tv[u][t][1].y;
                     if (co0 + 2 <= Cout) {
-                        sq += e0 * e0; ab += fabsf(e0); sq += e1 * e1; ab += fabsf(e1);
-                        stage[sidx] = f2bf2(H.gscale * e0, H.gscale * e1);
+                        const float g0 = loss_elem<LK, W>(e0, tw[u], H.gscale, sq, ab);
+                        const float g1 = loss_elem<LK, W>(e1, tw[u], H.gscale, sq, ab);
+                        stage[sidx] = f2bf2(g0, g1);
                     }
                     if (co0 + 4 <= Cout) {
-                        sq += e2 * e2; ab += fabsf(e2); sq += e3 * e3; ab += fabsf(e3);
-                        stage[sidx + 1] = f2bf2(H.gscale * e2, H.gscale * e3);
+                        const float g2 = loss_elem<LK, W>(e2, tw[u], H.gscale, sq, ab);
+                        const float g3 = loss_elem<LK, W>(e3, tw[u], H.gscale, sq, ab);
+                        stage[sidx + 1] = f2bf2(g2, g3);
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -1321,6 +1327,14 @@ __global__ void __launch_bounds__(256) pw_head_train_kernel(HeadParams H) {
         __syncthreads();
     }
     if (threadIdx.x == 0) { H.partial[2 * blockIdx.x] = s_sq[0]; H.partial[2 * blockIdx.x + 1] = s_ab[0]; }
+}
+
+template <int MT>
+__global__ void __launch_bounds__(256) pw_head_train_kernel(HeadParams H) { pw_head_train_body<MT, DLWPCS_LOSS_MSE, false>(H, nullptr, 0u); }
+// the other losses of dlwpcs_head_loss_step ('mae', latitude-weighted 'mse' / 'mae')
+template <int MT, int LK, bool W>
+__global__ void __launch_bounds__(256) pw_head_loss_kernel(HeadParams H, const float *wfield, uint32_t wper) {
+    pw_head_train_body<MT, LK, W>(H, wfield, wper);
 }
 
 __global__ void __launch_bounds__(256) head_stage2_kernel(const float *__restrict__ partial, float *__restrict__ loss_out,
@@ -1587,10 +1601,20 @@ extern "C" int dlwpcs_loss_tail_run(const dlwpcs_loss_tail *tail, dlwpcs_stream_
 
 extern "C" size_t dlwpcs_head_mse_scratch_bytes(void) { return (size_t)2048 * 2 * sizeof(float); }
 
+static int head_loss_impl(const dlwpcs_conv_desc *d, const dlwpcs_loss_desc *L, const void *x, const void *wpk_fwd,
+                          const void *bias_pk, const void *wpk_bwd, const float *target, void *dy, void *dx, float *loss_out,
+                          void *scratch, int mask_dx, float m_alpha, float m_vmax, dlwpcs_stream_t stream);
+
 static int head_mse_impl(const dlwpcs_conv_desc *d, const void *x, const void *wpk_fwd, const void *bias_pk,
                          const void *wpk_bwd, const float *target, float weight, void *dy, void *dx,
                          float *loss_out, int overwrite, void *scratch, int mask_dx, float m_alpha, float m_vmax,
-                         dlwpcs_stream_t stream);
+                         dlwpcs_stream_t stream) {
+    dlwpcs_loss_desc L{};
+    L.kind = DLWPCS_LOSS_MSE;
+    L.loss_weight = weight;
+    L.overwrite = overwrite;
+    return head_loss_impl(d, &L, x, wpk_fwd, bias_pk, wpk_bwd, target, dy, dx, loss_out, scratch, mask_dx, m_alpha, m_vmax, stream);
+}
 
 extern "C" int dlwpcs_head_mse_step(const dlwpcs_conv_desc *d, const void *x, const void *wpk_fwd, const void *bias_pk,
                                     const void *wpk_bwd, const float *target, float weight, void *dy, void *dx,
@@ -1607,10 +1631,30 @@ extern "C" int dlwpcs_head_mse_step_masked(const dlwpcs_conv_desc *d, const void
     return head_mse_impl(d, x, wpk_fwd, bias_pk, wpk_bwd, target, weight, dy, dx, loss_out, overwrite, scratch, 1, m_alpha, m_vmax, stream);
 }
 
-static int head_mse_impl(const dlwpcs_conv_desc *d, const void *x, const void *wpk_fwd, const void *bias_pk,
-                         const void *wpk_bwd, const float *target, float weight, void *dy, void *dx,
-                         float *loss_out, int overwrite, void *scratch, int mask_dx, float m_alpha, float m_vmax,
-                         dlwpcs_stream_t stream) {
+extern "C" int dlwpcs_head_loss_step(const dlwpcs_conv_desc *d, const dlwpcs_loss_desc *L, const void *x, const void *wpk_fwd,
+                                     const void *bias_pk, const void *wpk_bwd, const float *target, void *dy, void *dx,
+                                     float *loss_out, void *scratch, int mask_dx, float m_alpha, float m_vmax,
+                                     dlwpcs_stream_t stream) {
+    if (!L) return fail(DLWPCS_E_INVALID, "head_loss_step: null loss descriptor");
+    if (mask_dx && (!(m_alpha >= 0.f) || !(m_vmax >= 0.f)))
+        return fail(DLWPCS_E_INVALID, "head_loss_step: activation needs negative_slope >= 0 and max_value >= 0");
+    return head_loss_impl(d, L, x, wpk_fwd, bias_pk, wpk_bwd, target, dy, dx, loss_out, scratch, mask_dx ? 1 : 0, m_alpha, m_vmax,
+                          stream);
+}
+
+template <int LK, bool W>
+static void head_launch(int Cout, unsigned grid, hipStream_t s, const HeadParams &H, const float *wfield, uint32_t wper) {
+    if constexpr (LK == DLWPCS_LOSS_MSE && !W) {
+        if (Cout <= 16) hipLaunchKernelGGL((pw_head_train_kernel<1>), dim3(grid), dim3(256), 0, s, H);
+        else hipLaunchKernelGGL((pw_head_train_kernel<2>), dim3(grid), dim3(256), 0, s, H);
+    } else {
+        if (Cout <= 16) hipLaunchKernelGGL((pw_head_loss_kernel<1, LK, W>), dim3(grid), dim3(256), 0, s, H, wfield, wper);
+        else hipLaunchKernelGGL((pw_head_loss_kernel<2, LK, W>), dim3(grid), dim3(256), 0, s, H, wfield, wper);
+    }
+}
+static int head_loss_impl(const dlwpcs_conv_desc *d, const dlwpcs_loss_desc *L, const void *x, const void *wpk_fwd,
+                          const void *bias_pk, const void *wpk_bwd, const float *target, void *dy, void *dx, float *loss_out,
+                          void *scratch, int mask_dx, float m_alpha, float m_vmax, dlwpcs_stream_t stream) {
     int rc = validate(d, "head_mse_step");
     if (rc) return rc;
     if (!x || !wpk_fwd || !wpk_bwd || !target || !dy || !dx || !loss_out || !scratch)
@@ -1618,24 +1662,36 @@ static int head_mse_impl(const dlwpcs_conv_desc *d, const void *x, const void *w
     if (!pw_applies(d) || d->act != DLWPCS_ACT_NONE || d->c0_valid != 0)
         return fail(DLWPCS_E_UNSUPPORTED, "head_mse_step: serves the bf16 pointwise head (k = 1, 32 input channels, even C_out in "
                                          "8..32, no activation)");
+    if (L->kind != DLWPCS_LOSS_MSE && L->kind != DLWPCS_LOSS_MAE)
+        return fail(DLWPCS_E_UNSUPPORTED, "head_loss_step: serves 'mse' and 'mae' (kind %d)", L->kind);
+    const long cells = 6L * d->N * d->N;
+    if (L->clim || (L->weight && (L->weight_div != d->Cout || L->weight_period != cells)))
+        return fail(DLWPCS_E_UNSUPPORTED, "head_loss_step: takes a per-cell weight field only (div = C_out, period = 6*N*N)");
+    const int overwrite = L->overwrite;
+    const float weight = L->loss_weight;
     hipStream_t s = (hipStream_t)stream;
     HeadParams H{};
     H.f.in = (const bf16_t *)x; H.f.wpk = (const bf16_t *)wpk_fwd; H.f.bias = (const float *)bias_pk; H.f.out = (bf16_t *)dy;
     H.f.ngroups = (long)d->B * 6 * d->N * d->N / 16; H.f.groups_per_face = d->N * d->N / 16; H.f.Cout = d->Cout;
     H.wpk_bwd = (const bf16_t *)wpk_bwd; H.target = target; H.dx = (bf16_t *)dx; H.partial = (float *)scratch;
     const double n = (double)d->B * 6 * d->N * d->N * d->Cout;
-    H.gscale = (float)(weight * 2.0 / n);
+    H.gscale = (float)(weight * (L->kind == DLWPCS_LOSS_MSE ? 2.0 : 1.0) / n);
     H.mask_dx = mask_dx; H.m_alpha = m_alpha; H.m_vmax = m_vmax;
     const unsigned grid = pw_grid(H.f.ngroups);
+    const bool W = L->weight != nullptr, mae = L->kind == DLWPCS_LOSS_MAE;
     int pidx = -1;
-    if (prof_enabled()) {
+    if (prof_enabled() && !mae && !W) {
+        // (the launch profiler knows the 'mse' instantiations; the other losses' head launches are not profiled)
         Work wk = conv_work(d);
         wk.flops *= 2.0;                                                        // forward + data gradient
         wk.bytes = (double)d->B * 6 * d->N * d->N * (2.0 * 32 * 2 + d->Cout * (4.0 + 2.0));   // x, dx, target, dy
         pidx = prof_begin(d->Cout <= 16 ? KTag<PwHeadName, void, 1>::tag() : KTag<PwHeadName, void, 2>::tag(), wk.flops, wk.bytes, s);
     }
-    if (d->Cout <= 16) hipLaunchKernelGGL((pw_head_train_kernel<1>), dim3(grid), dim3(256), 0, s, H);
-    else hipLaunchKernelGGL((pw_head_train_kernel<2>), dim3(grid), dim3(256), 0, s, H);
+    const uint32_t wper = (uint32_t)cells;
+    if (!mae && !W) head_launch<DLWPCS_LOSS_MSE, false>(d->Cout, grid, s, H, L->weight, wper);
+    else if (!mae) head_launch<DLWPCS_LOSS_MSE, true>(d->Cout, grid, s, H, L->weight, wper);
+    else if (!W) head_launch<DLWPCS_LOSS_MAE, false>(d->Cout, grid, s, H, L->weight, wper);
+    else head_launch<DLWPCS_LOSS_MAE, true>(d->Cout, grid, s, H, L->weight, wper);
     if (pidx >= 0) prof_end(pidx, s);
     // DLWPCS_HEAD_DEFER_STAGE2: the caller finishes the loss (dlwpcs_head_mse_tail + dlwpcs_loss_tail_run, or inside the
     // weight-gradient reduction: dlwpcs_wgrad_batch_adam_tail)

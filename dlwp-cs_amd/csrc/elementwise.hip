@@ -684,19 +684,20 @@ __global__ void __launch_bounds__(256) batch_gather_cf_kernel(const float *__res
 
 // ---------------------------------------------------------------------------------------------------------------
 // keras 'mse' (+ 'mae' metric) with gradient, two-stage fixed-order reduction          (Azure/train_cs.py:424-430)
+// LK / W (dlwpcs_loss_desc): 'mae' and the latitude-weighted forms of both (reference DLWP/custom.py:1543-1578) -- the same
+// kernels with loss_elem's other arithmetic; <float/bf16, .., DLWPCS_LOSS_MSE, false> is the plain 'mse' code.  Stage 2 is shared.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int MSE_BLOCKS = 1024;
 
-template <typename S, typename TT>
+template <typename S, typename TT, int LK = DLWPCS_LOSS_MSE, bool W = false>
 __global__ void __launch_bounds__(256) mse_stage1_kernel(const S *__restrict__ y, const TT *__restrict__ t,
                                                          S *__restrict__ dy, float *__restrict__ partial, size_t n,
-                                                         float gscale) {
+                                                         float gscale, LossField wf) {
     float sq = 0.f, ab = 0.f;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float d = VT<S>::ld(y + i).v[0] - VT<TT>::ld(t + i).v[0];
-        sq += d * d;
-        ab += fabsf(d);
-        if (dy) { Acc<1> g; g.v[0] = gscale * d; VT<S>::st(dy + i, g); }
+        const float g = loss_elem<LK, W>(d, W ? wf.at((uint32_t)i) : 1.f, gscale, sq, ab);
+        if (dy) { Acc<1> a; a.v[0] = g; VT<S>::st(dy + i, a); }
     }
     __shared__ float s_sq[256], s_ab[256];
     s_sq[threadIdx.x] = sq; s_ab[threadIdx.x] = ab;
@@ -708,22 +709,24 @@ __global__ void __launch_bounds__(256) mse_stage1_kernel(const S *__restrict__ y
     if (threadIdx.x == 0) { partial[2 * blockIdx.x] = s_sq[0]; partial[2 * blockIdx.x + 1] = s_ab[0]; }
 }
 
-// 8 elements per lane and iteration (n % 8 == 0): YV / TV = storage vectors of 8 predictions / 8 targets
-template <typename YV, typename TV8>
+// 8 elements per lane and iteration (n % 8 == 0): YV / TV = storage vectors of 8 predictions / 8 targets.  W: the field index
+// of the first element is divided once per iteration and stepped along the 8 (n < 2^32).
+template <typename YV, typename TV8, int LK = DLWPCS_LOSS_MSE, bool W = false>
 __global__ void __launch_bounds__(256) mse_stage1_vec_kernel(const YV *__restrict__ y, const TV8 *__restrict__ t,
                                                              YV *__restrict__ dy, float *__restrict__ partial, size_t n8,
-                                                             float gscale) {
+                                                             float gscale, LossField wf) {
     float sq = 0.f, ab = 0.f;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
         const Acc<8> yv = VT<YV>::ld(y + i);
         const Acc<8> tv = VT<TV8>::ld(t + i);
+        uint32_t q = 0, r = 0;
+        if (W) { const uint32_t e = (uint32_t)i * 8u, c = e / wf.div; q = c % wf.per; r = e - c * wf.div; }
         Acc<8> g;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const float d = yv.v[k] - tv.v[k];
-            sq += d * d;
-            ab += fabsf(d);
-            g.v[k] = gscale * d;
+            g.v[k] = loss_elem<LK, W>(d, W ? wf.p[q] : 1.f, gscale, sq, ab);
+            if (W && ++r == wf.div) { r = 0; if (++q == wf.per) q = 0; }
         }
         if (dy) VT<YV>::st(dy + i, g);
     }
@@ -752,6 +755,104 @@ __global__ void __launch_bounds__(256) mse_stage2_kernel(const float *__restrict
         const float l0 = (float)(s_sq[0] * inv_n) * weight, l1 = (float)(s_ab[0] * inv_n);
         loss_out[0] = overwrite ? l0 : loss_out[0] + l0;
         loss_out[1] = overwrite ? l1 : loss_out[1] + l1;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// anomaly-correlation loss (reference DLWP/custom.py:1581-1676), on p' = w y - c and t' = w t - c:
+//   a = sum p't' / sqrt(sum p'^2 sum t'^2)   (the reference's means cancel),  m = the regulariser,  L = +-m -+ a.
+// Stage 1: per-workgroup partial sums in a fixed order; stage 2: one workgroup, fp64 -> loss_out and three gradient
+// coefficients in device memory; stage 3: dy = w (cA t' + cB p') + the regulariser's term.  No host synchronisation.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int ACC_SUMS = 6;      // {sum p't', sum p'^2, sum t'^2, r0, r1, sum |y - t|}; r0 / r1: see acc_stage1_kernel
+constexpr int ACC_STRIDE = 8;    // floats per workgroup in the scratch
+constexpr int ACC_COEF = MSE_BLOCKS * ACC_STRIDE;    // scratch offset (floats) of the stage-2 coefficients
+
+__device__ __forceinline__ float sgnf(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+
+template <typename S, typename TT>
+__global__ void __launch_bounds__(256) acc_stage1_kernel(const S *__restrict__ y, const TT *__restrict__ t,
+                                                         float *__restrict__ partial, size_t n, LossField wf, LossField cf,
+                                                         int reg) {
+    float a[ACC_SUMS];
+#pragma unroll
+    for (int j = 0; j < ACC_SUMS; ++j) a[j] = 0.f;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float p = VT<S>::ld(y + i).v[0], q = VT<TT>::ld(t + i).v[0];
+        const float w = wf.at_or((uint32_t)i, 1.f), c = cf.at_or((uint32_t)i, 0.f);
+        const float wp = w * p, wt = w * q, pa = wp - c, ta = wt - c, d = p - q, wd = w * d;
+        a[0] += pa * ta; a[1] += pa * pa; a[2] += ta * ta;
+        if (reg == DLWPCS_REG_MSE) a[3] += wd * wd;                 // r0 = sum (w d)^2
+        else if (reg == DLWPCS_REG_MAE) a[3] += fabsf(wd);          // r0 = sum |w d|
+        else if (reg == DLWPCS_REG_GLOBAL) { a[3] += wt; a[4] += wp; }   // r0 = sum w t, r1 = sum w y
+        a[5] += fabsf(d);
+    }
+    __shared__ float s[ACC_SUMS][256];
+#pragma unroll
+    for (int j = 0; j < ACC_SUMS; ++j) s[j][threadIdx.x] = a[j];
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) {
+#pragma unroll
+            for (int j = 0; j < ACC_SUMS; ++j) s[j][threadIdx.x] += s[j][threadIdx.x + st];
+        }
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < ACC_SUMS) partial[ACC_STRIDE * blockIdx.x + threadIdx.x] = s[threadIdx.x][0];
+}
+
+__global__ void __launch_bounds__(256) acc_stage2_kernel(float *__restrict__ partial, int nblocks, double n, float lw, int reg,
+                                                         int reverse, int overwrite, float *__restrict__ loss_out) {
+    __shared__ double s[ACC_SUMS][256];
+    double a[ACC_SUMS];
+#pragma unroll
+    for (int j = 0; j < ACC_SUMS; ++j) a[j] = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 256) {
+#pragma unroll
+        for (int j = 0; j < ACC_SUMS; ++j) a[j] += partial[ACC_STRIDE * i + j];
+    }
+#pragma unroll
+    for (int j = 0; j < ACC_SUMS; ++j) s[j][threadIdx.x] = a[j];
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) {
+#pragma unroll
+            for (int j = 0; j < ACC_SUMS; ++j) s[j][threadIdx.x] += s[j][threadIdx.x + st];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double X = s[0][0], P = s[1][0], T = s[2][0], r0 = s[3][0], r1 = s[4][0];
+        const double rt = sqrt(P * T), acc = X / rt;
+        double m = 0.0, km = 0.0;                   // regulariser and d m / d (w y) per element (times w for 'mse' / 'mae')
+        if (reg == DLWPCS_REG_MSE) { m = r0 / n; km = 2.0 / n; }
+        else if (reg == DLWPCS_REG_MAE) { m = r0 / n; km = 1.0 / n; }
+        else if (reg == DLWPCS_REG_GLOBAL) { const double q = (r0 - r1) / r0; m = fabs(q); km = -(q > 0 ? 1.0 : (q < 0 ? -1.0 : 0.0)) / r0; }
+        const double sa = reverse ? -1.0 : 1.0, sm = reg == DLWPCS_REG_NONE ? 0.0 : (reverse ? 1.0 : -1.0);
+        const float l0 = (float)(lw * (sm * m + sa * acc)), l1 = (float)(s[5][0] / n);
+        loss_out[0] = overwrite ? l0 : loss_out[0] + l0;
+        loss_out[1] = overwrite ? l1 : loss_out[1] + l1;
+        float *coef = partial + ACC_COEF;
+        coef[0] = (float)(lw * sa / rt);            // d a / d p' = t' / sqrt(PT) - a p' / P
+        coef[1] = (float)(-lw * sa * acc / P);
+        coef[2] = (float)(lw * sm * km);
+    }
+}
+
+template <typename S, typename TT>
+__global__ void __launch_bounds__(256) acc_dy_kernel(const S *__restrict__ y, const TT *__restrict__ t, S *__restrict__ dy,
+                                                     size_t n, LossField wf, LossField cf, int reg,
+                                                     const float *__restrict__ coef) {
+    const float cA = coef[0], cB = coef[1], cM = coef[2];
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float p = VT<S>::ld(y + i).v[0], q = VT<TT>::ld(t + i).v[0];
+        const float w = wf.at_or((uint32_t)i, 1.f), c = cf.at_or((uint32_t)i, 0.f);
+        const float pa = w * p - c, ta = w * q - c, wd = w * (p - q);
+        float g = w * (cA * ta + cB * pa);
+        if (reg == DLWPCS_REG_MSE) g += cM * (w * wd);
+        else if (reg == DLWPCS_REG_MAE) g += cM * (w * sgnf(wd));
+        else if (reg == DLWPCS_REG_GLOBAL) g += cM * w;
+        Acc<1> o; o.v[0] = g; VT<S>::st(dy + i, o);
     }
 }
 
@@ -1238,43 +1339,104 @@ extern "C" int dlwpcs_weight_constraint(float *w, int rows, int cols, int kind, 
 }
 
 extern "C" size_t dlwpcs_mse_scratch_bytes(void) { return (size_t)MSE_BLOCKS * 2 * sizeof(float); }
+extern "C" size_t dlwpcs_loss_scratch_bytes(void) { return (size_t)(ACC_COEF + 16) * sizeof(float); }
+
+template <int LK, bool W>
+static void loss_stage1(int dtype, bool t_f32, bool vec, const void *y, const void *t, void *dy, float *partial, size_t n,
+                        size_t g, float gscale, LossField wf, hipStream_t s) {
+    if (vec) {
+        const size_t n8 = n / 8;
+        if (dtype == DLWPCS_BF16 && t_f32)
+            hipLaunchKernelGGL((mse_stage1_vec_kernel<H8, F8, LK, W>), dim3((unsigned)g), dim3(256), 0, s,
+                               (const H8 *)y, (const F8 *)t, (H8 *)dy, partial, n8, gscale, wf);
+        else if (dtype == DLWPCS_BF16)
+            hipLaunchKernelGGL((mse_stage1_vec_kernel<H8, H8, LK, W>), dim3((unsigned)g), dim3(256), 0, s,
+                               (const H8 *)y, (const H8 *)t, (H8 *)dy, partial, n8, gscale, wf);
+        else
+            hipLaunchKernelGGL((mse_stage1_vec_kernel<F8, F8, LK, W>), dim3((unsigned)g), dim3(256), 0, s,
+                               (const F8 *)y, (const F8 *)t, (F8 *)dy, partial, n8, gscale, wf);
+    } else if (dtype == DLWPCS_BF16 && t_f32)
+        hipLaunchKernelGGL((mse_stage1_kernel<bf16_t, float, LK, W>), dim3((unsigned)g), dim3(256), 0, s,
+                           (const bf16_t *)y, (const float *)t, (bf16_t *)dy, partial, n, gscale, wf);
+    else if (dtype == DLWPCS_BF16)
+        hipLaunchKernelGGL((mse_stage1_kernel<bf16_t, bf16_t, LK, W>), dim3((unsigned)g), dim3(256), 0, s,
+                           (const bf16_t *)y, (const bf16_t *)t, (bf16_t *)dy, partial, n, gscale, wf);
+    else
+        hipLaunchKernelGGL((mse_stage1_kernel<float, float, LK, W>), dim3((unsigned)g), dim3(256), 0, s,
+                           (const float *)y, (const float *)t, (float *)dy, partial, n, gscale, wf);
+}
+
+template <typename S, typename TT>
+static void acc_launch(const dlwpcs_loss_desc *L, const void *y, const void *t, void *dy, float *loss_out, size_t n,
+                       float *scratch, LossField wf, LossField cf, hipStream_t s) {
+    size_t g = (n + 255) / 256;
+    if (g > MSE_BLOCKS) g = MSE_BLOCKS;
+    hipLaunchKernelGGL((acc_stage1_kernel<S, TT>), dim3((unsigned)g), dim3(256), 0, s, (const S *)y, (const TT *)t, scratch, n,
+                       wf, cf, L->regularize);
+    hipLaunchKernelGGL(acc_stage2_kernel, dim3(1), dim3(256), 0, s, scratch, (int)g, (double)n, L->loss_weight, L->regularize,
+                       L->reverse ? 1 : 0, L->overwrite & 1, loss_out);
+    if (dy) {
+        size_t g3 = (n + 255) / 256;
+        if (g3 > 2048) g3 = 2048;
+        hipLaunchKernelGGL((acc_dy_kernel<S, TT>), dim3((unsigned)g3), dim3(256), 0, s, (const S *)y, (const TT *)t, (S *)dy, n,
+                           wf, cf, L->regularize, (const float *)(scratch + ACC_COEF));
+    }
+}
+
+static int loss_fwd_bwd_impl(const dlwpcs_loss_desc *L, const void *y, const void *t, void *dy, float *loss_out, size_t n,
+                             int dtype, void *scratch, hipStream_t s) {
+    const bool t_f32 = (dtype & DLWPCS_MSE_TARGET_F32) != 0;
+    dtype &= ~(DLWPCS_MSE_TARGET_F32 | DLWPCS_MSE_OVERWRITE);
+    REQUIRE_DTYPE(dtype, "loss_fwd_bwd");
+    REQUIRE(L && y && t && loss_out && scratch && n > 0, "loss_fwd_bwd: bad arguments");
+    REQUIRE(L->kind >= DLWPCS_LOSS_MSE && L->kind <= DLWPCS_LOSS_ACC, "loss_fwd_bwd: unknown loss kind %d", L->kind);
+    REQUIRE(L->regularize >= DLWPCS_REG_NONE && L->regularize <= DLWPCS_REG_GLOBAL, "loss_fwd_bwd: unknown regulariser %d",
+            L->regularize);
+    REQUIRE(!L->weight || (L->weight_div >= 1 && L->weight_period >= 1), "loss_fwd_bwd: weight field needs div, period >= 1");
+    REQUIRE(!L->clim || (L->clim_div >= 1 && L->clim_period >= 1), "loss_fwd_bwd: climatology needs div, period >= 1");
+    REQUIRE(!L->clim || L->kind == DLWPCS_LOSS_ACC, "loss_fwd_bwd: a climatology belongs to the anomaly-correlation loss");
+    REQUIRE(((!L->weight && !L->clim) || n < (1ull << 32)), "loss_fwd_bwd: fields index at most 2^32 elements");
+    const LossField wf{L->weight, (uint32_t)L->weight_div, (uint32_t)L->weight_period};
+    const LossField cf{L->clim, (uint32_t)L->clim_div, (uint32_t)L->clim_period};
+    float *part = (float *)scratch;
+    if (L->kind == DLWPCS_LOSS_ACC) {
+        if (dtype == DLWPCS_BF16 && t_f32) acc_launch<bf16_t, float>(L, y, t, dy, loss_out, n, part, wf, cf, s);
+        else if (dtype == DLWPCS_BF16) acc_launch<bf16_t, bf16_t>(L, y, t, dy, loss_out, n, part, wf, cf, s);
+        else acc_launch<float, float>(L, y, t, dy, loss_out, n, part, wf, cf, s);
+        return check_launch("loss_fwd_bwd");
+    }
+    const float weight = L->loss_weight;
+    size_t g = (n + 255) / 256;
+    if (g > MSE_BLOCKS) g = MSE_BLOCKS;
+    const float gscale = L->kind == DLWPCS_LOSS_MSE ? weight * 2.f / (float)n : weight / (float)n;
+    const bool al = (((uintptr_t)y | (uintptr_t)t | (uintptr_t)dy) & 31) == 0;
+    const bool vec = n % 8 == 0 && al;
+    if (vec) {
+        g = (n / 8 + 255) / 256;
+        if (g > MSE_BLOCKS) g = MSE_BLOCKS;
+    }
+    const bool W = L->weight != nullptr;
+    if (L->kind == DLWPCS_LOSS_MSE && !W) loss_stage1<DLWPCS_LOSS_MSE, false>(dtype, t_f32, vec, y, t, dy, part, n, g, gscale, wf, s);
+    else if (L->kind == DLWPCS_LOSS_MSE) loss_stage1<DLWPCS_LOSS_MSE, true>(dtype, t_f32, vec, y, t, dy, part, n, g, gscale, wf, s);
+    else if (!W) loss_stage1<DLWPCS_LOSS_MAE, false>(dtype, t_f32, vec, y, t, dy, part, n, g, gscale, wf, s);
+    else loss_stage1<DLWPCS_LOSS_MAE, true>(dtype, t_f32, vec, y, t, dy, part, n, g, gscale, wf, s);
+    hipLaunchKernelGGL(mse_stage2_kernel, dim3(1), dim3(256), 0, s, (const float *)scratch, loss_out, (int)g, 1.f / (float)n,
+                       weight, L->overwrite & 1);
+    return check_launch("loss_fwd_bwd");
+}
+
+extern "C" int dlwpcs_loss_fwd_bwd(const dlwpcs_loss_desc *L, const void *y, const void *t, void *dy, float *loss_out, size_t n,
+                                   int dtype, void *scratch, dlwpcs_stream_t stream) {
+    return loss_fwd_bwd_impl(L, y, t, dy, loss_out, n, dtype, scratch, (hipStream_t)stream);
+}
 
 extern "C" int dlwpcs_mse_fwd_bwd(const void *y, const void *t, void *dy, float *loss_out, size_t n, float weight,
                                   int dtype, void *scratch, dlwpcs_stream_t stream) {
-    const bool t_f32 = (dtype & DLWPCS_MSE_TARGET_F32) != 0;
-    const int overwrite = (dtype & DLWPCS_MSE_OVERWRITE) ? 1 : 0;
-    dtype &= ~(DLWPCS_MSE_TARGET_F32 | DLWPCS_MSE_OVERWRITE);
-    REQUIRE_DTYPE(dtype, "mse_fwd_bwd");
-    REQUIRE(y && t && loss_out && scratch && n > 0, "mse_fwd_bwd: bad arguments");
-    size_t g = (n + 255) / 256;
-    if (g > MSE_BLOCKS) g = MSE_BLOCKS;
-    const float gscale = weight * 2.f / (float)n;
-    const bool al = (((uintptr_t)y | (uintptr_t)t | (uintptr_t)dy) & 31) == 0;
-    if (n % 8 == 0 && al) {
-        const size_t n8 = n / 8;
-        g = (n8 + 255) / 256;
-        if (g > MSE_BLOCKS) g = MSE_BLOCKS;
-        if (dtype == DLWPCS_BF16 && t_f32)
-            hipLaunchKernelGGL((mse_stage1_vec_kernel<H8, F8>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
-                               (const H8 *)y, (const F8 *)t, (H8 *)dy, (float *)scratch, n8, gscale);
-        else if (dtype == DLWPCS_BF16)
-            hipLaunchKernelGGL((mse_stage1_vec_kernel<H8, H8>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
-                               (const H8 *)y, (const H8 *)t, (H8 *)dy, (float *)scratch, n8, gscale);
-        else
-            hipLaunchKernelGGL((mse_stage1_vec_kernel<F8, F8>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
-                               (const F8 *)y, (const F8 *)t, (F8 *)dy, (float *)scratch, n8, gscale);
-    } else if (dtype == DLWPCS_BF16 && t_f32)
-        hipLaunchKernelGGL((mse_stage1_kernel<bf16_t, float>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t *)y, (const float *)t, (bf16_t *)dy, (float *)scratch, n, gscale);
-    else if (dtype == DLWPCS_BF16)
-        hipLaunchKernelGGL((mse_stage1_kernel<bf16_t, bf16_t>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t *)y, (const bf16_t *)t, (bf16_t *)dy, (float *)scratch, n, gscale);
-    else
-        hipLaunchKernelGGL((mse_stage1_kernel<float, float>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
-                           (const float *)y, (const float *)t, (float *)dy, (float *)scratch, n, gscale);
-    hipLaunchKernelGGL(mse_stage2_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float *)scratch, loss_out,
-                       (int)g, 1.f / (float)n, weight, overwrite);
-    return check_launch("mse_fwd_bwd");
+    dlwpcs_loss_desc L{};
+    L.kind = DLWPCS_LOSS_MSE;
+    L.loss_weight = weight;
+    L.overwrite = (dtype & DLWPCS_MSE_OVERWRITE) ? 1 : 0;
+    return loss_fwd_bwd_impl(&L, y, t, dy, loss_out, n, dtype, scratch, (hipStream_t)stream);
 }
 
 extern "C" int dlwpcs_adam_step(float *p, const float *g, float *m, float *v, size_t n, int32_t *step_dev, float lr,

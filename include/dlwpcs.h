@@ -462,6 +462,43 @@ int dlwpcs_head_mse_step_masked(const dlwpcs_conv_desc *d, const void *x, const 
                                 const void *wpk_bwd, const float *target, float weight, void *dy, void *dx, float *loss_out,
                                 int overwrite, void *scratch, float m_alpha, float m_vmax, dlwpcs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------- *
+ * Training losses of the reference's DLWP/custom.py:1543-1676 (and keras 'mae'), with their gradient.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_LOSS_MSE 0            /* weight * mean((w*(y-t))^2)                           keras mean_squared_error */
+#define DLWPCS_LOSS_MAE 1            /* weight * mean(|w*(y-t)|)                              keras mean_absolute_error */
+#define DLWPCS_LOSS_ACC 2            /* weight * anomaly-correlation loss of w*y, w*t against the climatology c */
+#define DLWPCS_REG_NONE   0          /* regularize_mean of the anomaly-correlation loss */
+#define DLWPCS_REG_MSE    1
+#define DLWPCS_REG_MAE    2
+#define DLWPCS_REG_GLOBAL 3
+/* Fields are fp32 device arrays indexed by the flat element index e of y:  field[(e / div) % period].  A field that is constant
+ * along the channels of a channels_last tensor is stored per cell (div = C, period = 6*N*N); a field of one sample's shape has
+ * div = 1, period = the sample's element count.  weight / clim NULL: w = 1 / c = 0.  (The latitude-weighted loss of the reference
+ * scores w*y against w*t: the weight enters an MSE squared.) */
+typedef struct dlwpcs_loss_desc {
+    int kind;                    /* DLWPCS_LOSS_* */
+    float loss_weight;           /* keras loss_weights entry */
+    const float *weight;         /* latitude weight field w, or NULL */
+    int weight_div, weight_period;
+    const float *clim;           /* climatology c (DLWPCS_LOSS_ACC), or NULL */
+    int clim_div, clim_period;
+    int regularize;              /* DLWPCS_REG_* (DLWPCS_LOSS_ACC) */
+    int reverse;                 /* DLWPCS_LOSS_ACC: nonzero -> m - a / -a, else a - m / a */
+    int overwrite;               /* bit 0: loss_out = ... instead of +=;  DLWPCS_HEAD_DEFER_STAGE2 (head step only) */
+} dlwpcs_loss_desc;
+/* loss_out[0] (+)= the loss, loss_out[1] (+)= mean(|y-t|) (the unweighted 'mae' metric); dy = d loss_out[0] / dy (may be NULL).
+ * dtype as for dlwpcs_mse_fwd_bwd (DLWPCS_MSE_TARGET_F32 may be OR-ed in).  n < 2^32.  scratch >= dlwpcs_loss_scratch_bytes().
+ * Deterministic; no host synchronisation (the anomaly-correlation gradient coefficients stay in device memory). */
+size_t dlwpcs_loss_scratch_bytes(void);
+int dlwpcs_loss_fwd_bwd(const dlwpcs_loss_desc *L, const void *y, const void *t, void *dy, float *loss_out, size_t n,
+                        int dtype, void *scratch, dlwpcs_stream_t stream);
+/* dlwpcs_head_mse_step(_masked) for DLWPCS_LOSS_MSE / DLWPCS_LOSS_MAE with an optional per-cell weight field (weight_div = C_out,
+ * weight_period = 6*N*N); mask_dx != 0: the masked form.  The deferred tail is described by dlwpcs_head_mse_tail as before. */
+int dlwpcs_head_loss_step(const dlwpcs_conv_desc *d, const dlwpcs_loss_desc *L, const void *x, const void *wpk_fwd,
+                          const void *bias_pk, const void *wpk_bwd, const float *target, void *dy, void *dx, float *loss_out,
+                          void *scratch, int mask_dx, float m_alpha, float m_vmax, dlwpcs_stream_t stream);
+
 int dlwpcs_adam_step(float *p, const float *g, float *m, float *v, size_t n, int32_t *step_dev,
                      float lr, float beta1, float beta2, float eps, float grad_scale, dlwpcs_stream_t stream);
 /* Same update as one launch: `state_dev` points to TWO device int32 {t-1, 0}; the second is a ticket counter (must be 0
