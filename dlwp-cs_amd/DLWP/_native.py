@@ -95,6 +95,18 @@ class GConvDesc(ctypes.Structure):
                  'flip_north_pole', 'dtype')]
 
 
+SCORE_MSE, SCORE_RMSE, SCORE_MAE, SCORE_ACC, SCORE_COS, SCORE_MEAN = 0, 1, 2, 3, 4, 5
+SCORE_MAX_DIMS = 8
+
+
+class ScoreDesc(ctypes.Structure):
+    """struct dlwpcs_score_desc (include/dlwpcs.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ('method', 'n_lead', 't_len', 't_cap', 't_slope', 'n_keep', 'n_red', 'kc')] + \
+               [('keep_ext', ctypes.c_int64 * SCORE_MAX_DIMS), ('red_ext', ctypes.c_int64 * SCORE_MAX_DIMS),
+                ('lead_stride', ctypes.c_int64 * 4), ('t_stride', ctypes.c_int64 * 4), ('kc_stride', ctypes.c_int64 * 4),
+                ('keep_stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 4), ('red_stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 4)]
+
+
 # name -> (restype, argtypes); must list EVERY symbol of include/dlwpcs.h (tests/test_abi.py checks this)
 PROTOTYPES = {
     'dlwpcs_version': (c_int, []),
@@ -162,6 +174,8 @@ PROTOTYPES = {
     'dlwpcs_loss_fwd_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
     'dlwpcs_head_loss_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int, c_float, c_float, c_void_p]),
+    'dlwpcs_score_scratch_bytes': (c_size_t, [c_void_p]),
+    'dlwpcs_score': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'dlwpcs_adam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,
                                  c_float, c_float, c_float, c_void_p]),
     'dlwpcs_adam_step_fused': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,

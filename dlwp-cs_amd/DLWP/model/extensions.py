@@ -33,8 +33,11 @@ class Forecast(object):
     def shape(self):
         return self.values.shape
 
-    def __array__(self, dtype=None):
-        return np.asarray(self.values, dtype=dtype)
+    def __array__(self, dtype=None, copy=None):
+        v = self.values
+        if hasattr(v, 'detach'):                                  # device-resident values (predict(keep_on_device=True))
+            v = v.detach().cpu().numpy()
+        return np.asarray(v, dtype=dtype)
 
     def isel(self, **indexers):
         idx = [slice(None)] * self.values.ndim
@@ -50,6 +53,13 @@ class Forecast(object):
 
 def _values(x):
     return np.asarray(getattr(x, 'values', x))
+
+
+def _permute(x, axes):
+    """numpy transpose / torch permute of x (axes may be negative)"""
+    if hasattr(x, 'permute'):
+        return x.permute(tuple(a % x.dim() for a in axes))
+    return x.transpose(axes)
 
 
 class TimeSeriesEstimator(object):
@@ -130,8 +140,26 @@ class TimeSeriesEstimator(object):
         extra_t = [t0 + k * self._dt for k in range(have.shape[0], n_rows)]
         return np.concatenate([have, insolation(extra_t, self._lat, self._lon)], axis=0)
 
+    def _lead_rows(self, steps):
+        """data-row offset of every forecast hour of predict(steps) from the initialisation row (f_hour / dt)"""
+        es, iv = self._output_time_steps, self._interval
+        effective_steps = int(np.ceil(int(steps) / es))
+        return np.array([(np.arange(0, es) + iv + e * (es - 1 + iv)) for e in range(effective_steps)]).flatten()[:int(steps)]
+
+    def _f_hour_scale(self, f_hour_timedelta_type):
+        if self._dt is None:
+            return 1.0
+        if f_hour_timedelta_type:
+            return self._dt
+        return float(np.timedelta64(self._dt) / np.timedelta64(1, 'h'))
+
+    def _time_coord(self, samples):
+        if self._sample_times is not None:
+            return self._sample_times[samples] + (self._input_time_steps - 1) * self._dt
+        return samples + (self._input_time_steps - 1)
+
     def predict(self, steps, samples=(), impute=False, keep_time_dim=False, prefer_first_times=True,
-                f_hour_timedelta_type=False, **kwargs):
+                f_hour_timedelta_type=False, keep_on_device=False, **kwargs):
         """
         Step forward the time series prediction from the model 'steps' times, feeding predictions back in as inputs
         (reference extensions.py:162-190).
@@ -140,6 +168,8 @@ class TimeSeriesEstimator(object):
         :param samples: list of int: which samples in the generator to predict for; () = all
         :param keep_time_dim: bool: keep the time_step dimension instead of integrating it with f_hour
         :param f_hour_timedelta_type: bool: f_hour as timedelta instead of float hours
+        :param keep_on_device: bool: `values` is an fp32 device tensor of its own (same layout, dims and coords) and the
+            series is not downloaded
         :return: Forecast with dims ('f_hour', 'time', ['time_step',] 'x0', 'x1', 'x2', 'varlev')
         """
         if int(steps) < 1:
@@ -179,39 +209,89 @@ class TimeSeriesEstimator(object):
             if rollout is not None:
                 series = rollout(plist if len(plist) > 1 else plist[0], sequence_steps, insolation=sol,
                                  start_index=samples if sol is not None else None, io_time_steps=its, verbose=verbose)
-                series = series.cpu().numpy()                      # ONE download: (sequence_steps, n_steps, B, ...)
-                result = np.moveaxis(series, 2, 0)
+                if keep_on_device:
+                    result = series.clone().movedim(2, 0)          # owns its storage: the next rollout reuses the buffers
+                else:
+                    series = series.cpu().numpy()                  # ONE download: (sequence_steps, n_steps, B, ...)
+                    result = np.moveaxis(series, 2, 0)
             else:
                 result = self._host_loop(plist, sequence_steps, sol, samples, **kwargs)
             result = result.reshape((t_shape[0], -1) + t_shape[1:])[:, :effective_steps]
+        if keep_on_device and not hasattr(result, 'permute'):
+            import torch
+            from ..keras import backend
+            result = torch.from_numpy(np.ascontiguousarray(result, dtype=np.float32)).to(backend.device())
         B = result.shape[0]
         space = tuple(g.output_convolution_shape[-self.rank - 1:-1])
         rv = result.reshape((B, effective_steps) + space + (ots, -1))
-        if self._dt is None:
-            dt_h = 1.0
-        elif f_hour_timedelta_type:
-            dt_h = self._dt
-        else:
-            dt_h = float(np.timedelta64(self._dt) / np.timedelta64(1, 'h'))
-        if self._sample_times is not None:
-            time_coord = self._sample_times[samples] + (its - 1) * self._dt
-        else:
-            time_coord = samples + (its - 1)
+        dt_h = self._f_hour_scale(f_hour_timedelta_type)
+        time_coord = self._time_coord(samples)
         grid = [np.arange(d) for d in space]
         xdims = ['x%d' % d for d in range(self.rank)]
         if keep_time_dim:
-            vals = rv.transpose((1, 0, -2) + tuple(range(2, 2 + self.rank)) + (-1,))
+            vals = _permute(rv, (1, 0, -2) + tuple(range(2, 2 + self.rank)) + (-1,))
             f_hour = np.arange(1, effective_steps * (es + iv - 1) + 1, es + iv - 1) * dt_h
             return Forecast(vals, ['f_hour', 'time', 'time_step'] + xdims + ['varlev'],
                             dict(zip(['f_hour', 'time', 'time_step'] + xdims + ['varlev'],
                                      [f_hour, time_coord, np.arange(ots)] + grid + [self._output_sel['varlev']])))
-        vals = rv.transpose((1, -2, 0) + tuple(range(2, 2 + self.rank)) + (-1,)).reshape(
+        vals = _permute(rv, (1, -2, 0) + tuple(range(2, 2 + self.rank)) + (-1,)).reshape(
             (rv.shape[1] * rv.shape[-2], rv.shape[0]) + space + (-1,))
-        f_hour = np.array([(np.arange(0, es) + iv + e * (es - 1 + iv)) for e in range(effective_steps)]).flatten() * dt_h
+        f_hour = self._lead_rows(effective_steps * es) * dt_h
         fc = Forecast(vals, ['f_hour', 'time'] + xdims + ['varlev'],
                       dict(zip(['f_hour', 'time'] + xdims + ['varlev'],
                                [f_hour, time_coord] + grid + [self._output_sel['varlev']])))
         return fc.isel(f_hour=slice(0, steps))
+
+    def verification(self, steps, samples=(), f_hour_timedelta_type=False, keep_on_device=False):
+        """
+        The verification of predict(steps, samples): the engine's counterpart of the reference's verification_from_series
+        (DLWP/verify.py:377-423) for the generator this estimator holds.  Same dims and coords as predict()'s result
+        (keep_time_dim=False layout); the value at (f_hour, time) is the generator's array at the row of time + f_hour (its
+        output variables, channels_last), NaN where that row lies outside the data.  `.lat` is the latitude (dims x0, x1, x2)
+        when the estimator knows it.  keep_on_device: fp32 device values; with a device-resident generator the gather reads
+        HBM only (one dlwpcs_batch_gather launch).
+        """
+        if int(steps) < 1:
+            raise ValueError('must use positive integer for steps')
+        g = self.generator
+        samples = np.arange(g._n_sample, dtype=np.int64) if len(samples) == 0 else np.asarray(samples, dtype=np.int64)
+        lead = self._lead_rows(steps)
+        rows = (samples + self._input_time_steps - 1)[None, :] + lead[:, None]            # (F, B)
+        n_rows = int(g.array.shape[0])
+        bad = (rows < 0) | (rows >= n_rows)
+        space = tuple(g.array.shape[2:])
+        vout = np.asarray(g._output_vars)
+        shape = rows.shape + space + (len(vout),)
+        dev_data = getattr(g, '_dev', None)
+        if keep_on_device and dev_data is not None:
+            import torch
+            from .. import ops
+            dev = dev_data['array'].device
+            idx = torch.from_numpy(np.where(bad, 0, rows).astype(np.int32).reshape(-1)).pin_memory().to(dev, non_blocking=True)
+            vals = torch.empty(shape, dtype=torch.float32, device=dev)
+            ops.batch_gather(dev_data['array'], idx, dev_data['vout'], vals.view((-1,) + space + (len(vout),)), 1, 0, 1, 0, 1,
+                             channels_last=True)
+            if bad.any():
+                where = torch.from_numpy(np.nonzero(bad.reshape(-1))[0]).pin_memory().to(dev, non_blocking=True)
+                vals.view(rows.size, -1).index_fill_(0, where, float('nan'))
+        else:
+            arr = g.array
+            vals = np.full(shape, np.nan, dtype=np.float32)
+            ok = ~bad
+            vals[ok] = np.moveaxis(np.asarray(arr[rows[ok]], dtype=np.float32)[:, vout], 1, -1)
+            if keep_on_device:
+                import torch
+                from ..keras import backend
+                vals = torch.from_numpy(vals).to(backend.device())
+        f_hour = lead * self._f_hour_scale(f_hour_timedelta_type)
+        grid = [np.arange(d) for d in space]
+        xdims = ['x%d' % d for d in range(self.rank)]
+        dims = ['f_hour', 'time'] + xdims + ['varlev']
+        ver = Forecast(vals, dims, dict(zip(dims, [f_hour, self._time_coord(samples)] + grid + [self._output_sel['varlev']])),
+                       name='verification')
+        if self._lat is not None and tuple(np.shape(self._lat)) == space:
+            ver.lat = Forecast(self._lat, xdims, dict(zip(xdims, grid)), name='lat')
+        return ver
 
     def _host_loop(self, plist, sequence_steps, sol, samples, **kwargs):
         """The reference's own loop (extensions.py:268-306) around `model.predict`, for model objects that do not expose

@@ -1527,3 +1527,102 @@ def batch_gather(array, samples, var_idx, out, n_steps, t_off, t_stride, c_off, 
                                     int(n_steps), int(t_off), int(t_stride), ptr(out), Ctot, int(c_off), int(c_stride),
                                     1 if channels_last else 0, nat.dtype_tag(out), stream_ptr()), 'dlwpcs_batch_gather')
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# Forecast verification (DLWP/verify.py): one strided reduction, include/dlwpcs.h dlwpcs_score
+# ------------------------------------------------------------------------------------------------------------------ #
+
+SCORE_METHODS = {'mse': nat.SCORE_MSE, 'rmse': nat.SCORE_RMSE, 'mae': nat.SCORE_MAE, 'acc': nat.SCORE_ACC,
+                 'cos': nat.SCORE_COS, 'mean': nat.SCORE_MEAN}
+
+
+def _coalesce(dims, shape, strides):
+    """[(extent, (stride per operand))] of `dims` in order, adjacent entries merged where every operand allows it."""
+    out = []
+    for i in dims:
+        e, s = int(shape[i]), tuple(int(st[i]) for st in strides)
+        if out and all(ps == cs * e for ps, cs in zip(out[-1][1], s)):
+            out[-1] = (out[-1][0] * e, s)
+        else:
+            out.append((e, s))
+    return out
+
+
+def score_reduce(method, operands, shape, reduced, lagged=None, out_f32=False):
+    """
+    Reduce fp32 device operands [a (forecast), b (verification), c (climatology), w (weights)] -- each None or
+    (tensor, strides in elements over the logical `shape`, 0 = broadcast) -- over the logical dims in `reduced`.
+    lagged=None: every dim is ordinary.  lagged=(t_cap, t_slope): dim 0 is the lead f (kept) and dim 1 the time axis
+    (reduced), of which only the first n_f = min(shape[1], t_cap - t_slope * f) entries take part.
+    Returns a device tensor (float64, or float32 with out_f32) shaped like the kept dims, enqueued on the current stream
+    with no host synchronisation.
+    """
+    m = SCORE_METHODS[method]
+    shape = tuple(int(s) for s in shape)
+    reduced = set(int(r) for r in reduced)
+    strides, ptrs, dev = [], [], None
+    for op in operands:
+        if op is None:
+            strides.append((0,) * len(shape))
+            ptrs.append(0)
+            continue
+        t, st = op
+        require_device(t, 'score')
+        if t.dtype != torch.float32:
+            raise TypeError('score: operands must be float32, got %s' % t.dtype)
+        dev = t.device if dev is None else dev
+        if t.device != dev:
+            raise ValueError('score: operands on %s and %s' % (dev, t.device))
+        strides.append(tuple(int(s) for s in st))
+        ptrs.append(t.data_ptr())
+    if ptrs[1] == 0:
+        raise ValueError('score: the verification operand is required')
+    d = nat.ScoreDesc()
+    d.method = m
+    if lagged is None:
+        first = 0
+        d.n_lead, d.t_len, d.t_cap, d.t_slope = 1, 1, 1, 0
+        out_shape = []
+    else:
+        if 1 not in reduced or 0 in reduced:
+            raise ValueError('score: the lagged form keeps the lead and reduces the time axis')
+        first = 2
+        d.n_lead, d.t_len, d.t_cap, d.t_slope = shape[0], shape[1], int(lagged[0]), int(lagged[1])
+        for k in range(4):
+            d.lead_stride[k], d.t_stride[k] = strides[k][0], strides[k][1]
+        out_shape = [shape[0]]
+    rest = range(first, len(shape))
+    kept = [i for i in rest if i not in reduced]
+    out_shape += [shape[i] for i in kept]
+    if any(shape[i] == 0 for i in kept) or d.n_lead == 0:
+        return torch.empty(out_shape, dtype=torch.float32 if out_f32 else torch.float64, device=dev)
+    kept = [i for i in kept if shape[i] != 1]
+    red = [i for i in rest if i in reduced and shape[i] != 1]
+    kc = 1
+    if kept and red and shape[kept[-1]] in (2, 4) and kept[-1] > red[-1] and \
+            (strides[0][kept[-1]] == 1 or strides[1][kept[-1]] == 1):
+        kc = shape[kept[-1]]
+        for k in range(4):
+            d.kc_stride[k] = strides[k][kept[-1]]
+        kept = kept[:-1]
+    d.kc = kc
+    keep_c, red_c = _coalesce(kept, shape, strides), _coalesce(red, shape, strides)
+    if len(keep_c) > nat.SCORE_MAX_DIMS or len(red_c) > nat.SCORE_MAX_DIMS:
+        raise NotImplementedError('score: more than %d kept or reduced dims after merging' % nat.SCORE_MAX_DIMS)
+    d.n_keep, d.n_red = len(keep_c), len(red_c)
+    for i, (e, s) in enumerate(keep_c):
+        d.keep_ext[i] = e
+        for k in range(4):
+            d.keep_stride[k][i] = s[k]
+    for i, (e, s) in enumerate(red_c):
+        d.red_ext[i] = e
+        for k in range(4):
+            d.red_stride[k][i] = s[k]
+    out = torch.empty(out_shape, dtype=torch.float32 if out_f32 else torch.float64, device=dev)
+    nbytes = int(lib().dlwpcs_score_scratch_bytes(ctypes.byref(d)))
+    scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        check(lib().dlwpcs_score(ctypes.byref(d), ptrs[0] or None, ptrs[1], ptrs[2] or None, ptrs[3] or None, out.data_ptr(),
+                                 1 if out_f32 else 0, ptr(scratch), nbytes, stream_ptr()), 'dlwpcs_score')
+    return out

@@ -499,6 +499,44 @@ int dlwpcs_head_loss_step(const dlwpcs_conv_desc *d, const dlwpcs_loss_desc *L, 
                           const void *bias_pk, const void *wpk_bwd, const float *target, void *dy, void *dx, float *loss_out,
                           void *scratch, int mask_dx, float m_alpha, float m_vmax, dlwpcs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------- *
+ * Forecast verification (reference DLWP/verify.py:18-164: forecast_error, persistence_error, climo_error).  ONE fp32 strided
+ * reduction: operand 0 = a (the forecast x), 1 = b (the verification y), 2 = c (climatology, NULL -> 0), 3 = w (weights,
+ * NULL -> 1), all fp32 device arrays addressed in ELEMENTS by per-operand strides (0 = broadcast).  For every output
+ * (lead f < n_lead, kept index o over keep_ext[], channel k < kc) it reduces every t < n_f = clamp(min(t_len, t_cap - t_slope*f), 0)
+ * and every reduced index r over red_ext[] (the last reduced dim is the row the lanes stream along):
+ *   a[f*lead_stride[0] + t*t_stride[0] + o.keep_stride[0] + r.red_stride[0] + k*kc_stride[0]]   (likewise b, c, w)
+ * Outputs are stored row-major over (f, keep..., k), fp64 (out_f32 = 0) or fp32.  Per method, each term counts its own
+ * non-NaN entries (np.nanmean of each factor) and an empty count gives NaN:
+ *   MSE / RMSE: nanmean(w*d^2) (sqrt), d = y - x      MAE: nanmean(|d*w|)
+ *   ACC: nanmean(w*av*af) / sqrt(nanmean(w*av^2) * nanmean(w*af^2)),  av = y - c, af = x - c
+ *   COS: sum(af*av*w) / (|af*w| * |av*w|), no NaN skipping          MEAN: nanmean(y) (a ignored)
+ * kc (1, 2 or 4) is the kept innermost channel axis handled inside a workgroup (per-variable scores of channels_last data).
+ * At most two launches, no atomics (fixed-order slab partials), bitwise reproducible, no host synchronisation.
+ * scratch >= dlwpcs_score_scratch_bytes(d) (0 when the first launch finishes the outputs itself).
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_SCORE_MSE  0
+#define DLWPCS_SCORE_RMSE 1
+#define DLWPCS_SCORE_MAE  2
+#define DLWPCS_SCORE_ACC  3
+#define DLWPCS_SCORE_COS  4
+#define DLWPCS_SCORE_MEAN 5
+#define DLWPCS_SCORE_MAX_DIMS 8
+typedef struct dlwpcs_score_desc {
+    int32_t method;              /* DLWPCS_SCORE_* */
+    int32_t n_lead;
+    int32_t t_len, t_cap, t_slope;
+    int32_t n_keep, n_red, kc;
+    int64_t keep_ext[DLWPCS_SCORE_MAX_DIMS];
+    int64_t red_ext[DLWPCS_SCORE_MAX_DIMS];
+    int64_t lead_stride[4], t_stride[4], kc_stride[4];
+    int64_t keep_stride[4][DLWPCS_SCORE_MAX_DIMS];
+    int64_t red_stride[4][DLWPCS_SCORE_MAX_DIMS];
+} dlwpcs_score_desc;
+size_t dlwpcs_score_scratch_bytes(const dlwpcs_score_desc *d);
+int dlwpcs_score(const dlwpcs_score_desc *d, const float *a, const float *b, const float *c, const float *w, void *out,
+                 int out_f32, void *scratch, size_t scratch_bytes, dlwpcs_stream_t stream);
+
 int dlwpcs_adam_step(float *p, const float *g, float *m, float *v, size_t n, int32_t *step_dev,
                      float lr, float beta1, float beta2, float eps, float grad_scale, dlwpcs_stream_t stream);
 /* Same update as one launch: `state_dev` points to TWO device int32 {t-1, 0}; the second is a ticket counter (must be 0
