@@ -6,8 +6,8 @@ Metric (BASELINE.json): cubed-sphere samples/sec, forward + backward (+ Adam ste
 variables x 2 time steps = 14 input/output channels (BASELINE config 3: geometry AND dtype -- bf16 compute with fp32
 master weights), batch 32 per GPU, synthetic data, random-init weights.  One "step" = one optimisation step (fwd + bwd +
 gradient all-reduce when N > 1 + Adam) on one batch already resident in HBM.  One process per GPU; N > 1 is launched by
-torch.distributed.run (RCCL).  At N = 1 the same workload is also measured in the exact-fp32 mode (the 1e-5 parity mode)
-and reported under the key "f32".
+torch.distributed.run (RCCL).  With --full, at N = 1 the same workload is also measured in the exact-fp32 mode (the 1e-5
+parity mode) and reported under the key "f32".
 
 Other workloads (same JSON contract, parity-test configurations of BASELINE.json timed by the driver's clock when asked):
   --workload encoder6 --channels 7 --dtype f32     BASELINE config 2 (6-layer encoder, 7 variables, fp32)
@@ -24,7 +24,12 @@ get_weights() order); rollouts -- the final `state` / the `forecast` series.  In
 same arguments give the same inputs on every run; an array above DUMP_MAX_ELEMENTS is written as a fixed, seeded sample of
 its flattened elements.
 
-Prints ONE JSON line on rank 0: value = whole-job samples/s, plus
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line.  --full adds everything else below (each part can still be switched off by its --no-* option): the
+companion dtype, the other configurations (`configs`), the data-parallel form (`dp_form`), the CPU baseline, the roofline with
+its PMC passes, the SMI utilisation and, at N > 1, the all-reduce probes (`exchange.allreduce_us`, `exposed_us`).
+
+Prints ONE JSON line on rank 0: value = whole-job samples/s, plus (--full)
   roofline     -- dominant convolution kernel: algorithmic FLOPs and bytes per launch / HIP-event time per launch (library
                   profiler, events on the launch stream: as event-record nodes INSIDE the replayed step graph for training
                   workloads -- `launch_time_from` -- with the eager figure beside it) against the roofline that bounds it;
@@ -701,10 +706,11 @@ def dp_form_probe(args, dtype, plain_ms):
             torch.distributed.destroy_process_group()
 
 
-def measure(args, dtype, rank, world, with_roofline, with_pmc, pmc_groups=None, dump_dir=None):
+def measure(args, dtype, rank, world, with_roofline, with_pmc, pmc_groups=None, dump_dir=None, probes=False):
     """Build the workload in `dtype`, warm up, time exactly K steps (bracketed by barrier + synchronize, MAX over ranks), dump
     what the last of them computed when `dump_dir` is given, then the optional --blocks, the per-launch roofline pass and the
-    PMC passes.  Returns the result dict on rank 0, None elsewhere."""
+    PMC passes.  `probes` (--full): also the SMI utilisation and, at N > 1, the all-reduce probes after the timed steps.
+    Returns the result dict on rank 0, None elsewhere."""
     N, C, base, B = args.face, args.channels, args.base, args.batch
     st = prepare(args, dtype, rank)
     model, dev = st['model'], st['dev']
@@ -773,16 +779,17 @@ def measure(args, dtype, rank, world, with_roofline, with_pmc, pmc_groups=None, 
                   'steps': args.steps, 'hip_event_ms_per_step': round(e0.elapsed_time(e1) / args.steps, 4),
                   'host_wall_ms_per_step': round(1e3 * step_s, 4),
                   'device_busy_fraction': round(min(1.0, e0.elapsed_time(e1) * 1e-3 / k_elapsed), 4)}
-    try:
-        self_check['smi_utilization_percent'] = int(torch.cuda.utilization(dev))
-    except Exception as exc:                  # amdsmi not importable on the box: say so instead of reporting 0
-        self_check['smi_utilization_percent'] = None
-        self_check['smi_note'] = 'torch.cuda.utilization unavailable: %s' % type(exc).__name__
-    ar_us = allreduce_probe(model, world) if st['train'] else None
+    if probes:
+        try:
+            self_check['smi_utilization_percent'] = int(torch.cuda.utilization(dev))
+        except Exception as exc:              # amdsmi not importable on the box: say so instead of reporting 0
+            self_check['smi_utilization_percent'] = None
+            self_check['smi_note'] = 'torch.cuda.utilization unavailable: %s' % type(exc).__name__
+    ar_us = allreduce_probe(model, world) if (probes and st['train']) else None
     # how much of the exchange the step actually waits for: the same blocks with the all-reduce calls turned into no-ops
     # (DLWP.parallel.SKIP_EXCHANGE_FOR_TIMING: timing only -- the replicas diverge, so this runs after everything that is reported)
     noex_s = None
-    if world > 1 and st['train']:
+    if probes and world > 1 and st['train']:
         noex_s = time_without_exchange(st, timed, args.steps, max(args.warmup, 3))
     # the roofline pass runs eager optimisation steps (gradient all-reduce included): EVERY rank takes part
     agg = roofline_pass(st) if with_roofline else None
@@ -989,6 +996,10 @@ def main():
     ap.add_argument('--min-block-s', type=float, default=0.5, help='minimum duration of a --blocks block')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help='write what the last timed step computed to DIR/<name>.npy (float32, < 64 MB in all)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: companion dtype, other configurations, '
+                         'data-parallel form, CPU baseline, roofline + PMC passes, SMI utilisation, all-reduce probes at N > 1.  '
+                         'The --no-* options below switch parts of it off')
     ap.add_argument('--no-companion', action='store_true',
                     help='skip the second measurement in the other dtype (N = 1 only) reported under "f32" / "bf16"')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -1000,13 +1011,16 @@ def main():
     ap.add_argument('--no-pmc', action='store_true', help='no rocprofv3 child passes (traffic / mfma_busy stay null)')
     ap.add_argument('--no-graphs', action='store_true')
     ap.add_argument('--pmc-out', default=None,
-                    help='also write the per-kernel PMC records of this run to FILE (JSON; tools/make_profiles.py commits it as '
+                    help='--full: also write the per-kernel PMC records of this run to FILE (JSON; tools/make_profiles.py commits it as '
                          'profiles/rNN_*_pmc.json, the fallback source when rocprofv3 cannot run)')
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--pmc-plan', default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full:
+        # a plain run: set up, warm up, time the K steps, dump, print the line -- every other measurement is --full's
+        args.no_companion = args.no_cpu_baseline = args.no_configs = args.no_roofline = args.no_dp_form = args.no_pmc = True
     if args.face is None:
         args.face = 96 if args.workload == 'rollout' else 48
     if args.channels is None:
@@ -1061,7 +1075,7 @@ def main():
     from DLWP.keras import backend
     backend.set_device('cuda:%d' % local_rank)
     single = world == 1
-    # the other workloads of the default line: BASELINE configs 2 and 5 and the reference scripts' production model
+    # the other workloads of the --full line: BASELINE configs 2 and 5 and the reference scripts' production model
     import copy
     cfg_runs = []
     if single and not args.no_configs and args.workload == 'unet2':
@@ -1087,7 +1101,7 @@ def main():
         from DLWP import parallel as _par
         _par.enable_native_comm(os.environ.get('DLWPCS_BENCH_NATIVE_RCCL', '1') == '1')
     result = measure(args, args.dtype, rank, world, with_roofline=not args.no_roofline,
-                     with_pmc=single and not args.no_pmc, dump_dir=args.dump_outputs)
+                     with_pmc=single and not args.no_pmc, dump_dir=args.dump_outputs, probes=args.full)
     if world > 1:
         torch.distributed.barrier()
     if single and not args.no_dp_form and 'rollout' not in args.workload:

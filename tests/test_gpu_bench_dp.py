@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_share_one_gpu():
     env = dict(os.environ, DLWPCS_BENCH_BACKEND='gloo', DLWPCS_BENCH_SHARE_GPU='1', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
-           '127.0.0.1', '--master-port', '29517', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4',
+           '127.0.0.1', '--master-port', '29517', os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '4',
            '--warmup', '3', '--batch', '4', '--face', '16', '--base', '8', '--channels', '6', '--min-block-s', '0.05',
            '--blocks', '3']
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
@@ -281,9 +281,9 @@ def test_roofline_times_the_launches_inside_the_replayed_graph():
     env = dict(os.environ)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '3', '--batch', '4', '--face', '16',
-           '--base', '8', '--channels', '6', '--min-block-s', '0.05', '--blocks', '3', '--no-pmc', '--no-companion',
-           '--no-configs', '--no-cpu-baseline', '--no-dp-form']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '4', '--warmup', '3', '--batch', '4',
+           '--face', '16', '--base', '8', '--channels', '6', '--min-block-s', '0.05', '--blocks', '3', '--no-pmc',
+           '--no-companion', '--no-configs', '--no-cpu-baseline', '--no-dp-form']
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][0])

@@ -12,7 +12,7 @@ for g in "${GS[@]}"; do
   d="$OUT/pass$i"
   echo "$g" > "$OUT/pass$i.counters"
   timeout 600 rocprofv3 --kernel-trace --pmc $g -d "$d" -o p --output-format csv -- \
-      python bench.py --steps 3 --warmup 3 --no-cpu-baseline --no-roofline --no-graphs "$@" > "$OUT/pass$i.log" 2>&1
+      python bench.py --full --steps 3 --warmup 3 --no-cpu-baseline --no-roofline --no-graphs "$@" > "$OUT/pass$i.log" 2>&1
   echo "pass $i ($g): rc=$?"
   i=$((i+1))
 done

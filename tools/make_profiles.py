@@ -2,10 +2,10 @@
 """
 Condense the rocprofv3 outputs of `python bench.py` into the committed summaries under profiles/.
 
-Inputs (written on the GPU box by tools/gpu_profile.sh, merged back under gpurun_out/):
-  gpurun_out/prof_<tag>/r_kernel_trace.csv, r_kernel_stats.csv   rocprofv3 --kernel-trace --stats -- python bench.py ...
-  gpurun_out/bench_<tag>.json                                    the bench line of that same command (un-profiled run)
-  gpurun_out/pmc_<tag>.json                                      bench.py --pmc-out: per-kernel FETCH_SIZE / WRITE_SIZE /
+Inputs (written on the GPU box by `tools/gpu_profile.sh <tag> <dir>`, then brought back as <dir>):
+  <dir>/prof_<tag>/r_kernel_trace.csv, r_kernel_stats.csv        rocprofv3 --kernel-trace --stats -- python bench.py --full ...
+  <dir>/bench_<tag>.json                                         the bench line of that same command (un-profiled run)
+  <dir>/pmc_<tag>.json                                           bench.py --full --pmc-out: per-kernel FETCH_SIZE / WRITE_SIZE /
                                                                  SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE records (live passes)
 Outputs:
   profiles/<tag>_bench_unet2_b32_kernel_summary.txt   per-kernel time per hipGraph-replayed step, both dtypes
@@ -13,7 +13,7 @@ Outputs:
   profiles/<tag>_bench_unet2_b32_benchline.json       the JSON line
   profiles/<tag>_bench_unet2_b32_pmc.json             PMC records (bench.py falls back to the newest of these)
   profiles/<tag>_bench_unet2_b32_pmc.txt              the same as a table (traffic vs algorithmic bytes, MFMA busy)
-usage: tools/make_profiles.py [tag]      (default r02)
+usage: tools/make_profiles.py <tag> <dir>
 """
 import collections
 import csv
@@ -25,7 +25,9 @@ import shutil
 import sys
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TAG = sys.argv[1] if len(sys.argv) > 1 else 'r03'
+if len(sys.argv) != 3:
+    sys.exit(__doc__)
+TAG, SRC = sys.argv[1], os.path.abspath(sys.argv[2])
 PRE = os.path.join(R, 'profiles', '%s_bench_unet2_b32' % TAG)
 
 
@@ -83,8 +85,8 @@ def step_summaries(pdir, modes):
 
 
 def main():
-    pdir = os.path.join(R, 'gpurun_out', 'prof_%s' % TAG)
-    head = 'rocprofv3 --kernel-trace --stats of `python bench.py` on 1 MI355X, '
+    pdir = os.path.join(SRC, 'prof_%s' % TAG)
+    head = 'rocprofv3 --kernel-trace --stats of `python bench.py --full` on 1 MI355X, '
     txt = step_summaries(pdir, ((True, head + 'bf16 mode (headline), hipGraph-replayed steps'),
                                 (False, head + 'f32 mode (companion), hipGraph-replayed steps')))
     open(PRE + '_kernel_summary.txt', 'w').write('\n\n'.join(txt) + '\n')
@@ -95,7 +97,7 @@ def main():
                                                         'rollout = 20 forward passes), eager launches'),
                             ('unet2x2', 'unet2x2_b32', '`python bench.py --workload unet2x2` (the reference scripts\' production model: '
                                                         'integration_steps 2, solar + constants inputs), hipGraph-replayed steps')):
-        d2 = os.path.join(R, 'gpurun_out', 'prof_%s_%s' % (TAG, wl))
+        d2 = os.path.join(SRC, 'prof_%s_%s' % (TAG, wl))
         if glob.glob(os.path.join(d2, '**', '*kernel_trace.csv'), recursive=True):
             t2 = step_summaries(d2, ((None, 'rocprofv3 --kernel-trace --stats of ' + title),))
             pre2 = os.path.join(R, 'profiles', '%s_bench_%s' % (TAG, name))
@@ -106,13 +108,13 @@ def main():
     stats = glob.glob(os.path.join(pdir, '**', '*kernel_stats.csv'), recursive=True)
     if stats:
         shutil.copy(stats[0], PRE + '_kernel_stats.csv')
-    shutil.copy(os.path.join(R, 'gpurun_out', 'bench_%s.json' % TAG), PRE + '_benchline.json')
-    pmc = os.path.join(R, 'gpurun_out', 'pmc_%s.json' % TAG)
+    shutil.copy(os.path.join(SRC, 'bench_%s.json' % TAG), PRE + '_benchline.json')
+    pmc = os.path.join(SRC, 'pmc_%s.json' % TAG)
     if os.path.exists(pmc):
         doc = json.load(open(pmc))
         json.dump(doc, open(PRE + '_pmc.json', 'w'), indent=1, sort_keys=True)
-        bench = json.load(open(os.path.join(R, 'gpurun_out', 'bench_%s.json' % TAG)))
-        lines = ['Per-launch PMC records of `python bench.py` (live rocprofv3 passes, one counter group per pass: %s).' % doc.get('_source', ''),
+        bench = json.load(open(os.path.join(SRC, 'bench_%s.json' % TAG)))
+        lines = ['Per-launch PMC records of `python bench.py --full` (live rocprofv3 passes, one counter group per pass: %s).' % doc.get('_source', ''),
                  'traffic = FETCH_SIZE x 2 (MI355X_MICROARCH.md: gfx950 rocprofv3 reports half of wide coalesced reads) + WRITE_SIZE;',
                  'mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE per XCC x 1024 SIMDs)  (the profiler\'s MfmaUtil).', '']
         for key in sorted(k for k in doc if not k.startswith('_')):
