@@ -107,6 +107,14 @@ class ScoreDesc(ctypes.Structure):
                 ('keep_stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 4), ('red_stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 4)]
 
 
+class SparseMapDesc(ctypes.Structure):
+    """struct dlwpcs_sparse_map_desc (include/dlwpcs.h)"""
+    _fields_ = [('n_a', ctypes.c_int64), ('n_b', ctypes.c_int64), ('nnz', ctypes.c_int64), ('x_dtype', ctypes.c_int32),
+                ('n_outer', ctypes.c_int32), ('outer_ext', ctypes.c_int64 * 3), ('x_outer_stride', ctypes.c_int64 * 3),
+                ('y_outer_stride', ctypes.c_int64 * 3), ('x_space_stride', ctypes.c_int64), ('y_space_stride', ctypes.c_int64),
+                ('inner_ext', ctypes.c_int64), ('x_inner_stride', ctypes.c_int64), ('y_inner_stride', ctypes.c_int64)]
+
+
 # name -> (restype, argtypes); must list EVERY symbol of include/dlwpcs.h (tests/test_abi.py checks this)
 PROTOTYPES = {
     'dlwpcs_version': (c_int, []),
@@ -176,6 +184,7 @@ PROTOTYPES = {
                                       c_void_p, c_void_p, c_int, c_float, c_float, c_void_p]),
     'dlwpcs_score_scratch_bytes': (c_size_t, [c_void_p]),
     'dlwpcs_score': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_sparse_map_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_adam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,
                                  c_float, c_float, c_float, c_void_p]),
     'dlwpcs_adam_step_fused': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,

@@ -1626,3 +1626,101 @@ def score_reduce(method, operands, shape, reduced, lagged=None, out_f32=False):
         check(lib().dlwpcs_score(ctypes.byref(d), ptrs[0] or None, ptrs[1], ptrs[2] or None, ptrs[3] or None, out.data_ptr(),
                                  1 if out_f32 else 0, ptr(scratch), nbytes, stream_ptr()), 'dlwpcs_score')
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# Offline-map remapping (DLWP/remap): one sparse matrix over a strided stack of fields, include/dlwpcs.h dlwpcs_sparse_map_apply
+# ------------------------------------------------------------------------------------------------------------------ #
+
+def _space_stride(shape, strides):
+    """the one stride of the consecutive space dims, or None when they are not one evenly strided run"""
+    run = [(int(e), int(s)) for e, s in zip(shape, strides) if int(e) != 1]
+    for (e0, s0), (e1, s1) in zip(run[:-1], run[1:]):
+        if s0 != s1 * e1:
+            return None
+    return run[-1][1] if run else 1
+
+
+def _fold(dims):
+    """[(extent, x stride, y stride)] with extent-1 dims dropped and neighbours merged where both operands allow it"""
+    out = []
+    for e, xs, ys in dims:
+        if e == 1:
+            continue
+        if out and out[-1][1] == xs * e and out[-1][2] == ys * e:
+            out[-1] = (out[-1][0] * e, xs, ys)
+        else:
+            out.append((e, xs, ys))
+    return out
+
+
+def sparse_map_apply(m, x, space_axes, out=None):
+    """
+    y = m applied to the source grid in the consecutive `space_axes` of the fp32 / bf16 device tensor x (DLWP.remap.OfflineMap;
+    the axes hold m.src_shape, or one axis of m.n_a cells), which the result replaces with m.dst_shape.  One launch on the
+    current stream, no host synchronisation.  `out`: a float32 tensor or view of the result's shape to write into (e.g. a
+    permuted channels_last buffer); otherwise a new contiguous fp32 tensor is returned.
+
+    Views are read and written in place through their strides: after merging, the dim of smallest output stride is the inner
+    dim of the descriptor (lanes span it) when x is also denser along it than along the space axis, and the other dims are up
+    to three outer dims.  Only a layout that cannot be described so -- space axes that are not one evenly strided run, or more
+    than three outer dims -- is copied: x with .contiguous(), and the result through a contiguous temporary that is copied
+    into `out`.
+    """
+    require_device(x, 'sparse_map_apply')
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError('sparse_map_apply: x must be float32 or bfloat16, got %s' % x.dtype)
+    a0, a1 = m._space(tuple(x.shape), space_axes)
+    dev = x.device
+    row_ptr, col, val = m.to(dev)
+    shape = tuple(x.shape[:a0]) + tuple(m.dst_shape) + tuple(x.shape[a1:])
+    b1 = a0 + len(m.dst_shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    else:
+        require_device(out, 'sparse_map_apply')
+        if out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != dev:
+            raise ValueError('sparse_map_apply: out must be a float32 tensor of shape %s on %s, got %s %s on %s'
+                             % (shape, dev, out.dtype, tuple(out.shape), out.device))
+    if out.numel() == 0:
+        return out
+
+    def describe(xv, yv):
+        xs = _space_stride(xv.shape[a0:a1], xv.stride()[a0:a1])
+        ys = _space_stride(yv.shape[a0:b1], yv.stride()[a0:b1])
+        if xs is None or ys is None:
+            return None
+        pre = _fold([(xv.shape[i], xv.stride(i), yv.stride(i)) for i in range(a0)])
+        post = _fold([(xv.shape[i], xv.stride(i), yv.stride(i - a1 + b1)) for i in range(a1, xv.dim())])
+        rest = pre + post
+        # inner (lanes span it): the dim of smallest output stride, if x is also denser along it than along the space axis;
+        # otherwise it becomes the fastest outer dim, whose consecutive slices a lane handles together
+        inner = min(range(len(rest)), key=lambda i: (abs(rest[i][2]), -i)) if rest else None
+        if inner is not None and abs(rest[inner][1]) >= abs(xs):
+            inner = None
+        # outer dims slowest first by x stride: the slices of one lane lie as close together as the layout allows
+        outer = sorted((d for i, d in enumerate(rest) if i != inner), key=lambda d: (abs(d[1]), abs(d[2])), reverse=True)
+        if len(outer) > 3:
+            return None
+        d = nat.SparseMapDesc()
+        d.n_a, d.n_b, d.nnz = m.n_a, m.n_b, m.nnz
+        d.x_dtype = nat.dtype_tag(xv)
+        d.n_outer = len(outer)
+        for i, (e, sx, sy) in enumerate(outer):
+            d.outer_ext[i], d.x_outer_stride[i], d.y_outer_stride[i] = e, sx, sy
+        d.x_space_stride, d.y_space_stride = xs, ys
+        d.inner_ext, d.x_inner_stride, d.y_inner_stride = (rest[inner] if inner is not None else (1, 0, 0))
+        return d
+
+    y = out
+    d = describe(x, y)
+    if d is None:                       # the documented fallback: contiguous operands
+        x = x.contiguous()
+        y = out if out.is_contiguous() else torch.empty(shape, dtype=torch.float32, device=dev)
+        d = describe(x, y)
+    with torch.cuda.device(dev):
+        check(lib().dlwpcs_sparse_map_apply(ctypes.byref(d), row_ptr.data_ptr(), ptr(col), ptr(val), x.data_ptr(),
+                                            y.data_ptr(), stream_ptr()), 'dlwpcs_sparse_map_apply')
+        if y is not out:
+            out.copy_(y)
+    return out

@@ -537,6 +537,30 @@ size_t dlwpcs_score_scratch_bytes(const dlwpcs_score_desc *d);
 int dlwpcs_score(const dlwpcs_score_desc *d, const float *a, const float *b, const float *c, const float *w, void *out,
                  int out_f32, void *scratch, size_t scratch_bytes, dlwpcs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------- *
+ * Offline-map remapping (cubed sphere <-> lat-lon, DLWP/remap): one sparse matrix in CSR form applied to a stack of fields,
+ *   y[o, r, k] = sum_{j in [row_ptr[r], row_ptr[r+1])} val[j] * x[o, col[j], k]      for r < n_b,
+ * the terms of each output added in CSR order with fp32 fma (no atomics, no split rows: bitwise repeatable, and eager and
+ * graph replay give the same bits).  o runs over up to three outer dims, k over at most one inner dim; every dim has its own
+ * stride in ELEMENTS for x and for y, so permuted views need no copy.  Offsets are 64-bit.  x is fp32 or bf16 (x_dtype =
+ * DLWPCS_F32 / DLWPCS_BF16), y and val are fp32.  row_ptr has n_b + 1 entries, col holds 0-based source cells.
+ * The kernel TRUSTS the CSR: row_ptr non-decreasing from 0 to nnz, every col in [0, n_a).  The host validates a map when it
+ * loads it (DLWP.remap.OfflineMap); nothing here re-checks it.
+ * One launch, no host synchronisation, no allocation (capturable).  A zero extent returns DLWPCS_OK without a launch.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct dlwpcs_sparse_map_desc {
+    int64_t n_a, n_b, nnz;              /* source cells, destination rows, CSR entries (nnz < 2^31, n_b * inner_ext < 2^31) */
+    int32_t x_dtype;                    /* DLWPCS_F32 or DLWPCS_BF16 */
+    int32_t n_outer;                    /* 0..3 outer dims */
+    int64_t outer_ext[3];
+    int64_t x_outer_stride[3], y_outer_stride[3];
+    int64_t x_space_stride, y_space_stride;
+    int64_t inner_ext;                  /* 1 when there is no inner dim */
+    int64_t x_inner_stride, y_inner_stride;
+} dlwpcs_sparse_map_desc;
+int dlwpcs_sparse_map_apply(const dlwpcs_sparse_map_desc *d, const int32_t *row_ptr, const int32_t *col, const float *val,
+                            const void *x, float *y, dlwpcs_stream_t stream);
+
 int dlwpcs_adam_step(float *p, const float *g, float *m, float *v, size_t n, int32_t *step_dev,
                      float lr, float beta1, float beta2, float eps, float grad_scale, dlwpcs_stream_t stream);
 /* Same update as one launch: `state_dev` points to TWO device int32 {t-1, 0}; the second is a ticket counter (must be 0
