@@ -115,6 +115,16 @@ class SparseMapDesc(ctypes.Structure):
                 ('inner_ext', ctypes.c_int64), ('x_inner_stride', ctypes.c_int64), ('y_inner_stride', ctypes.c_int64)]
 
 
+GROUP_SLAB_ROWS = 512
+
+
+class RowsDesc(ctypes.Structure):
+    """struct dlwpcs_rows_desc (include/dlwpcs.h)"""
+    _fields_ = [('n_inner', ctypes.c_int32), ('reserved', ctypes.c_int32), ('src_row_stride', ctypes.c_int64),
+                ('out_row_stride', ctypes.c_int64), ('inner_ext', ctypes.c_int64 * SCORE_MAX_DIMS),
+                ('src_stride', ctypes.c_int64 * SCORE_MAX_DIMS), ('out_stride', ctypes.c_int64 * SCORE_MAX_DIMS)]
+
+
 # name -> (restype, argtypes); must list EVERY symbol of include/dlwpcs.h (tests/test_abi.py checks this)
 PROTOTYPES = {
     'dlwpcs_version': (c_int, []),
@@ -184,6 +194,12 @@ PROTOTYPES = {
                                       c_void_p, c_void_p, c_int, c_float, c_float, c_void_p]),
     'dlwpcs_score_scratch_bytes': (c_size_t, [c_void_p]),
     'dlwpcs_score': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_score_indexed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int,
+                                     c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_group_mean_scratch_bytes': (c_size_t, [c_void_p, c_int, ctypes.c_int64, c_int]),
+    'dlwpcs_group_mean': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_rows_gather': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_adam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,
                                  c_float, c_float, c_float, c_void_p]),

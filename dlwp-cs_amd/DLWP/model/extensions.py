@@ -293,6 +293,49 @@ class TimeSeriesEstimator(object):
             ver.lat = Forecast(self._lat, xdims, dict(zip(xdims, grid)), name='lat')
         return ver
 
+    def climatology(self, by='dayofyear', samples=None, keep_on_device=False):
+        """
+        The climatology of the generator's own array over the estimator's output variables, in the layout of predict()'s
+        result: a Forecast with dims (`by`, x0, x1, x2, varlev), `by` = 'dayofyear' or 'month' holding the sorted present keys
+        (DLWP.verify.daily_climatology of the array's rows at `sample_times`).  samples: restrict to these rows of the array.
+        keep_on_device: fp32 device values; with a device-resident generator the channels-first array is reduced in HBM
+        straight into the channels-last result (dlwpcs_group_mean), nothing is copied or uploaded but the row grouping.
+        """
+        from ..verify import _climatology
+        g = self.generator
+        if self._sample_times is None:
+            raise ValueError('TimeSeriesEstimator.climatology: the generator has no dates; pass sample_times')
+        n_rows = int(g.array.shape[0])
+        times = np.asarray(self._sample_times)[:n_rows]
+        if times.shape[0] != n_rows:
+            raise ValueError('TimeSeriesEstimator.climatology: %d sample times for %d rows' % (times.shape[0], n_rows))
+        vout = np.asarray(g._output_vars)
+        dev_data = getattr(g, '_dev', None)
+        arr = dev_data['array'] if keep_on_device and dev_data is not None else g.array
+        step = int(vout[1] - vout[0]) if len(vout) > 1 else 1
+        if len(vout) and step > 0 and np.array_equal(vout, vout[0] + step * np.arange(len(vout))):
+            arr = arr[:, int(vout[0]):int(vout[-1]) + 1:step]   # a view: the output variables are evenly spaced
+        elif hasattr(arr, 'index_select'):
+            arr = arr.index_select(1, dev_data['vout'].long())
+        else:
+            arr = np.asarray(arr)[:, vout]
+        if keep_on_device and not hasattr(arr, 'is_cuda'):
+            import torch
+            from ..keras import backend
+            arr = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).to(backend.device())
+        elif not keep_on_device and not isinstance(arr, np.ndarray):
+            arr = np.asarray(arr)
+        xdims = ['x%d' % d for d in range(self.rank)]
+        src = Forecast(arr, ['time', 'varlev'] + xdims, {'time': times})
+        rows = None if samples is None or len(samples) == 0 else np.asarray(samples, dtype=np.int64)
+        values, keys = _climatology(src, 'time', by, rows=rows, out_perm=(0,) + tuple(range(2, 2 + self.rank)) + (1,))
+        dims = [by] + xdims + ['varlev']
+        grid = [np.arange(d) for d in values.shape[1:-1]]
+        out = Forecast(values, dims, dict(zip(dims, [keys] + grid + [self._output_sel['varlev']])), name='climatology')
+        if self._lat is not None and tuple(np.shape(self._lat)) == tuple(values.shape[1:-1]):
+            out.lat = Forecast(self._lat, xdims, dict(zip(xdims, grid)), name='lat')
+        return out
+
     def _host_loop(self, plist, sequence_steps, sol, samples, **kwargs):
         """The reference's own loop (extensions.py:268-306) around `model.predict`, for model objects that do not expose
         the device-resident rollout (e.g. a wrapped third-party predictor): same bookkeeping, one host round trip per step."""

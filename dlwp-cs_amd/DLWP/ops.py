@@ -1549,16 +1549,26 @@ def _coalesce(dims, shape, strides):
     return out
 
 
-def score_reduce(method, operands, shape, reduced, lagged=None, out_f32=False):
+def score_reduce(method, operands, shape, reduced, lagged=None, out_f32=False, indexed=None):
     """
     Reduce fp32 device operands [a (forecast), b (verification), c (climatology), w (weights)] -- each None or
     (tensor, strides in elements over the logical `shape`, 0 = broadcast) -- over the logical dims in `reduced`.
     lagged=None: every dim is ordinary.  lagged=(t_cap, t_slope): dim 0 is the lead f (kept) and dim 1 the time axis
     (reduced), of which only the first n_f = min(shape[1], t_cap - t_slope * f) entries take part.
+    indexed=(rows, table_row_stride), lagged form only: the climatology operand -- c of 'acc' / 'cos', a of 'mse' / 'rmse' /
+    'mae' -- is a table; `rows` is an int32 device tensor of shape[0] * shape[1] entries, the table row of every (lead, time), and
+    the operand's strides over dims 0 and 1 are 0 (dlwpcs_score_indexed: bitwise the result of the materialised operand).
     Returns a device tensor (float64, or float32 with out_f32) shaped like the kept dims, enqueued on the current stream
     with no host synchronisation.
     """
     m = SCORE_METHODS[method]
+    if indexed is not None:
+        if lagged is None or method == 'mean':
+            raise ValueError('score: the indexed form is the lagged form of a two-operand score')
+        rows, table_stride = indexed
+        if rows.dtype != torch.int32 or not rows.is_cuda or not rows.is_contiguous() or \
+                rows.numel() != int(shape[0]) * int(shape[1]):
+            raise ValueError('score: the row table is a contiguous int32 device tensor of leads x times entries')
     shape = tuple(int(s) for s in shape)
     reduced = set(int(r) for r in reduced)
     strides, ptrs, dev = [], [], None
@@ -1623,8 +1633,122 @@ def score_reduce(method, operands, shape, reduced, lagged=None, out_f32=False):
     nbytes = int(lib().dlwpcs_score_scratch_bytes(ctypes.byref(d)))
     scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev) if nbytes else None
     with torch.cuda.device(dev):
-        check(lib().dlwpcs_score(ctypes.byref(d), ptrs[0] or None, ptrs[1], ptrs[2] or None, ptrs[3] or None, out.data_ptr(),
-                                 1 if out_f32 else 0, ptr(scratch), nbytes, stream_ptr()), 'dlwpcs_score')
+        if indexed is not None:
+            check(lib().dlwpcs_score_indexed(ctypes.byref(d), ptrs[0] or None, ptrs[1], ptrs[2] or None, ptrs[3] or None,
+                                             rows.data_ptr(), int(table_stride), out.data_ptr(), 1 if out_f32 else 0,
+                                             ptr(scratch), nbytes, stream_ptr()), 'dlwpcs_score_indexed')
+        else:
+            check(lib().dlwpcs_score(ctypes.byref(d), ptrs[0] or None, ptrs[1], ptrs[2] or None, ptrs[3] or None,
+                                     out.data_ptr(), 1 if out_f32 else 0, ptr(scratch), nbytes, stream_ptr()), 'dlwpcs_score')
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# Climatologies (DLWP/verify.py): grouped mean over rows and indexed row gather, include/dlwpcs.h dlwpcs_rows_desc
+# ------------------------------------------------------------------------------------------------------------------ #
+
+def _rows_desc(src, row_axis, out_perm, n_out):
+    """(descriptor, output tensor) for rows of `src` along `row_axis`: the output has src's dims in the order `out_perm` (default:
+    as they are) with the row axis n_out long, contiguous.  Unit dims are dropped, neighbours merged where both sides allow it,
+    and the dim that is contiguous in the source goes last (lanes run along it)."""
+    require_device(src, 'rows')
+    if src.dtype != torch.float32:
+        raise TypeError('rows: the source must be float32, got %s' % src.dtype)
+    nd = src.dim()
+    row_axis = row_axis % nd
+    perm = tuple(range(nd)) if out_perm is None else tuple(int(a) % nd for a in out_perm)
+    if sorted(perm) != list(range(nd)):
+        raise ValueError('rows: out_perm %s is not a permutation of %d dims' % (out_perm, nd))
+    out = torch.empty([n_out if a == row_axis else int(src.shape[a]) for a in perm], dtype=torch.float32, device=src.device)
+    dims, out_row = [], 0
+    for pos, a in enumerate(perm):
+        if a == row_axis:
+            out_row = int(out.stride(pos))
+            dims.append(None)                                   # the row axis separates what may merge
+        elif int(src.shape[a]) != 1:
+            cur = (int(src.shape[a]), int(src.stride(a)), int(out.stride(pos)))
+            if dims and dims[-1] is not None and dims[-1][1] == cur[1] * cur[0] and dims[-1][2] == cur[2] * cur[0]:
+                dims[-1] = (dims[-1][0] * cur[0], cur[1], cur[2])
+            else:
+                dims.append(cur)
+    dims = [x for x in dims if x is not None]
+    unit = [i for i, x in enumerate(dims) if x[1] == 1]
+    if unit:
+        dims.append(dims.pop(unit[-1]))
+    if len(dims) > nat.SCORE_MAX_DIMS:
+        raise NotImplementedError('rows: more than %d inner dims after merging' % nat.SCORE_MAX_DIMS)
+    d = nat.RowsDesc()
+    d.n_inner = len(dims)
+    d.src_row_stride, d.out_row_stride = int(src.stride(row_axis)), out_row
+    for i, (e, ss, os_) in enumerate(dims):
+        d.inner_ext[i], d.src_stride[i], d.out_stride[i] = e, ss, os_
+    return d, out
+
+
+def _int32_dev(x, dev):
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).pin_memory().to(dev, non_blocking=True)
+
+
+def group_mean(src, group_start, row_index, row_axis=0, out_perm=None, split=None, counts=False):
+    """
+    Per-element mean over groups of rows of the fp32 device tensor `src` (any strides): group k holds the rows
+    row_index[group_start[k]:group_start[k + 1]] of `row_axis` (numpy int arrays in CSR form, checked here and uploaded).  NaN
+    entries are skipped per element; an element with no member left is NaN.  fp64 sums in a fixed order, rounded to fp32 once.
+    The result has src's dims in the order `out_perm` (default: unchanged) with the row axis K long, contiguous: a channels-first
+    array is reduced straight into a channels-last result.  split: None = the library chooses between one launch and the
+    two-launch slab form, True / False forces it (same bits either way).  counts=True also returns the int32 member counts.
+    At most two launches on the current stream, no host synchronisation.
+    """
+    gs = np.asarray(group_start, dtype=np.int64).reshape(-1)
+    ri = np.asarray(row_index, dtype=np.int64).reshape(-1)
+    if gs.size < 1 or gs[0] != 0 or np.any(np.diff(gs) < 0) or gs[-1] != ri.size:
+        raise ValueError('group_mean: group_start must rise from 0 to len(row_index)')
+    n_rows = int(src.shape[row_axis])
+    if ri.size and (ri.min() < 0 or ri.max() >= n_rows):
+        raise IndexError('group_mean: row index out of range of the %d source rows' % n_rows)
+    K = gs.size - 1
+    d, out = _rows_desc(src, row_axis, out_perm, K)
+    cnt = torch.empty(out.shape, dtype=torch.int32, device=src.device) if counts else None
+    if K == 0 or out.numel() == 0:
+        return (out, cnt) if counts else out
+    longest = int(np.diff(gs).max())
+    flag = -1 if split is None else int(bool(split))
+    dev = src.device
+    with torch.cuda.device(dev):
+        gs_d, ri_d = _int32_dev(gs, dev), _int32_dev(ri if ri.size else np.zeros(1), dev)
+        nbytes = int(lib().dlwpcs_group_mean_scratch_bytes(ctypes.byref(d), K, longest, flag))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        check(lib().dlwpcs_group_mean(ctypes.byref(d), src.data_ptr(), gs_d.data_ptr(), ri_d.data_ptr(), K, longest, flag,
+                                      out.data_ptr(), ptr(cnt), ptr(scratch), nbytes, stream_ptr()), 'dlwpcs_group_mean')
+    return (out, cnt) if counts else out
+
+
+def rows_gather(src, index, row_axis=0, out_perm=None):
+    """
+    out[i] = row index[i] of `row_axis` of the fp32 device tensor `src` (any strides); a negative index gives a NaN row.
+    `index`: numpy ints (checked and uploaded) or an int32 device tensor (trusted).  The result has src's dims in the order
+    `out_perm` with the row axis len(index) long, contiguous.  One launch on the current stream.
+    """
+    n_rows = int(src.shape[row_axis])
+    dev = src.device
+    if isinstance(index, torch.Tensor):
+        if index.dtype != torch.int32 or index.device != dev or not index.is_contiguous():
+            raise TypeError('rows_gather: a device index must be contiguous int32 on the device of the source')
+        idx = index.reshape(-1)
+    else:
+        ih = np.asarray(index, dtype=np.int64).reshape(-1)
+        if ih.size and ih.max() >= n_rows:
+            raise IndexError('rows_gather: row index out of range of the %d source rows' % n_rows)
+        idx = None
+    n = int(idx.numel()) if idx is not None else int(ih.size)
+    d, out = _rows_desc(src, row_axis, out_perm, n)
+    if n == 0 or out.numel() == 0:
+        return out
+    with torch.cuda.device(dev):
+        if idx is None:
+            idx = _int32_dev(ih, dev)
+        check(lib().dlwpcs_rows_gather(ctypes.byref(d), src.data_ptr(), idx.data_ptr(), n, out.data_ptr(), stream_ptr()),
+              'dlwpcs_rows_gather')
     return out
 
 

@@ -3,6 +3,9 @@ Scoring forecasts (reference DLWP/verify.py:18-164: `forecast_error`, `persisten
 cubed-sphere forecast array (behaviour of reference DLWP/verify.py:291-325, pinned by tests/golden/g11_verify.npz:
 dimension names and order, coordinate values, the split of the channel axis into variable x level).
 
+Climatologies (reference DLWP/verify.py:167-214, 426-456: `monthly_climo_error`, `daily_climatology`,
+`daily_climo_time_series`): grouped means over the time axis by month or day of the year, on the device where the values lie.
+
 The engine has no xarray: the labelled result is the `Forecast` record of DLWP.model.extensions (values, dimension names, one
 coordinate array per dimension, `isel`).  `meta_ds` is anything with a `dims` mapping {name: size} and `meta_ds[name]` ->
 coordinate values -- an xarray.Dataset qualifies.
@@ -222,6 +225,46 @@ def _aligned_device(method, f, v, c, w, axis):
     return out.cpu().numpy()
 
 
+def _lookup_serves(lookup, forecast, valid, method, axis):
+    """whether dlwpcs_score_indexed can score this call: device operands with a forecast hour axis each, the table's rows on
+    its first axis, the time axis reduced and the forecast hour kept, rows of a multiple of 4 elements"""
+    if method not in ('acc', 'cos') or len(forecast.shape) != len(valid.shape) or len(forecast.shape) < 2:
+        return False
+    if not _on_device(forecast, valid, lookup.table) or lookup.row_axis != 0:
+        return False
+    nd = len(valid.shape)
+    ax = tuple(range(1, nd)) if axis is None else _axes(axis, nd)
+    if 0 in ax or 1 not in ax:
+        return False
+    if int(np.prod(forecast.shape[2:])) % 4 != 0:
+        # a row of odd length: the array path may merge the time axis into 16-byte chunks that straddle rows, which a lookup
+        # per row cannot follow in the same order -- materialise, so that the bits are those of the array path
+        return False
+    return lookup.rows.shape[-1] == forecast.shape[1] and (lookup.rows.ndim == 1 or lookup.rows.shape[0] == forecast.shape[0])
+
+
+def _indexed_device(method, f, v, lookup, w, axis):
+    """_aligned_device with the climatology looked up by row: the lagged form of the kernel with every time taking part"""
+    import torch
+    dev = (f if f.is_cuda else v).device
+    table = _dev_operand(lookup.table, dev)
+    n_lead, n_time = int(f.shape[0]), int(f.shape[1])
+    series = (n_lead, n_time) + tuple(table.shape[1:])
+    shape = _bshape(*([f.shape, v.shape, series] + ([w.shape] if w is not None else [])))
+    if shape[:2] != (n_lead, n_time):
+        raise ValueError('operands could not be broadcast together: %s and %s' % (tuple(f.shape), tuple(v.shape)))
+    if lookup.rows.ndim == 2:
+        rows = lookup.rows_on(dev)
+    else:
+        rows = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(lookup.rows, (n_lead, n_time))).reshape(-1)
+                                ).pin_memory().to(dev, non_blocking=True)
+    ops = [(f, _bstrides(f, shape)), (v, _bstrides(v, shape)), (table, (0, 0) + _bstrides(table[0], shape[2:])),
+           (w, _bstrides(w, shape)) if w is not None else None]
+    from . import ops as dops
+    out = dops.score_reduce(method, ops, shape, set(axis), lagged=(n_time, 0), indexed=(rows, int(table.stride(0))))
+    return out.cpu().numpy()
+
+
 def _lagged_device(method, a, a_lead, b, c, w, axis, n_lead, t_cap):
     """out[f] = score of a-rows [f*a_lead, ...) against b rows [f, f + n_f) with n_f = min(rows of a, t_cap - f), reduced
     over `axis` of the per-lead (n_f, S...) arrays.  a: (n_lead?, T, S...) when a_lead else (T, S...); b: (V, S...)."""
@@ -271,7 +314,8 @@ def forecast_error(forecast, valid, method='mse', axis=None, weighted=False, cli
     :param method: 'mse', 'mae', 'rmse', 'acc' (anomaly correlation) or 'cos' (cosine similarity; labelled inputs)
     :param axis: int, tuple or None: axes to average over (None: every axis but the forecast hour)
     :param weighted: weight by cos(latitude) read from `valid.lat`
-    :param climatology: climatology for 'acc' / 'cos'
+    :param climatology: climatology for 'acc' / 'cos': a number, an array, or a `ClimatologyLookup`
+        (`daily_climo_time_series(..., lazy=True)`), whose rows are looked up inside the score on the device
     :return: float64 ndarray with forecast hour as the first dimension
     """
     assert method in _METHODS, _METHOD_MSG
@@ -279,6 +323,12 @@ def forecast_error(forecast, valid, method='mse', axis=None, weighted=False, cli
         warnings.warn("'acc' and 'cos' error methods expect to get a climatology; using 0 instead, which may yield "
                       "unexpected results.")
         climatology = 0.
+    lookup = None
+    if isinstance(climatology, ClimatologyLookup):
+        if _lookup_serves(climatology, forecast, valid, method, axis):
+            lookup, climatology = climatology, climatology.table
+        else:                                              # the host path, and axes the indexed kernel does not serve
+            climatology = climatology.materialize()
     _check_labels(forecast, valid)
     n_f = forecast.shape[0]
     w = _weights(valid) if weighted else None
@@ -300,6 +350,8 @@ def forecast_error(forecast, valid, method='mse', axis=None, weighted=False, cli
             f, v = _dev_operand(forecast, dev), _dev_operand(valid, dev)
             c = _const_operand(climatology, dev) if method in ('acc', 'cos') else None
             wt = _dev_operand(w, dev) if w is not None else None
+            if lookup is not None:
+                return np.asarray(_indexed_device(method, f, v, lookup, wt, ax), dtype=np.float64)
             return np.asarray(_aligned_device(method, f, v, c, wt, ax), dtype=np.float64)
     # valid given as a continuous time series without a forecast hour dimension
     clim_shape = np.shape(_raw(climatology)) if climatology is not None else ()
@@ -415,3 +467,306 @@ def climo_error(valid, n_fhour, method='mse', axis=None, weighted=False):
         red = {1} | (set(range(2, len(shape))) if ax is None else set(a + 1 for a in ax if a > 0))
         out = dops.score_reduce(method, ops, shape, red, lagged=(n_f, 1))
         return np.asarray(out.cpu().numpy(), dtype=np.float64)
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# Climatologies (reference DLWP/verify.py:167-214 monthly_climo_error, :426-456 daily_climatology / daily_climo_time_series)
+# --------------------------------------------------------------------------------------------------------------------- #
+
+_BY = ('dayofyear', 'month')
+
+
+def calendar_keys(times, by='dayofyear'):
+    """int64 month (1..12) or day of the year (1 January = 1, so 29 February = 60 and 31 December of a leap year = 366) of
+    every datetime64 in `times`: numpy datetime64 arithmetic only"""
+    if by not in _BY:
+        raise ValueError("'by' must be 'dayofyear' or 'month'")
+    t = np.asarray(getattr(times, 'values', times))
+    if t.dtype.kind != 'M':
+        raise TypeError('the time coordinate must be datetime64, got %s' % t.dtype)
+    if by == 'month':
+        return t.astype('datetime64[M]').astype(np.int64) % 12 + 1
+    day = t.astype('datetime64[D]')
+    return (day - day.astype('datetime64[Y]').astype('datetime64[D]')).astype(np.int64) + 1
+
+
+def _coord(x, name):
+    c = x.coords[name]
+    return np.asarray(getattr(c, 'values', c))
+
+
+def _csr(keys):
+    """(sorted present keys, group_start, row_index): rows grouped by key, in time order inside a group"""
+    uniq, inv = np.unique(keys, return_inverse=True)
+    order = np.argsort(inv.reshape(-1), kind='stable')
+    start = np.concatenate([[0], np.cumsum(np.bincount(inv.reshape(-1), minlength=len(uniq)))])
+    return uniq.astype(np.int64), start.astype(np.int64), order.astype(np.int64)
+
+
+def _group_mean_host(v, axis, start, order, out_perm=None):
+    """the formula of dlwpcs_group_mean in numpy: per element, the fp64 sum of the non-NaN members over their count, one
+    rounding to fp32; an element with no member is NaN"""
+    x = np.moveaxis(np.asarray(v), axis, 0)
+    out = np.empty((len(start) - 1,) + x.shape[1:], dtype=np.float32)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        for k in range(len(start) - 1):
+            rows = np.asarray(x[order[start[k]:start[k + 1]]], dtype=np.float64)
+            ok = ~np.isnan(rows)
+            n = ok.sum(axis=0)
+            out[k] = np.where(n > 0, np.where(ok, rows, 0.).sum(axis=0) / np.maximum(n, 1), np.nan)
+    out = np.moveaxis(out, 0, axis)
+    return out if out_perm is None else np.ascontiguousarray(out.transpose(out_perm))
+
+
+def _climatology(ds, time_dim, by, rows=None, out_perm=None):
+    """grouped mean of ds.values over `time_dim` (rows: restrict to these positions) -> (values, present keys)"""
+    dims = tuple(ds.dims)
+    if time_dim not in dims:
+        raise ValueError("the data has no '%s' dimension (dims: %s)" % (time_dim, ', '.join(dims)))
+    axis = dims.index(time_dim)
+    times = _coord(ds, time_dim)
+    v = _raw(ds)
+    if times.shape[0] != v.shape[axis]:
+        raise ValueError("the '%s' coordinate has %d entries but its axis %d" % (time_dim, times.shape[0], v.shape[axis]))
+    sel = np.arange(times.shape[0]) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
+    uniq, start, order = _csr(calendar_keys(times[sel], by))
+    order = sel[order]
+    if _is_tensor(v) and v.is_cuda:
+        import torch
+        from . import ops as dops
+        with torch.cuda.device(v.device):
+            src = v if v.dtype == torch.float32 else v.to(torch.float32)
+            return dops.group_mean(src, start, order, row_axis=axis, out_perm=out_perm), uniq
+    return _group_mean_host(_host(v), axis, start, order, out_perm), uniq
+
+
+def _relabel(ds, old, new, values, coord, name):
+    dims = tuple(new if d == old else d for d in ds.dims)
+    coords = {}
+    for d in ds.dims:
+        if d == old:
+            coords[new] = coord
+        elif d in ds.coords:
+            coords[d] = _coord(ds, d)
+    out = Forecast(values, dims, coords, name=name)
+    if hasattr(ds, 'lat'):
+        out.lat = ds.lat
+    return out
+
+
+def daily_climatology(ds, *, by='dayofyear'):
+    """
+    Generate a daily climatology from labelled data with a 'time' dimension (reference DLWP/verify.py:426-433:
+    `ds.groupby('time.dayofyear').mean()`): per element, the mean over the times of each day of the year, NaN skipped.
+
+    :param ds: a `Forecast`, or anything with `.dims`, `.coords` and `.values`; 'time' (datetime64 coordinate) on any axis.
+        Values on a HIP device are reduced there (dlwpcs_group_mean) and the result stays there; numpy values are reduced on the
+        host in fp64.
+    :param by: 'dayofyear' or 'month' (the grouping `monthly_climo_error` uses)
+    :return: Forecast, fp32, with the 'time' dimension replaced by `by`; its coordinate holds the sorted present keys (int64)
+    """
+    values, uniq = _climatology(ds, 'time', by)
+    return _relabel(ds, 'time', by, values, uniq, 'climatology')
+
+
+def _lead_hours(f_hour):
+    """timedelta64[h] of every forecast hour: the reference's np.array(f).astype('timedelta64[h]') (:449), floats truncated"""
+    f = np.asarray(getattr(f_hour, 'values', f_hour))
+    if f.dtype.kind == 'f':
+        f = np.trunc(f).astype(np.int64)
+    return f.astype('timedelta64[h]')
+
+
+class ClimatologyLookup(object):
+    """
+    A climatology time series that is not laid out: the (K, ...) climatology `table`, and for every (forecast hour,) time the
+    row of the table that stands there (`rows`, int32).  It has the dims, coords and shape of the series it stands for;
+    `materialize()` builds that series.  `forecast_error` takes it as `climatology` and looks the rows up inside the score.
+    """
+
+    def __init__(self, table, row_axis, rows, dims, coords, name='climatology'):
+        self.table = table
+        self.row_axis = int(row_axis)
+        self.rows = np.ascontiguousarray(rows, dtype=np.int32)
+        self.dims = tuple(dims)
+        self.coords = dict(coords)
+        self.name = name
+        self._rows_dev = None
+
+    @property
+    def shape(self):
+        t = tuple(int(s) for s in _raw(self.table).shape)
+        series = t[:self.row_axis] + (self.rows.shape[-1],) + t[self.row_axis + 1:]
+        return (self.rows.shape[0],) + series if self.rows.ndim == 2 else series
+
+    def rows_on(self, dev):
+        """the row table as an int32 device tensor (uploaded once)"""
+        if self._rows_dev is None or self._rows_dev.device != dev:
+            import torch
+            self._rows_dev = torch.from_numpy(self.rows.reshape(-1)).pin_memory().to(dev, non_blocking=True)
+        return self._rows_dev
+
+    def materialize(self):
+        """the series itself: a Forecast of `shape` (device values: one dlwpcs_rows_gather launch)"""
+        t = _raw(self.table)
+        ax, lead = self.row_axis, self.rows.ndim == 2
+        split = tuple(t.shape[:ax]) + tuple(self.rows.shape) + tuple(t.shape[ax + 1:])
+        if _is_tensor(t) and t.is_cuda:
+            import torch
+            from . import ops as dops
+            with torch.cuda.device(t.device):
+                src = t if t.dtype == torch.float32 else t.to(torch.float32)
+                v = dops.rows_gather(src, self.rows_on(t.device), row_axis=ax).reshape(split)
+            v = v.movedim(ax, 0) if lead else v
+        else:
+            v = np.take(np.asarray(_host(t), dtype=np.float32), self.rows.reshape(-1), axis=ax).reshape(split)
+            v = np.moveaxis(v, ax, 0) if lead else v
+        return Forecast(v, self.dims, self.coords, name=self.name)
+
+
+def daily_climo_time_series(climatology, times, f_hour=None, *, lazy=False):
+    """
+    Generate a time series of daily climatology values from a climatology and the desired times (reference
+    DLWP/verify.py:436-456): the value at (f, t) is the climatology of the day of the year of t + f hours.
+
+    :param climatology: labelled climatology with a 'dayofyear' dimension (`daily_climatology`)
+    :param times: datetime64 times
+    :param f_hour: None, or forecast hours as ints / floats / timedelta64
+    :param lazy: True returns a `ClimatologyLookup` instead of the series (nothing of the series' size is allocated)
+    :return: Forecast with the 'dayofyear' dimension replaced by 'time' (behind a leading 'f_hour' when given), coordinates
+        `times` / `f_hour`.  A day the climatology does not hold raises KeyError naming it.
+    """
+    dims = tuple(climatology.dims)
+    if 'dayofyear' not in dims:
+        raise ValueError("the climatology has no 'dayofyear' dimension (dims: %s)" % ', '.join(dims))
+    axis = dims.index('dayofyear')
+    have = _coord(climatology, 'dayofyear').astype(np.int64)
+    t = np.asarray(getattr(times, 'values', times))
+    if t.dtype.kind != 'M':
+        t = t.astype('datetime64[ns]')
+    if f_hour is None:
+        when = t
+    else:
+        when = t.astype('datetime64[s]')[None, :] + _lead_hours(f_hour).astype('timedelta64[s]')[:, None]
+    doy = calendar_keys(when, 'dayofyear')
+    rows = _sel_rows(have, doy, 'dayofyear')
+    out_dims = tuple('time' if d == 'dayofyear' else d for d in dims)
+    coords = {d: _coord(climatology, d) for d in dims if d != 'dayofyear' and d in climatology.coords}
+    coords['time'] = t
+    if f_hour is not None:
+        out_dims = ('f_hour',) + out_dims
+        coords['f_hour'] = np.asarray(getattr(f_hour, 'values', f_hour))
+    look = ClimatologyLookup(_raw(climatology), axis, rows, out_dims, coords)
+    return look if lazy else look.materialize()
+
+
+def _sel_rows(labels, wanted, what):
+    """position of every wanted label in `labels` (exact match, as .sel); KeyError names the first that is missing"""
+    order = np.argsort(labels, kind='stable')
+    srt = labels[order]
+    flat = np.asarray(wanted).reshape(-1)
+    if len(srt) == 0:
+        if flat.size:
+            raise KeyError('%s %s is not in the data' % (what, flat[0]))
+        return np.zeros(np.shape(wanted), dtype=np.int32)
+    pos = np.minimum(np.searchsorted(srt, flat), len(srt) - 1)
+    miss = srt[pos] != flat
+    if miss.any():
+        raise KeyError('%s %s is not in the data' % (what, flat[np.argmax(miss)]))
+    return order[pos].astype(np.int32).reshape(np.shape(wanted))
+
+
+def monthly_climo_error(da, val_set, n_fhour=None, method='mse', climo_da=None, by_day_of_year=False, return_da=False,
+                        weighted=False):
+    """
+    Calculates a month-aware climatology error for a validation set (reference DLWP/verify.py:167-214).
+
+    :param da: labelled data with a 'time' or 'sample' dimension ('sample' is preferred) with a datetime64 coordinate
+    :param val_set: times for which to calculate an error; each must be a time of `da` (KeyError otherwise)
+    :param n_fhour: int or None: if int, the error is repeated into an array of length n_fhour
+    :param method: 'mse', 'mae', 'rmse'; 'acc' and 'cos' return zeros
+    :param climo_da: pre-computed monthly or daily climatology (dimension 'month' / 'dayofyear' in place of the time dimension)
+    :param by_day_of_year: climatology by day of year instead of monthly
+    :param return_da: also return the anomaly (a Forecast with the dims of `da`, its time dimension = val_set)
+    :param weighted: weight by cos(latitude) read from `da.lat`
+    :return: float or ndarray[, Forecast].  Device values are scored by one dlwpcs_score_indexed call.
+    """
+    assert method in _METHODS, _METHOD_MSG
+    dims = tuple(da.dims)
+    time_dim = 'sample' if 'sample' in dims else 'time'
+    parameter = 'dayofyear' if by_day_of_year else 'month'
+    if time_dim not in dims:
+        raise ValueError("the data has no 'sample' or 'time' dimension (dims: %s)" % ', '.join(dims))
+    axis = dims.index(time_dim)
+    times = _coord(da, time_dim)
+    if climo_da is None:
+        table, keys = _climatology(da, time_dim, parameter)
+    else:
+        want = tuple(parameter if d == time_dim else d for d in dims)
+        if tuple(climo_da.dims) != want:
+            raise ValueError('the climatology has dims %s, expected %s' % (tuple(climo_da.dims), want))
+        table, keys = _raw(climo_da), _coord(climo_da, parameter).astype(np.int64)
+    wanted = np.asarray(getattr(val_set, 'values', val_set)).reshape(-1)
+    if wanted.dtype.kind != 'M':
+        wanted = wanted.astype(times.dtype)
+    sel = _sel_rows(times, wanted.astype(times.dtype), time_dim).astype(np.int64)
+    rows = _sel_rows(keys, calendar_keys(times[sel], parameter), parameter)
+    w = _weights(da) if weighted else None
+    if w is not None and np.ndim(w) == len(dims):
+        w = np.moveaxis(w, axis, 0)                        # beside the time-first views below
+    device = _on_device(da, table)
+    anomaly = None
+    if method in ('acc', 'cos') and not return_da:
+        me = 0.
+    elif device:
+        me, anomaly = _climo_error_device(method, _raw(da), table, axis, sel, rows, w, return_da)
+    else:
+        x = np.asarray(np.moveaxis(_host(da), axis, 0)[sel], dtype=np.float64)
+        anomaly = x - np.asarray(np.moveaxis(_host(table), axis, 0)[rows], dtype=np.float64)
+        wh = 1. if w is None else w
+        me = 0. if method in ('acc', 'cos') else float(_score_host(method, 0., anomaly, 0., wh, None))
+        anomaly = np.moveaxis(anomaly.astype(np.float32), 0, axis)
+    if method == 'rmse':
+        me = np.sqrt(me) if device else np.float64(me)
+    if n_fhour is not None:
+        me = np.array([me] * n_fhour)
+    if return_da:
+        coords = {d: _coord(da, d) for d in dims if d in da.coords}
+        coords[time_dim] = times[sel]
+        return me, Forecast(anomaly, dims, coords, name='anomaly')
+    return me
+
+
+def _climo_error_device(method, v, table, axis, sel, rows, w, want_anomaly):
+    """the score of v's rows `sel` (time axis `axis`) against the table rows `rows`, on the device: (float, anomaly or None)"""
+    import torch
+    from . import ops as dops
+    dev = next(x.device for x in (v, table) if _is_tensor(x) and x.is_cuda)
+    with torch.cuda.device(dev):
+        vt, tt = _dev_operand(v, dev).movedim(axis, 0), _dev_operand(table, dev).movedim(axis, 0)
+        step = int(sel[1] - sel[0]) if len(sel) > 1 else 1
+        if len(sel) and step > 0 and np.array_equal(sel, sel[0] + step * np.arange(len(sel))):
+            b = vt[int(sel[0]):int(sel[-1]) + 1:step]         # a view: the selected rows are evenly spaced
+        else:
+            b = dops.rows_gather(vt, sel, row_axis=0)
+        anomaly = None
+        if want_anomaly:
+            anomaly = (b - dops.rows_gather(tt, rows, row_axis=0)).movedim(0, axis)
+        if method in ('acc', 'cos'):
+            return 0., anomaly
+        n = int(b.shape[0])
+        shape = (1, n) + tuple(int(s) for s in b.shape[1:])
+        ops_ = [(tt, (0, 0) + tuple(int(s) for s in tt.stride()[1:])), (b, (0,) + tuple(int(s) for s in b.stride())), None]
+        if w is not None:
+            wt = _dev_operand(w, dev)
+            ws = wt.reshape(tuple(wt.shape[1:])) if wt.dim() == b.dim() and wt.shape[0] == 1 else wt
+            if ws.dim() >= b.dim():
+                raise ValueError('the weights of %s do not broadcast against the data behind its time axis' % (tuple(wt.shape),))
+            ops_.append((ws, (0, 0) + _bstrides(ws, shape[2:])))
+        else:
+            ops_.append(None)
+        idx = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).pin_memory().to(dev, non_blocking=True)
+        kind = 'mse' if method == 'rmse' else method            # the reference takes the root of a Python float (:203)
+        out = dops.score_reduce(kind, ops_, shape, set(range(1, len(shape))), lagged=(n, 0),
+                                indexed=(idx, int(tt.stride(0))))
+        return float(out.cpu().numpy().reshape(-1)[0]), anomaly

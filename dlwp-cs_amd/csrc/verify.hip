@@ -11,6 +11,10 @@
 //
 // Vector path: when a and b are contiguous along the row (row stride = kc, channel stride 1) and every row starts on 16 B, a lane
 // reads one float4 of each per chunk; slot j of the float4 belongs to channel j % kc (kc = 1, 2 or 4).
+//
+// Indexed form (dlwpcs_score_indexed, IDX instantiations): one operand is a (K, inner...) table whose row for (lead f, time t)
+// is row_tab[f * t_len + t] -- one load where a row's offsets are computed, nothing else differs, so the plan, the slabs
+// and the order of every sum are those of the materialised operand.  Which operand it is follows from the method (idx_operand).
 #include <string.h>
 #include "common.h"
 
@@ -34,6 +38,8 @@ struct ScoreGeom {
     int64_t outer_stride[4][DLWPCS_SCORE_MAX_DIMS];
     int32_t slabs, has_c, has_w, out_f32;
     int32_t cmode, wmode;                       // vector path: how c / w are read (AUX_*)
+    int32_t idx_op;                             // indexed form: the operand looked up by row (idx_operand), else -1
+    int64_t idx_stride;                         // indexed form: elements between rows of its table
     int64_t nblk;                               // workgroups of the launch (the grid may round up)
 };
 
@@ -75,10 +81,16 @@ __device__ __forceinline__ int64_t n_rows_of(const ScoreGeom &G, int f) {
 }
 
 // offsets of row r (t, outer reduced coordinates) relative to the group base
-__device__ __forceinline__ void row_offsets(const ScoreGeom &G, int64_t r, const int64_t base[4], int64_t off[4]) {
+// the operand the indexed form looks up: the climatology c of ACC / COS, else a (the climatology as the forecast of an error)
+__host__ __device__ constexpr int idx_operand(int M) { return (M == DLWPCS_SCORE_ACC || M == DLWPCS_SCORE_COS) ? 2 : 0; }
+
+template <int IOP>
+__device__ __forceinline__ void row_offsets(const ScoreGeom &G, int64_t r, const int64_t base[4], int64_t off[4],
+                                            const int32_t *__restrict__ lead_rows) {
     int64_t t = r / G.red_outer, rr = r - t * G.red_outer;
 #pragma unroll
     for (int op = 0; op < 4; ++op) off[op] = base[op] + t * G.t_stride[op];
+    if constexpr (IOP >= 0) off[IOP] += (int64_t)lead_rows[t] * G.idx_stride;
     for (int d = G.n_outer - 1; d >= 0; --d) {
         int64_t e = G.outer_ext[d];
         int64_t c = rr % e;
@@ -133,11 +145,11 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-template <int M, bool VEC>
+template <int M, bool VEC, bool IDX>
 __global__ void __launch_bounds__(SC_THREADS) score_partial_kernel(ScoreGeom G, const float *__restrict__ a,
                                                                   const float *__restrict__ b, const float *__restrict__ c,
                                                                   const float *__restrict__ w, double *__restrict__ partial,
-                                                                  void *__restrict__ out) {
+                                                                  void *__restrict__ out, const int32_t *__restrict__ row_tab) {
     constexpr int V = VEC ? 4 : 1;                      // elements per chunk
     const int64_t bid = flat_block();
     if (bid >= G.nblk) return;
@@ -155,6 +167,7 @@ __global__ void __launch_bounds__(SC_THREADS) score_partial_kernel(ScoreGeom G, 
 #pragma unroll
         for (int op = 0; op < 4; ++op) base[op] += cidx * G.keep_stride[op][d];
     }
+    const int32_t *lead_rows = IDX ? row_tab + (int64_t)f * G.t_len : nullptr;    // the table rows of this lead
     const int64_t rows = n_rows_of(G, f);
     const int64_t rl = G.row_len * G.kc;                // elements per row
     const int64_t cpr = rl / V;                         // chunks per row
@@ -170,7 +183,7 @@ __global__ void __launch_bounds__(SC_THREADS) score_partial_kernel(ScoreGeom G, 
     int64_t q = q0 + threadIdx.x;
     int64_t row = cpr ? q / cpr : 0, col = cpr ? q - row * cpr : 0;
     int64_t roff[4];
-    if (q < q1) row_offsets(G, row, base, roff);
+    if (q < q1) row_offsets<IDX ? idx_operand(M) : -1>(G, row, base, roff, lead_rows);
     const int kmask = G.kc - 1;
     while (q < q1) {
         float x[SC_UNROLL][V], y[SC_UNROLL][V], cc[SC_UNROLL][V], ww[SC_UNROLL][V];
@@ -201,7 +214,7 @@ __global__ void __launch_bounds__(SC_THREADS) score_partial_kernel(ScoreGeom G, 
                 if (col >= cpr) {
                     row += col / cpr;
                     col %= cpr;
-                    if (q < q1) row_offsets(G, row, base, roff);
+                    if (q < q1) row_offsets<IDX ? idx_operand(M) : -1>(G, row, base, roff, lead_rows);
                 }
             }
         }
@@ -300,10 +313,11 @@ __global__ void __launch_bounds__(256) score_finalize_kernel(const double *__res
 
 // Column form, for many outputs with short reductions (e.g. a kept innermost spatial axis): one lane per output reduces its
 // elements serially (fp32 runs of 16 terms, fp64 beyond) and finishes it; neighbouring lanes read neighbouring outputs.
-template <int M>
+template <int M, bool IDX>
 __global__ void __launch_bounds__(256) score_column_kernel(ScoreGeom G, int64_t n_out, const float *__restrict__ a,
                                                            const float *__restrict__ b, const float *__restrict__ c,
-                                                           const float *__restrict__ w, void *__restrict__ out) {
+                                                           const float *__restrict__ w, void *__restrict__ out,
+                                                           const int32_t *__restrict__ row_tab) {
     const int64_t i = flat_block() * 256 + threadIdx.x;
     if (i >= n_out) return;
     const int64_t g = i / G.kc;
@@ -320,6 +334,7 @@ __global__ void __launch_bounds__(256) score_column_kernel(ScoreGeom G, int64_t 
 #pragma unroll
         for (int op = 0; op < 4; ++op) base[op] += cidx * G.keep_stride[op][d];
     }
+    const int32_t *lead_rows = IDX ? row_tab + (int64_t)f * G.t_len : nullptr;
     const int64_t rows = n_rows_of(G, f);
     double m6[SC_NM];
 #pragma unroll
@@ -329,7 +344,7 @@ __global__ void __launch_bounds__(256) score_column_kernel(ScoreGeom G, int64_t 
     int run = 0;
     for (int64_t r = 0; r < rows; ++r) {
         int64_t roff[4];
-        row_offsets(G, r, base, roff);
+        row_offsets<IDX ? idx_operand(M) : -1>(G, r, base, roff, lead_rows);
         for (int64_t l = 0; l < G.row_len; ++l) {
             const float x = a[roff[0] + l * G.row_stride[0]];
             const float y = b[roff[1] + l * G.row_stride[1]];
@@ -364,7 +379,7 @@ static dim3 grid_of(int64_t n) {
 
 static int aux_mode(const ScoreGeom &G, int op) {
     bool v4 = (G.kc == 1 || G.kc_stride[op] == 1) && G.row_stride[op] == G.kc && G.lead_stride[op] % 4 == 0 &&
-              G.t_stride[op] % 4 == 0;
+              G.t_stride[op] % 4 == 0 && (op != G.idx_op || G.idx_stride % 4 == 0);
     for (int i = 0; i < G.n_keep && v4; ++i) v4 = G.keep_stride[op][i] % 4 == 0;
     for (int i = 0; i < G.n_outer && v4; ++i) v4 = G.outer_stride[op][i] % 4 == 0;
     if (v4) return AUX_VEC;
@@ -372,7 +387,7 @@ static int aux_mode(const ScoreGeom &G, int op) {
     return AUX_ELEM;
 }
 
-int make_plan(const dlwpcs_score_desc *d, Plan &P) {
+int make_plan(const dlwpcs_score_desc *d, Plan &P, int idx_op = -1, int64_t idx_stride = 0) {
     if (!d) return fail(DLWPCS_E_INVALID, "score: null descriptor");
     if (d->method < DLWPCS_SCORE_MSE || d->method > DLWPCS_SCORE_MEAN) return fail(DLWPCS_E_INVALID, "score: unknown method %d", d->method);
     if (d->n_lead < 1 || d->t_len < 0 || d->t_slope < 0) return fail(DLWPCS_E_INVALID, "score: bad lead / time extents");
@@ -388,6 +403,8 @@ int make_plan(const dlwpcs_score_desc *d, Plan &P) {
     G.t_slope = d->t_slope;
     G.kc = d->kc;
     G.kc_shift = d->kc == 4 ? 2 : d->kc == 2 ? 1 : 0;
+    G.idx_op = idx_op;
+    G.idx_stride = idx_stride;
     G.n_keep = d->n_keep;
     G.keep_total = 1;
     for (int i = 0; i < d->n_keep; ++i) {
@@ -428,7 +445,7 @@ int make_plan(const dlwpcs_score_desc *d, Plan &P) {
     bool vec = (G.row_len * G.kc) % 4 == 0;
     for (int op = 0; op < 2 && vec; ++op) {
         vec = (G.kc == 1 || G.kc_stride[op] == 1) && G.row_stride[op] == G.kc && G.lead_stride[op] % 4 == 0 &&
-              G.t_stride[op] % 4 == 0;
+              G.t_stride[op] % 4 == 0 && (op != G.idx_op || G.idx_stride % 4 == 0);
         for (int i = 0; i < G.n_keep && vec; ++i) vec = G.keep_stride[op][i] % 4 == 0;
         for (int i = 0; i < G.n_outer && vec; ++i) vec = G.outer_stride[op][i] % 4 == 0;
     }
@@ -458,21 +475,54 @@ int make_plan(const dlwpcs_score_desc *d, Plan &P) {
     return DLWPCS_OK;
 }
 
-template <int M>
+template <int M, bool IDX>
 void launch(const Plan &P, const float *a, const float *b, const float *c, const float *w, double *partial, void *out,
-            hipStream_t s) {
+            const int32_t *row_tab, hipStream_t s) {
     const dim3 grid = grid_of(P.G.nblk);
     if (P.column) {
-        hipLaunchKernelGGL((score_column_kernel<M>), grid, dim3(256), 0, s, P.G, P.n_out, a, b, c, w, out);
+        hipLaunchKernelGGL((score_column_kernel<M, IDX>), grid, dim3(256), 0, s, P.G, P.n_out, a, b, c, w, out, row_tab);
         return;
     }
     if (P.vec)
-        hipLaunchKernelGGL((score_partial_kernel<M, true>), grid, dim3(SC_THREADS), 0, s, P.G, a, b, c, w, partial, out);
+        hipLaunchKernelGGL((score_partial_kernel<M, true, IDX>), grid, dim3(SC_THREADS), 0, s, P.G, a, b, c, w, partial, out,
+                           row_tab);
     else
-        hipLaunchKernelGGL((score_partial_kernel<M, false>), grid, dim3(SC_THREADS), 0, s, P.G, a, b, c, w, partial, out);
+        hipLaunchKernelGGL((score_partial_kernel<M, false, IDX>), grid, dim3(SC_THREADS), 0, s, P.G, a, b, c, w, partial, out,
+                           row_tab);
     if (P.G.slabs > 1)
         hipLaunchKernelGGL((score_finalize_kernel<M>), grid_of((P.n_out + 255) / 256), dim3(256), 0, s, partial, P.n_out,
                            P.G.kc, P.G.slabs, P.G.out_f32, out);
+}
+
+// the entry points' common tail: operand checks, load widths from the pointers, launch
+template <bool IDX>
+int run(const dlwpcs_score_desc *d, Plan &P, const float *a, const float *b, const float *c, const float *w, void *out,
+        int out_f32, void *scratch, size_t scratch_bytes, const int32_t *row_tab, dlwpcs_stream_t stream) {
+    if (!out || !b || (d->method != DLWPCS_SCORE_MEAN && !a)) return fail(DLWPCS_E_INVALID, "score: null operand");
+    const size_t need = P.G.slabs > 1 ? (size_t)(P.groups * P.G.slabs * P.G.kc * SC_NM) * sizeof(double) : 0;
+    if (need && (!scratch || scratch_bytes < need))
+        return fail(DLWPCS_E_INVALID, "score: scratch of %zu bytes, need %zu", scratch_bytes, need);
+    if (d->method == DLWPCS_SCORE_MEAN) a = b;
+    if (P.vec && ((((uintptr_t)a) & 15) || (((uintptr_t)b) & 15))) P.vec = false;
+    if (P.G.cmode == AUX_VEC && (((uintptr_t)c) & 15)) P.G.cmode = AUX_ELEM;
+    if (P.G.wmode == AUX_VEC && (((uintptr_t)w) & 15)) P.G.wmode = AUX_ELEM;
+    P.G.has_c = c != nullptr;
+    P.G.has_w = w != nullptr;
+    P.G.out_f32 = out_f32 != 0;
+    if (P.n_out == 0) return DLWPCS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    double *partial = (double *)scratch;
+    switch (d->method) {
+    case DLWPCS_SCORE_MSE: launch<DLWPCS_SCORE_MSE, IDX>(P, a, b, c, w, partial, out, row_tab, s); break;
+    case DLWPCS_SCORE_RMSE: launch<DLWPCS_SCORE_RMSE, IDX>(P, a, b, c, w, partial, out, row_tab, s); break;
+    case DLWPCS_SCORE_MAE: launch<DLWPCS_SCORE_MAE, IDX>(P, a, b, c, w, partial, out, row_tab, s); break;
+    case DLWPCS_SCORE_ACC: launch<DLWPCS_SCORE_ACC, IDX>(P, a, b, c, w, partial, out, row_tab, s); break;
+    case DLWPCS_SCORE_COS: launch<DLWPCS_SCORE_COS, IDX>(P, a, b, c, w, partial, out, row_tab, s); break;
+    default:
+        if constexpr (!IDX) launch<DLWPCS_SCORE_MEAN, false>(P, a, b, c, w, partial, out, row_tab, s);
+        break;
+    }
+    return check_launch("score");
 }
 
 }  // namespace
@@ -492,27 +542,20 @@ extern "C" int dlwpcs_score(const dlwpcs_score_desc *d, const float *a, const fl
     Plan P;
     int rc = make_plan(d, P);
     if (rc != DLWPCS_OK) return rc;
-    if (!out || !b || (d->method != DLWPCS_SCORE_MEAN && !a)) return fail(DLWPCS_E_INVALID, "score: null operand");
-    const size_t need = P.G.slabs > 1 ? (size_t)(P.groups * P.G.slabs * P.G.kc * SC_NM) * sizeof(double) : 0;
-    if (need && (!scratch || scratch_bytes < need))
-        return fail(DLWPCS_E_INVALID, "score: scratch of %zu bytes, need %zu", scratch_bytes, need);
-    if (d->method == DLWPCS_SCORE_MEAN) a = b;
-    if (P.vec && ((((uintptr_t)a) & 15) || (((uintptr_t)b) & 15))) P.vec = false;
-    if (P.G.cmode == AUX_VEC && (((uintptr_t)c) & 15)) P.G.cmode = AUX_ELEM;
-    if (P.G.wmode == AUX_VEC && (((uintptr_t)w) & 15)) P.G.wmode = AUX_ELEM;
-    P.G.has_c = c != nullptr;
-    P.G.has_w = w != nullptr;
-    P.G.out_f32 = out_f32 != 0;
-    if (P.n_out == 0) return DLWPCS_OK;
-    hipStream_t s = (hipStream_t)stream;
-    double *partial = (double *)scratch;
-    switch (d->method) {
-    case DLWPCS_SCORE_MSE: launch<DLWPCS_SCORE_MSE>(P, a, b, c, w, partial, out, s); break;
-    case DLWPCS_SCORE_RMSE: launch<DLWPCS_SCORE_RMSE>(P, a, b, c, w, partial, out, s); break;
-    case DLWPCS_SCORE_MAE: launch<DLWPCS_SCORE_MAE>(P, a, b, c, w, partial, out, s); break;
-    case DLWPCS_SCORE_ACC: launch<DLWPCS_SCORE_ACC>(P, a, b, c, w, partial, out, s); break;
-    case DLWPCS_SCORE_COS: launch<DLWPCS_SCORE_COS>(P, a, b, c, w, partial, out, s); break;
-    default: launch<DLWPCS_SCORE_MEAN>(P, a, b, c, w, partial, out, s); break;
-    }
-    return check_launch("score");
+    return run<false>(d, P, a, b, c, w, out, out_f32, scratch, scratch_bytes, nullptr, stream);
+}
+
+extern "C" int dlwpcs_score_indexed(const dlwpcs_score_desc *d, const float *a, const float *b, const float *c, const float *w,
+                                    const int32_t *row_dev, int64_t table_row_stride, void *out, int out_f32,
+                                    void *scratch, size_t scratch_bytes, dlwpcs_stream_t stream) {
+    if (!d) return fail(DLWPCS_E_INVALID, "score: null descriptor");
+    if (d->method == DLWPCS_SCORE_MEAN) return fail(DLWPCS_E_INVALID, "score_indexed: the mean has no indexed operand");
+    const int indexed_op = idx_operand(d->method);
+    if ((d->lead_stride[indexed_op] != 0 || d->t_stride[indexed_op] != 0))
+        return fail(DLWPCS_E_INVALID, "score_indexed: the indexed operand's lead and time strides must be 0");
+    Plan P;
+    int rc = make_plan(d, P, indexed_op, table_row_stride);
+    if (rc != DLWPCS_OK) return rc;
+    if (!row_dev || !(indexed_op == 0 ? a : c)) return fail(DLWPCS_E_INVALID, "score_indexed: null table");
+    return run<true>(d, P, a, b, c, w, out, out_f32, scratch, scratch_bytes, row_dev, stream);
 }

@@ -536,6 +536,54 @@ typedef struct dlwpcs_score_desc {
 size_t dlwpcs_score_scratch_bytes(const dlwpcs_score_desc *d);
 int dlwpcs_score(const dlwpcs_score_desc *d, const float *a, const float *b, const float *c, const float *w, void *out,
                  int out_f32, void *scratch, size_t scratch_bytes, dlwpcs_stream_t stream);
+/* The same reduction with ONE operand looked up by row instead of laid out over (lead, time): the climatology -- operand c of
+ * ACC / COS, operand a of MSE / RMSE / MAE (the error of a climatology forecast) -- is a (K, inner...) table, and for lead f
+ * and time t its row is row_dev[f * t_len + t] (int32 on the device, one load per (f, t) row); its offset is row * table_row_stride plus the kept / reduced / channel strides of the descriptor as
+ * before, and its lead_stride and t_stride must be 0.  Same plan, same partial-sum slabs, same order: the result is bitwise
+ * that of dlwpcs_score on the materialised (n_lead, t_len, inner...) operand.  Scratch as for dlwpcs_score.  The kernel TRUSTS
+ * the table: every entry that is read lies in [0, K).  DLWPCS_SCORE_MEAN is refused. */
+int dlwpcs_score_indexed(const dlwpcs_score_desc *d, const float *a, const float *b, const float *c, const float *w,
+                         const int32_t *row_dev, int64_t table_row_stride, void *out, int out_f32,
+                         void *scratch, size_t scratch_bytes, dlwpcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- *
+ * Climatologies (reference DLWP/verify.py:167-214 monthly_climo_error, :426-456 daily_climatology / daily_climo_time_series).
+ * A row set: fp32 device rows of up to DLWPCS_SCORE_MAX_DIMS inner dims, every dim with its stride in ELEMENTS in the source and
+ * in the output (so a channels-first array is reduced or gathered straight into a channels-last result); source row r starts at
+ * r * src_row_stride, output row i at i * out_row_stride.  Lanes run along the LAST dim of the descriptor: list the dim that is
+ * contiguous in the source last.  16-byte loads when that dim has source stride 1 and every extent / stride / pointer allows
+ * it, else one element per lane.
+ *
+ * dlwpcs_group_mean: out[k] = per-element mean of the rows row_index[group_start[k] .. group_start[k + 1]) for k < n_groups,
+ * NaN entries skipped per element (xarray groupby().mean(), np.nanmean): an element with no finite-or-infinite member is NaN,
+ * +-inf propagate.  count (may be NULL): int32, same layout as out, the members that entered each element.
+ * Sums are fp64, rounded to fp32 once.  Fixed order, whatever the grid: a group's rows are cut into slabs of
+ * DLWPCS_GROUP_SLAB_ROWS rows in CSR order, a slab is summed row by row from zero, and the slab sums are added in slab order.
+ * split = 0: one launch, a lane walks the slabs of its group itself.  split = 1: launch 1 gives every (group, slab) its own
+ * workgroups and writes the slab sums to scratch, launch 2 adds them -- the same additions, hence the same bits; for few
+ * groups over many rows (monthly, K = 1).  split < 0: chosen from the grid size.  max_group_rows >= the longest group (the
+ * host built the CSR and knows it); scratch >= dlwpcs_group_mean_scratch_bytes(...) of the same arguments (0 for one launch).
+ * No atomics, no host synchronisation, no allocation.  The kernel TRUSTS the CSR: group_start non-decreasing, every row_index
+ * in range of the source.
+ *
+ * dlwpcs_rows_gather: out[i] = source row index[i] for i < n (int32 device table); a negative index writes a NaN row.
+ * One launch.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_GROUP_SLAB_ROWS 512
+typedef struct dlwpcs_rows_desc {
+    int32_t n_inner;                                /* 0..DLWPCS_SCORE_MAX_DIMS */
+    int32_t reserved;
+    int64_t src_row_stride, out_row_stride;
+    int64_t inner_ext[DLWPCS_SCORE_MAX_DIMS];
+    int64_t src_stride[DLWPCS_SCORE_MAX_DIMS];
+    int64_t out_stride[DLWPCS_SCORE_MAX_DIMS];
+} dlwpcs_rows_desc;
+size_t dlwpcs_group_mean_scratch_bytes(const dlwpcs_rows_desc *d, int n_groups, int64_t max_group_rows, int split);
+int dlwpcs_group_mean(const dlwpcs_rows_desc *d, const float *src, const int32_t *group_start, const int32_t *row_index,
+                      int n_groups, int64_t max_group_rows, int split, float *out, int32_t *count, void *scratch,
+                      size_t scratch_bytes, dlwpcs_stream_t stream);
+int dlwpcs_rows_gather(const dlwpcs_rows_desc *d, const float *src, const int32_t *index, int64_t n, float *out,
+                       dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
  * Offline-map remapping (cubed sphere <-> lat-lon, DLWP/remap): one sparse matrix in CSR form applied to a stack of fields,
