@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <string.h>
 #include "../../include/dlwpcs.h"
 
 namespace dlwpcs {
@@ -200,5 +201,19 @@ struct LossField {
 
 static inline size_t dtype_size(int dtype) { return dtype == DLWPCS_BF16 ? 2 : 4; }
 static inline bool dtype_ok(int dtype) { return dtype == DLWPCS_F32 || dtype == DLWPCS_BF16; }
+
+// host: the max_value that act_leaky_clip_grad_from_y compares a STORED output against.  fp32 storage: max_value itself (a
+// clipped output equals it).  bf16 storage: a clipped output is stored as one of the two bf16 neighbours of max_value, and
+// the lower one is < max_value when max_value is not representable and rounds down (0.7 -> 0.69921875), so the comparison
+// uses the largest bf16 <= max_value: both neighbours are then recognised as clipped.  A representable max_value (and +inf)
+// is returned unchanged; NaN is handed through (the callers reject it).
+static inline float mask_vmax_for(int dtype, float vmax) {
+    if (dtype != DLWPCS_BF16 || !(vmax >= 0.f)) return vmax;
+    uint32_t u;
+    memcpy(&u, &vmax, 4);
+    u &= 0xffff0000u;                                  // vmax >= 0: truncation is the floor
+    memcpy(&vmax, &u, 4);
+    return vmax;
+}
 
 }  // namespace dlwpcs

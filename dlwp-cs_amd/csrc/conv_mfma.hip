@@ -1676,7 +1676,7 @@ static int head_loss_impl(const dlwpcs_conv_desc *d, const dlwpcs_loss_desc *L, 
     H.wpk_bwd = (const bf16_t *)wpk_bwd; H.target = target; H.dx = (bf16_t *)dx; H.partial = (float *)scratch;
     const double n = (double)d->B * 6 * d->N * d->N * d->Cout;
     H.gscale = (float)(weight * (L->kind == DLWPCS_LOSS_MSE ? 2.0 : 1.0) / n);
-    H.mask_dx = mask_dx; H.m_alpha = m_alpha; H.m_vmax = m_vmax;
+    H.mask_dx = mask_dx; H.m_alpha = m_alpha; H.m_vmax = mask_vmax_for(d->dtype, m_vmax);
     const unsigned grid = pw_grid(H.f.ngroups);
     const bool W = L->weight != nullptr, mae = L->kind == DLWPCS_LOSS_MAE;
     int pidx = -1;
@@ -1899,7 +1899,7 @@ static int conv_bwd_data_impl(const dlwpcs_conv_desc *d, const void *dy, const v
             const Work wk = conv_work(d);
             pidx = prof_begin(in_kernel_mask ? "pw_dgrad_kernel<true>" : "pw_dgrad_kernel<false>", wk.flops, wk.bytes, s);
         }
-        Q.mask = (const bf16_t *)m0; Q.m_alpha = m_alpha; Q.m_vmax = m_vmax;
+        Q.mask = (const bf16_t *)m0; Q.m_alpha = m_alpha; Q.m_vmax = mask_vmax_for(d->dtype, m_vmax);
         if (in_kernel_mask) hipLaunchKernelGGL(pw_dgrad_kernel<true>, dim3(pw_grid(Q.ngroups)), dim3(256), 0, s, Q);
         else hipLaunchKernelGGL(pw_dgrad_kernel<false>, dim3(pw_grid(Q.ngroups)), dim3(256), 0, s, Q);
         if (pidx >= 0) prof_end(pidx, s);
@@ -1916,7 +1916,7 @@ static int conv_bwd_data_impl(const dlwpcs_conv_desc *d, const void *dy, const v
     P.C0 = d->Cout; P.C1 = 0; P.Cin = d->Cout; P.Cout = Cin;
     P.CG = ceil_div(d->Cout, cgw_of(d->dtype)); P.NTtot = ceil_div(Cin, 32); P.up0 = 0;
     P.mode = MODE_ZERO;
-    P.act = DLWPCS_ACT_NONE; P.alpha = d->alpha; P.vmax = d->vmax;
+    P.act = DLWPCS_ACT_NONE; P.alpha = d->alpha; P.vmax = mask_vmax_for(d->dtype, d->vmax);   // (act' of the dz loader only)
     // direct mode: interior cells of the padded gradient go straight to the (non-upsampled) sources' gradient tensors, only
     // the halo ring is materialised in dxv and a border fix-up replaces the full inverse-gather pass
     int direct_done = 0, mask_done = 0;
@@ -1926,7 +1926,7 @@ static int conv_bwd_data_impl(const dlwpcs_conv_desc *d, const void *dy, const v
     P.dsplit = d->C0;
     P.direct_done = &direct_done;
     P.m0 = P.d0 ? m0 : nullptr; P.m1 = P.d1 ? m1 : nullptr;
-    P.m_alpha = m_alpha; P.m_vmax = m_vmax; P.m_thr1 = bf16_mask_threshold(m_vmax);
+    P.m_alpha = m_alpha; P.m_vmax = mask_vmax_for(d->dtype, m_vmax); P.m_thr1 = bf16_mask_threshold(m_vmax);
     P.mask_done = &mask_done;
     // ---- gather form (DLWPCS_CONV_DGRAD_GATHER; conv_ws.h EDGE): the gradient on the N x N grid, every cell complete when it is
     // stored.  Sources that are not upsampled are written directly (masked where asked), an upsampled source 0 goes through the
@@ -2095,7 +2095,7 @@ extern "C" int dlwpcs_conv_bwd_weights(const dlwpcs_conv_desc *d, const void *sr
     P.B = d->B; P.Nin = d->N; P.No = out_size(d);
     P.C0 = d->C0; P.C1 = d->C1; P.Cin = Cin; P.Cout = d->Cout; P.up0 = d->up0;
     P.mode = d->halo ? MODE_HALO : MODE_DIRECT;
-    P.alpha = d->alpha; P.vmax = d->vmax;
+    P.alpha = d->alpha; P.vmax = mask_vmax_for(d->dtype, d->vmax);    // (act' on load only: no epilogue here)
     P.pix_per_block = L.wg_pix; P.nblk_face = L.wg_nblk;
     P.W2 = P.No + KS - 1; P.magicW2 = div_magic(P.W2); P.magicNo = div_magic(P.No);
     P.tile_rows_max = tile_rows_for(L.wg_pix, P.No) + (KS - 1);

@@ -99,6 +99,11 @@ template <typename F> static inline void dispatch_vec(int dtype, int g, F &&f) {
     }
 }
 // pure data movement: widest power-of-two byte vector dividing `row_bytes`
+// flat kernels (activation, add): the 16-B vector with a scalar tail, or the scalar instantiation when a pointer is not
+// 16-B aligned (a contiguous view that starts at an odd element offset is a legal argument)
+static inline bool aligned16(const void *a, const void *b = nullptr, const void *c = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
 template <typename F> static inline void dispatch_mover(size_t row_bytes, F &&f) {
     if (row_bytes % 16 == 0) f(uint4{}, 16); else if (row_bytes % 4 == 0) f(uint32_t{}, 4); else f(uint16_t{}, 2);
 }
@@ -959,6 +964,7 @@ int launch_mask_inplace(void *dx, const void *m, size_t n, float alpha, float vm
 int launch_src_grad(const void *dxv, void *dsrc, const int32_t *inv, int B, int N, int CT, int choff, int CS, int up,
                     int halo, int dtype, hipStream_t s, const void *msrc, float m_alpha, float m_vmax, int *masked) {
     if (masked) *masked = msrc ? 1 : 0;
+    m_vmax = mask_vmax_for(dtype, m_vmax);
     const int No = up ? N / 2 : N;
     // common divisor of the three channel counts decides the vector width
     int g = 8;
@@ -980,6 +986,7 @@ int launch_src_grad(const void *dxv, void *dsrc, const int32_t *inv, int B, int 
 int launch_src_pair(const void *dxv, void *dsrc0, void *dsrc1, const int32_t *inv, int B, int N, int C0, int C1, int up0,
                     int dtype, hipStream_t s, const void *m0, const void *m1, float m_alpha, float m_vmax) {
     const int CT = C0 + C1;
+    m_vmax = mask_vmax_for(dtype, m_vmax);
     int g = 8;
     while (g > 1 && (C0 % g || C1 % g)) g >>= 1;
     const int No = up0 ? N / 2 : N;
@@ -998,6 +1005,7 @@ int launch_src_pair(const void *dxv, void *dsrc0, void *dsrc1, const int32_t *in
 // upsampling): adds the halo-ring cells of dxv that gathered from each border cell
 int launch_ring_fix(const void *dxv, void *dsrc, const int32_t *inv, int B, int N, int CT, int choff, int CS, int dtype,
                     hipStream_t s, const void *msrc, float m_alpha, float m_vmax) {
+    m_vmax = mask_vmax_for(dtype, m_vmax);
     int g = 8;
     while (g > 1 && (CT % g || choff % g || CS % g)) g >>= 1;
     const int nb = N > 1 ? 4 * N - 4 : 1;
@@ -1013,12 +1021,23 @@ int launch_ring_fix(const void *dxv, void *dsrc, const int32_t *inv, int B, int 
 // dx *= act'(m), in place (the fallback of the pre-masked gradient convention where no kernel fuses the multiply)
 int launch_mask_inplace(void *dx, const void *m, size_t n, float alpha, float vmax, int dtype, hipStream_t s) {
     if (n == 0) return DLWPCS_OK;
-    if (dtype == DLWPCS_BF16)
-        hipLaunchKernelGGL((act_bwd_kernel<H8, bf16_t>), stream_grid(n / 8 + 1), dim3(256), 0, s, (const bf16_t *)dx,
-                           (const bf16_t *)m, (bf16_t *)dx, n, alpha, vmax);
-    else
-        hipLaunchKernelGGL((act_bwd_kernel<float4, float>), stream_grid(n / 4 + 1), dim3(256), 0, s, (const float *)dx,
-                           (const float *)m, (float *)dx, n, alpha, vmax);
+    vmax = mask_vmax_for(dtype, vmax);
+    const bool vec = aligned16(dx, m);
+    if (dtype == DLWPCS_BF16) {
+        if (vec)
+            hipLaunchKernelGGL((act_bwd_kernel<H8, bf16_t>), stream_grid(n / 8 + 1), dim3(256), 0, s, (const bf16_t *)dx,
+                               (const bf16_t *)m, (bf16_t *)dx, n, alpha, vmax);
+        else
+            hipLaunchKernelGGL((act_bwd_kernel<bf16_t, bf16_t>), stream_grid(n), dim3(256), 0, s, (const bf16_t *)dx,
+                               (const bf16_t *)m, (bf16_t *)dx, n, alpha, vmax);
+    } else {
+        if (vec)
+            hipLaunchKernelGGL((act_bwd_kernel<float4, float>), stream_grid(n / 4 + 1), dim3(256), 0, s, (const float *)dx,
+                               (const float *)m, (float *)dx, n, alpha, vmax);
+        else
+            hipLaunchKernelGGL((act_bwd_kernel<float, float>), stream_grid(n), dim3(256), 0, s, (const float *)dx,
+                               (const float *)m, (float *)dx, n, alpha, vmax);
+    }
     return check_launch("mask_inplace");
 }
 }  // namespace dlwpcs
@@ -1029,12 +1048,22 @@ extern "C" int dlwpcs_act_fwd(const void *x, void *y, size_t n, int act, float a
     REQUIRE(x && y, "act_fwd: null pointer");
     REQUIRE(act == DLWPCS_ACT_LEAKY_CLIP, "act_fwd: unknown activation %d", act);
     if (n == 0) return DLWPCS_OK;
-    if (dtype == DLWPCS_BF16)
-        hipLaunchKernelGGL((act_fwd_kernel<H8, bf16_t>), stream_grid(n / 8 + 1), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t *)x, (bf16_t *)y, n, alpha, vmax);
-    else
-        hipLaunchKernelGGL((act_fwd_kernel<float4, float>), stream_grid(n / 4 + 1), dim3(256), 0, (hipStream_t)stream,
-                           (const float *)x, (float *)y, n, alpha, vmax);
+    const bool vec = aligned16(x, y);
+    if (dtype == DLWPCS_BF16) {
+        if (vec)
+            hipLaunchKernelGGL((act_fwd_kernel<H8, bf16_t>), stream_grid(n / 8 + 1), dim3(256), 0, (hipStream_t)stream,
+                               (const bf16_t *)x, (bf16_t *)y, n, alpha, vmax);
+        else
+            hipLaunchKernelGGL((act_fwd_kernel<bf16_t, bf16_t>), stream_grid(n), dim3(256), 0, (hipStream_t)stream,
+                               (const bf16_t *)x, (bf16_t *)y, n, alpha, vmax);
+    } else {
+        if (vec)
+            hipLaunchKernelGGL((act_fwd_kernel<float4, float>), stream_grid(n / 4 + 1), dim3(256), 0, (hipStream_t)stream,
+                               (const float *)x, (float *)y, n, alpha, vmax);
+        else
+            hipLaunchKernelGGL((act_fwd_kernel<float, float>), stream_grid(n), dim3(256), 0, (hipStream_t)stream,
+                               (const float *)x, (float *)y, n, alpha, vmax);
+    }
     return check_launch("act_fwd");
 }
 
@@ -1044,12 +1073,23 @@ extern "C" int dlwpcs_act_bwd(const void *dy, const void *y, void *dx, size_t n,
     REQUIRE(dy && y && dx, "act_bwd: null pointer");
     REQUIRE(act == DLWPCS_ACT_LEAKY_CLIP, "act_bwd: unknown activation %d", act);
     if (n == 0) return DLWPCS_OK;
-    if (dtype == DLWPCS_BF16)
-        hipLaunchKernelGGL((act_bwd_kernel<H8, bf16_t>), stream_grid(n / 8 + 1), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t *)dy, (const bf16_t *)y, (bf16_t *)dx, n, alpha, vmax);
-    else
-        hipLaunchKernelGGL((act_bwd_kernel<float4, float>), stream_grid(n / 4 + 1), dim3(256), 0, (hipStream_t)stream,
-                           (const float *)dy, (const float *)y, (float *)dx, n, alpha, vmax);
+    vmax = mask_vmax_for(dtype, vmax);
+    const bool vec = aligned16(dy, y, dx);
+    if (dtype == DLWPCS_BF16) {
+        if (vec)
+            hipLaunchKernelGGL((act_bwd_kernel<H8, bf16_t>), stream_grid(n / 8 + 1), dim3(256), 0, (hipStream_t)stream,
+                               (const bf16_t *)dy, (const bf16_t *)y, (bf16_t *)dx, n, alpha, vmax);
+        else
+            hipLaunchKernelGGL((act_bwd_kernel<bf16_t, bf16_t>), stream_grid(n), dim3(256), 0, (hipStream_t)stream,
+                               (const bf16_t *)dy, (const bf16_t *)y, (bf16_t *)dx, n, alpha, vmax);
+    } else {
+        if (vec)
+            hipLaunchKernelGGL((act_bwd_kernel<float4, float>), stream_grid(n / 4 + 1), dim3(256), 0, (hipStream_t)stream,
+                               (const float *)dy, (const float *)y, (float *)dx, n, alpha, vmax);
+        else
+            hipLaunchKernelGGL((act_bwd_kernel<float, float>), stream_grid(n), dim3(256), 0, (hipStream_t)stream,
+                               (const float *)dy, (const float *)y, (float *)dx, n, alpha, vmax);
+    }
     return check_launch("act_bwd");
 }
 
@@ -1118,6 +1158,7 @@ static int avgpool2_bwd_masked_impl(const void *dy, const void *dskip, const voi
     REQUIRE(B >= 0 && N >= 2 && N % 2 == 0 && C >= 1, "avgpool2_bwd_masked: bad shape B=%d N=%d C=%d", B, N, C);
     REQUIRE(m_alpha >= 0.f && m_vmax >= 0.f, "avgpool2_bwd_masked: activation needs negative_slope >= 0 and max_value >= 0");
     if (B == 0) return DLWPCS_OK;
+    m_vmax = mask_vmax_for(dtype, m_vmax);
     int g = 8;
     while (g > 1 && (C % g || (ring && (ring_channels % g || ring_choff % g)))) g >>= 1;
     dispatch_vec(dtype, g, [&](auto tag, int w) {
@@ -1261,12 +1302,22 @@ extern "C" int dlwpcs_add(const void *a, const void *b, void *y, size_t n, int d
     REQUIRE_DTYPE(dtype, "add");
     REQUIRE(a && b && y, "add: null pointer");
     if (n == 0) return DLWPCS_OK;
-    if (dtype == DLWPCS_BF16)
-        hipLaunchKernelGGL((add_kernel<H8, bf16_t>), stream_grid(n / 8 + 1), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t *)a, (const bf16_t *)b, (bf16_t *)y, n);
-    else
-        hipLaunchKernelGGL((add_kernel<float4, float>), stream_grid(n / 4 + 1), dim3(256), 0, (hipStream_t)stream,
-                           (const float *)a, (const float *)b, (float *)y, n);
+    const bool vec = aligned16(a, b, y);
+    if (dtype == DLWPCS_BF16) {
+        if (vec)
+            hipLaunchKernelGGL((add_kernel<H8, bf16_t>), stream_grid(n / 8 + 1), dim3(256), 0, (hipStream_t)stream,
+                               (const bf16_t *)a, (const bf16_t *)b, (bf16_t *)y, n);
+        else
+            hipLaunchKernelGGL((add_kernel<bf16_t, bf16_t>), stream_grid(n), dim3(256), 0, (hipStream_t)stream,
+                               (const bf16_t *)a, (const bf16_t *)b, (bf16_t *)y, n);
+    } else {
+        if (vec)
+            hipLaunchKernelGGL((add_kernel<float4, float>), stream_grid(n / 4 + 1), dim3(256), 0, (hipStream_t)stream,
+                               (const float *)a, (const float *)b, (float *)y, n);
+        else
+            hipLaunchKernelGGL((add_kernel<float, float>), stream_grid(n), dim3(256), 0, (hipStream_t)stream,
+                               (const float *)a, (const float *)b, (float *)y, n);
+    }
     return check_launch("add");
 }
 

@@ -38,9 +38,9 @@ __device__ __forceinline__ void vmask(uint4 &v, const uint4 &y, float a, float m
     v.x = bmask2(v.x, y.x, a, m); v.y = bmask2(v.y, y.y, a, m); v.z = bmask2(v.z, y.z, a, m); v.w = bmask2(v.w, y.w, a, m);
 }
 // The same product on packed bf16 pairs with 16-bit SIMD-in-register integer ops (11 VALU instructions per pair instead of ~17):
-// thr1 = (bits of the smallest bf16 >= vmax) - 1 in both halves (0 when vmax == 0), see bf16_mask_threshold().
+// thr1 = (bits of the largest bf16 <= vmax) - 1 in both halves (0 when vmax == 0), see bf16_mask_threshold() / mask_vmax_for().
 //   y < 0            -> alpha * v     (sign bit; y = -0.0 counts as negative here)
-//   0 < y < vmax     -> v             (1 <= bits(y) < thr, as an unsigned saturating subtraction)
+//   0 < y < thr      -> v             (1 <= bits(y) < thr, as an unsigned saturating subtraction)
 //   otherwise        -> 0
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
@@ -61,8 +61,7 @@ __device__ __forceinline__ void vmask_pk(uint4 &v, const uint4 &y, float a, uint
 static inline uint32_t bf16_mask_threshold(float vmax) {
     uint32_t u;
     memcpy(&u, &vmax, 4);
-    uint32_t thr = u >> 16;
-    if (u & 0xffffu) thr += 1;                      // not representable: the next bf16 above
+    uint32_t thr = u >> 16;                         // not representable: the bf16 below (a clipped output may be stored as it)
     if (vmax != vmax || thr > 0x7f80u) thr = 0x7f80u;
     const uint32_t t1 = thr ? thr - 1 : 0;
     return t1 | (t1 << 16);

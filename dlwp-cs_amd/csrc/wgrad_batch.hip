@@ -1320,7 +1320,7 @@ static int wb_geometry(const dlwpcs_conv_desc *d, bool want_bias, bool has_np, b
         if (KS != 3) return fail(DLWPCS_E_UNSUPPORTED, "wgrad_batch: act' on load is built for the 3x3 kernels (pass a pre-masked dz)");
         if (d->act != DLWPCS_ACT_LEAKY_CLIP || !(d->alpha >= 0.f) || !(d->vmax >= 0.f))
             return fail(DLWPCS_E_INVALID, "wgrad_batch: item with y needs act = LEAKY_CLIP with negative_slope >= 0 and max_value >= 0");
-        L.mask = 1; L.alpha = d->alpha; L.vmax = d->vmax; L.pad0 = f32 ? 0 : (int32_t)bf16_mask_threshold(d->vmax);
+        L.mask = 1; L.alpha = d->alpha; L.vmax = mask_vmax_for(d->dtype, d->vmax); L.pad0 = f32 ? 0 : (int32_t)bf16_mask_threshold(d->vmax);
     }
     const int TAPS = KS * KS;
     L.slot_floats = (int)align_up((size_t)TAPS * 32 * CT * 32 * NT + 32 * NT, 64);
