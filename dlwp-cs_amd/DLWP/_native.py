@@ -219,6 +219,8 @@ PROTOTYPES = {
                                      c_void_p]),
     'dlwpcs_batch_gather': (c_int, [c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, c_void_p, c_int, c_void_p, c_int,
                                     c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'dlwpcs_solar_fill': (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'dlwpcs_comm_load': (c_int, [ctypes.c_char_p]),
     'dlwpcs_comm_unique_id': (c_int, [c_void_p]),
     'dlwpcs_comm_init': (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int]),

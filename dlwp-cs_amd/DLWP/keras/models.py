@@ -1592,7 +1592,12 @@ class Model(object):
         :param predictors: the model's initial inputs (array / list of arrays or device tensors), as the generator yields them
         :param sequence_steps: how many times the whole model is applied
         :param insolation: (T, 6, N, N) fp32 array on the data's time grid (row r = time r * dt), or None for a model
-            without solar forcing (the main input is then the last output itself)
+            without solar forcing (the main input is then the last output itself), or a `DLWP.util.SolarForcing` on that time
+            grid: nothing dense is uploaded, the gathers become `dlwpcs_solar_fill` launches on its two tables (which a captured
+            chain keeps in its static buffers), and rows past its dates are its own continuation.  A replay copies both tables
+            into those buffers (32 B per row, 24 B per cell), so another forcing of the same shape replays correctly; the
+            tables' shapes are part of the graph key, and the continuation grows in chunks of `SolarForcing.ROW_CHUNK` rows,
+            so a forecast that reaches into a new chunk past the dates is captured once more
         :param start_index: (B,) int: row of `insolation` of each sample's FIRST input time step
         :param io_time_steps: input (= output) time steps folded into the channel axis; default: the time axis of the
             solar inputs, else 1
@@ -1606,6 +1611,8 @@ class Model(object):
         n_out = len(self.outputs)
         dev = backend.device()
         cdt = backend.torch_dtype(self.compute_dtype)
+        from ..util import SolarForcing
+        lazy = isinstance(insolation, SolarForcing)
         with torch.no_grad():
             cur = [self._to_device(a) for a in xs]
             self._check_shapes(cur, self.inputs, 'input')
@@ -1621,20 +1628,29 @@ class Model(object):
                                      'time steps x (variables + 1 solar channel)' % (c_main, c_out, its))
                 if start_index is None:
                     raise ValueError('rollout_with_forcing: `start_index` is needed with `insolation`')
-                sol = insolation if isinstance(insolation, torch.Tensor) else torch.from_numpy(
-                    np.ascontiguousarray(insolation, dtype=np.float32))
-                sol = sol.to(dev, dtype=torch.float32).contiguous()
-                if tuple(sol.shape[1:]) != space:
-                    raise ValueError('rollout_with_forcing: insolation grid %s != input grid %s' % (tuple(sol.shape[1:]), space))
-                sol = sol.unsqueeze(1)                                              # (T, 1, *space): one "variable"
                 start = np.asarray(start_index, dtype=np.int64).reshape(-1)
                 if start.shape[0] != B:
                     raise ValueError('rollout_with_forcing: start_index needs one entry per sample')
                 # every row read below, checked on the host (the gather kernels trust their indices)
                 last = int(start.max()) + (sequence_steps - 1) * its * n_out + (n_out - 1) * its + its - 1
-                if sequence_steps > 1 and (int(start.min()) < 0 or last >= sol.shape[0]):
+                if lazy:
+                    # described, not stored: the two tables of the forcing, continued past its dates as far as the forecast reads
+                    if tuple(insolation.shape[1:]) != space:
+                        raise ValueError('rollout_with_forcing: insolation grid %s != input grid %s'
+                                         % (tuple(insolation.shape[1:]), space))
+                    sol = insolation.rows(last + 1 if sequence_steps > 1 else 0).tables(dev)
+                    n_rows = int(sol[0].shape[0])
+                else:
+                    sol = insolation if isinstance(insolation, torch.Tensor) else torch.from_numpy(
+                        np.ascontiguousarray(insolation, dtype=np.float32))
+                    sol = sol.to(dev, dtype=torch.float32).contiguous()
+                    if tuple(sol.shape[1:]) != space:
+                        raise ValueError('rollout_with_forcing: insolation grid %s != input grid %s' % (tuple(sol.shape[1:]), space))
+                    sol = sol.unsqueeze(1)                                              # (T, 1, *space): one "variable"
+                    n_rows = int(sol.shape[0])
+                if sequence_steps > 1 and (int(start.min()) < 0 or last >= n_rows):
                     raise IndexError('rollout_with_forcing: insolation rows up to %d are needed, the array has %d'
-                                     % (last, sol.shape[0]))
+                                     % (last, n_rows))
                 zero = torch.zeros(1, dtype=torch.int32, device=dev)
                 steps_ar = np.arange(its, dtype=np.int64)
             elif c_main != c_out or i_solar:
@@ -1663,7 +1679,10 @@ class Model(object):
                     nxt = []
                     for m in range(n_out):
                         buf = torch.empty((B, its) + space + (1,), dtype=cdt, device=dev)
-                        ops.batch_gather(sol, idx_all[s, m], zero, buf.view((B * its,) + space + (1,)), 1, 0, 1, 0, 1, True)
+                        if lazy:
+                            ops.solar_fill(sol[0], sol[1], idx_all[s, m], buf.view((B * its,) + space + (1,)), 1, 0, 1, 0, 1, True)
+                        else:
+                            ops.batch_gather(sol, idx_all[s, m], zero, buf.view((B * its,) + space + (1,)), 1, 0, 1, 0, 1, True)
                         nxt.append(buf)
                     cur[i_main] = ops.state_repack(res[-1], nxt[0], its)
                     for m, i in enumerate(i_solar):
@@ -1675,7 +1694,8 @@ class Model(object):
             # inputs, insolation rows and gather indices are copied into the graph's static buffers, the series it returns lives in the
             # graph's pool and is overwritten by the next call with the same key (TimeSeriesEstimator downloads it at once).
             key = ('forcing', tuple(tuple(t.shape) for t in cur), str(cur[i_main].dtype), sequence_steps,
-                   None if insolation is None else tuple(sol.shape), os.environ.get('DLWPCS_OPTIONS', ''))
+                   None if insolation is None else (('tables',) + tuple(tuple(t.shape) for t in sol) if lazy else tuple(sol.shape)),
+                   os.environ.get('DLWPCS_OPTIONS', ''))
             g = self._infer_graphs.get(key) if (self.use_graphs and cur[i_main].is_cuda) else False
             if g is None:
                 n = self._seen_batch.get(key, 0)
@@ -1683,7 +1703,10 @@ class Model(object):
                 if n > 0:
                     self._ensure_packed(dev)
                     sin = [torch.empty_like(t).copy_(t) for t in cur]
-                    ssol = None if insolation is None else torch.empty_like(sol).copy_(sol)
+                    if lazy:
+                        ssol = tuple(torch.empty_like(t).copy_(t) for t in sol)     # (T x 4 and S x 3 values, not T x S)
+                    else:
+                        ssol = None if insolation is None else torch.empty_like(sol).copy_(sol)
                     sidx = None if idx_all is None else torch.empty_like(idx_all).copy_(idx_all)
                     sser = torch.empty((sequence_steps, n_out, B) + space + (c_out,), dtype=torch.float32, device=dev)
                     szero = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1710,7 +1733,10 @@ class Model(object):
             if g:
                 for dst, src in zip(g['in'], cur):
                     dst.copy_(src, non_blocking=True)
-                if g['sol'] is not None:
+                if lazy:
+                    for dst, src in zip(g['sol'], sol):
+                        dst.copy_(src, non_blocking=True)
+                elif g['sol'] is not None:
                     g['sol'].copy_(sol, non_blocking=True)
                 if g['idx'] is not None:
                     g['idx'].copy_(idx_all, non_blocking=True)

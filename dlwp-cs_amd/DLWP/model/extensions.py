@@ -128,7 +128,11 @@ class TimeSeriesEstimator(object):
     # ------------------------------------------------------------------------------------------------------------- #
     def _insolation_rows(self, n_rows):
         """insolation on the data's time grid for rows [0, n_rows): the generator's array, extended past its end with
-        DLWP.util.insolation when times and coordinates are known (the reference always recomputes, extensions.py:279-287)."""
+        DLWP.util.insolation when times and coordinates are known (the reference always recomputes, extensions.py:279-287).
+        A generator fed a DLWP.util.SolarForcing needs neither: the forcing continues itself, nothing dense is built."""
+        from ..util import SolarForcing
+        if isinstance(self.generator.insolation_array, SolarForcing):
+            return self.generator.insolation_array.rows(n_rows)
         have = np.asarray(self.generator.insolation_array, dtype=np.float32)
         if n_rows <= have.shape[0]:
             return have

@@ -14,7 +14,9 @@ class itself: tests/golden/g5_generators.npz):
 Two execution paths behind the same API:
 
   * host (default): numpy views/fancy indexing exactly like the reference (any model type: dense, recurrent, conv);
-  * `device=...` (MI355X): the data array, the insolation array and the constants are uploaded to HBM ONCE (a 40-year
+  * `device=...` (MI355X): the data array, the insolation array (or, for a `DLWP.util.SolarForcing`, only its two small
+    tables: the values are then computed by `dlwpcs_solar_fill` where the gather would have copied them) and the constants
+    are uploaded to HBM ONCE (a 40-year
     6-hourly C48 ERA5 set of 7 variables is 22 GB of the 288 GB) and `generate()` returns device tensors assembled by one
     gather kernel per tensor (`dlwpcs_batch_gather`: fancy-index + time-major channel packing + channels_last transpose +
     optional bf16 rounding in one pass) -- no host work, no PCIe traffic per batch.  `DLWPFunctional.fit_generator`
@@ -22,7 +24,7 @@ Two execution paths behind the same API:
 """
 import numpy as np
 
-from ..util import to_bool
+from ..util import SolarForcing, to_bool
 
 
 def delete_nan_samples(predictors, targets, large_fill_value=False, threshold=None):
@@ -317,7 +319,10 @@ class ArrayDataGenerator(object):
              'pdtype': backend.torch_dtype(dtype)}
         if self._remove_nan and bool(torch.isnan(d['array']).any().item()):
             raise NotImplementedError('remove_nan with NaNs present: use the host path (device=None)')
-        if self._add_insolation:
+        if self._add_insolation and isinstance(self.insolation_array, SolarForcing):
+            # described, not stored: two small tables, every value is computed where it is written (dlwpcs_solar_fill)
+            d['sol_row'], d['sol_cell'] = self.insolation_array.tables(dev)
+        elif self._add_insolation:
             d['sol'] = up(self.insolation_array).unsqueeze(1)                      # (T, 1, *space)
         if self.constants is not None:
             c = up(self.constants)                                                  # (Cc, *space)
@@ -343,6 +348,9 @@ class ArrayDataGenerator(object):
             lo, hi = int(samples.min()), int(samples.max())
             if lo < 0 or hi + last >= T:
                 raise IndexError('index %d is out of bounds for axis 0 with size %d' % (lo if lo < 0 else hi + last, T))
+            if 'sol_row' in d and hi + last >= int(d['sol_row'].shape[0]):
+                raise IndexError('index %d is out of bounds for the %d rows of the solar forcing'
+                                 % (hi + last, int(d['sol_row'].shape[0])))
         # (pinned + non_blocking: a pageable upload is a SYNCHRONOUS copy on the current stream, i.e. the host waited here for the
         # training step of the previous batch to finish before it could even enqueue this batch's gathers: generator-fed training
         # ran at 1.25 ms per step where the step itself takes 0.65 -- round 6)
@@ -358,10 +366,16 @@ class ArrayDataGenerator(object):
         def empty(c, dt, lead=()):
             return torch.empty(((n,) + lead + space + (c,)) if cl else ((n,) + lead + (c,) + space), dtype=dt,
                                device=self.device)
+
+        def solar(rows, out, n_steps, t_stride, c_off, c_stride):
+            if 'sol' in d:
+                ops.batch_gather(d['sol'], rows, d['zero'], out, n_steps, 0, t_stride, c_off, c_stride, cl)
+            else:
+                ops.solar_fill(d['sol_row'], d['sol_cell'], rows, out, n_steps, 0, t_stride, c_off, c_stride, cl)
         p = empty(cin, d['pdtype'])
         ops.batch_gather(d['array'], smp, d['vin'], p, its, 0, iv, 0, vin_n + add, cl)
         if add:
-            ops.batch_gather(d['sol'], smp, d['zero'], p, its, 0, iv, vin_n, vin_n + add, cl)
+            solar(smp, p, its, iv, vin_n, vin_n + add)
         targets = []
         for t_off, steps in self._windows():
             t = empty(steps * self._output_size, torch.float32)
@@ -374,7 +388,7 @@ class ArrayDataGenerator(object):
                 sol = empty(1, d['pdtype'], lead=(its,))
                 flat = sol.view((n * its,) + tuple(sol.shape[2:]))
                 idx = (smp.view(-1, 1) + iv * (its * s + torch.arange(its, device=self.device, dtype=torch.int32))).view(-1)
-                ops.batch_gather(d['sol'], idx.contiguous(), d['zero'], flat, 1, 0, 1, 0, 1, cl)
+                solar(idx.contiguous(), flat, 1, 1, 0, 1)
                 plist.append(sol)
         if 'const' in d:
             plist.append(d['const'].unsqueeze(0).expand((n,) + tuple(d['const'].shape)))

@@ -1529,6 +1529,36 @@ def batch_gather(array, samples, var_idx, out, n_steps, t_off, t_stride, c_off, 
     return out
 
 
+def solar_fill(row_tab, cell_tab, samples, out, n_steps, t_off, t_stride, c_off, c_stride, channels_last=True):
+    """
+    The computing twin of `batch_gather(insolation[:, None], samples, [0], out, ...)`: channel c_off + n*c_stride of `out`
+    <- the insolation of row samples + t_off + n*t_stride, computed from the tables of a DLWP.util.SolarForcing (row_tab (T, 4),
+    cell_tab (S, 3), float64 device tensors) instead of read from a dense array.  out (B, *space, Ctot) or (B, Ctot, *space),
+    float32 or bfloat16, written in place.  The rows are trusted: the caller checks 0 <= row < T.
+    """
+    require_device(out, 'solar_fill')
+    for t in (row_tab, cell_tab, samples):
+        if not isinstance(t, torch.Tensor) or t.device != out.device:
+            raise nat.NativeError('solar_fill: tables and samples must be tensors on the device of `out` (no CPU fallback)')
+    if row_tab.dtype != torch.float64 or cell_tab.dtype != torch.float64 or not row_tab.is_contiguous() or \
+            not cell_tab.is_contiguous() or not out.is_contiguous():
+        raise TypeError('solar_fill: tables must be contiguous float64, out contiguous')
+    if row_tab.dim() != 2 or row_tab.shape[1] != 4 or cell_tab.dim() != 2 or cell_tab.shape[1] != 3:
+        raise ValueError('solar_fill: row table (T, 4) and cell table (S, 3), got %s and %s'
+                         % (tuple(row_tab.shape), tuple(cell_tab.shape)))
+    if samples.dtype != torch.int32 or not samples.is_contiguous():
+        raise TypeError('solar_fill: samples must be a contiguous int32 device tensor')
+    T, S = int(row_tab.shape[0]), int(cell_tab.shape[0])
+    B = int(samples.numel())
+    Ctot = int(out.shape[-1] if channels_last else out.shape[1])
+    if out.numel() != B * S * Ctot:
+        raise ValueError('solar_fill: out shape %s does not match batch %d, space %d' % (tuple(out.shape), B, S))
+    check(lib().dlwpcs_solar_fill(ptr(row_tab), T, ptr(cell_tab), S, ptr(samples), B, int(n_steps), int(t_off), int(t_stride),
+                                  ptr(out), Ctot, int(c_off), int(c_stride), 1 if channels_last else 0, nat.dtype_tag(out),
+                                  stream_ptr()), 'dlwpcs_solar_fill')
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------ #
 # Forecast verification (DLWP/verify.py): one strided reduction, include/dlwpcs.h dlwpcs_score
 # ------------------------------------------------------------------------------------------------------------------ #

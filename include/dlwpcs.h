@@ -653,6 +653,21 @@ int dlwpcs_batch_gather(const void *array, int64_t T, int V, int64_t S, const in
                         int Ctot, int c_off, int c_stride, int channels_last, int dtype, dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Solar forcing (reference DLWP/util.py:306-364): the computing twin of a one-variable (nv = 1) batch_gather out of a dense
+ * (T, 1, S) insolation array.  Same output addressing, row r = samples[b] + t_off + n*t_stride (the caller guarantees
+ * 0 <= r < T), but the value is computed from two host-built fp64 tables (DLWP.util.SolarForcing) instead of read:
+ *   row_tab  (T, 4): {sin(decl), cos(decl), S0 * dist^-2, day}  -- day holds the host's fp32 fractional day of the year
+ *   cell_tab (S, 3): {sin(phi), cos(phi), lon / 360}            -- lon / 360 holds the host's fp32 quotient
+ *   out[..] = max(0, scale[r] * (sinphi[s] * sindec[r] - cosphi[s] * cosdec[r] * cos(hour))),  hour = f32(2 pi) * (day[r] + lonfrac[s])
+ * hour is formed with two rounded fp32 operations exactly as the host forms it, the cosine is the accurate cosf, the combine is
+ * fp64 without contraction, the result is rounded to fp32 and then to `dtype`: the result differs from DLWP.util.insolation only
+ * through the cosine, and a bf16 output is the round-to-nearest-even of the fp32 output.
+ * ------------------------------------------------------------------------------------------------------------- */
+int dlwpcs_solar_fill(const double *row_tab, int64_t T, const double *cell_tab, int64_t S, const int32_t *samples_dev, int B,
+                      int n_steps, int t_off, int t_stride, void *out, int Ctot, int c_off, int c_stride, int channels_last,
+                      int dtype, dlwpcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Data-parallel exchange: ONE in-place sum of the flat fp32 gradient buffer over the ranks, through an RCCL
  * communicator the caller owns, enqueued on the CALLER's stream -- inside a captured training step the collective is a plain
  * node of the step's graph between dlwpcs_wgrad_batch (reduction into the buffer) and dlwpcs_wgrad_batch_apply.
