@@ -125,6 +125,16 @@ class RowsDesc(ctypes.Structure):
                 ('src_stride', ctypes.c_int64 * SCORE_MAX_DIMS), ('out_stride', ctypes.c_int64 * SCORE_MAX_DIMS)]
 
 
+AFFINE_MUL_ADD, AFFINE_SUB_DIV = 0, 1
+AFFINE_MAX_CHANNELS = 1024
+
+
+class ChanDesc(ctypes.Structure):
+    """struct dlwpcs_chan_desc (include/dlwpcs.h)"""
+    _fields_ = [(n, ctypes.c_int64) for n in ('R', 'C', 'S', 'row_stride', 'chan_stride', 'inner_stride', 'dst_row_stride',
+                                              'dst_chan_stride', 'dst_inner_stride')]
+
+
 # name -> (restype, argtypes); must list EVERY symbol of include/dlwpcs.h (tests/test_abi.py checks this)
 PROTOTYPES = {
     'dlwpcs_version': (c_int, []),
@@ -221,6 +231,10 @@ PROTOTYPES = {
                                     c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'dlwpcs_solar_fill': (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_int, c_int, c_int, c_int,
                                   c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'dlwpcs_channel_moments_scratch_bytes': (c_size_t, [c_void_p, ctypes.c_int64]),
+    'dlwpcs_channel_moments': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                       c_void_p]),
+    'dlwpcs_channel_affine': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'dlwpcs_comm_load': (c_int, [ctypes.c_char_p]),
     'dlwpcs_comm_unique_id': (c_int, [c_void_p]),
     'dlwpcs_comm_init': (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int]),

@@ -1878,3 +1878,133 @@ def sparse_map_apply(m, x, space_axes, out=None):
         if y is not out:
             out.copy_(y)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# Per-variable scaling (DLWP/model/preprocessing.py): channel moments and the channel affine, include/dlwpcs.h dlwpcs_chan_desc
+# ------------------------------------------------------------------------------------------------------------------ #
+
+def _chan_desc(x, axis, y=None, row0=False):
+    """dlwpcs_chan_desc of the dims of x (and of y, same shape, its own strides) around the channel dim `axis`: the leading k dims
+    are the rows, every other dim the inner extent, and each group has to merge into one strided dim on every operand.  k = 1
+    (rows = dim 0) is tried first, then 0, then 2 .. axis; row0=True (a row list indexes dim 0) allows k = 1 only.  None when no
+    split can be described."""
+    nd = x.dim()
+    y = x if y is None else y
+    dims = [(int(x.shape[i]), int(x.stride(i)), int(y.stride(i))) for i in range(nd)]
+    if row0:
+        ks = [1] if axis >= 1 else []
+    else:
+        ks = [k for k in [1, 0] + list(range(2, axis + 1)) if k <= axis]
+    for k in ks:
+        rows, inner = _fold(dims[:k]), _fold(dims[k:axis] + dims[axis + 1:])
+        if len(rows) > 1 or len(inner) > 1:
+            continue
+        r, s = (rows or [(1, 0, 0)])[0], (inner or [(1, 0, 0)])[0]
+        if min(r[1:] + s[1:] + dims[axis][1:]) < 0:
+            continue
+        d = nat.ChanDesc()
+        d.R, d.row_stride, d.dst_row_stride = r
+        d.S, d.inner_stride, d.dst_inner_stride = s
+        d.C, d.chan_stride, d.dst_chan_stride = dims[axis]
+        return d
+    return None
+
+
+def channel_moments(x, axis=1, rows=None, center=None, skipna=False, as_numpy=False):
+    """
+    {count, sum (x - center[c]), sum (x - center[c])^2} of every channel c along `axis` of the fp32 device tensor x, over the rows
+    (entries of dim 0) in `rows` -- numpy ints, checked and uploaded, or an int32 device tensor, trusted; duplicates count as
+    given; None = all -- and over every other dim.  center: None (0) or C float64 values (numpy or a device tensor).  skipna:
+    leave NaN elements out of all three (else they propagate into the sums).  fp64 sums in an order fixed by the shape: the
+    same call gives the same bits.  Views are read through their strides where dim 0, the channel dim and the merged rest
+    describe them (channels-first and channels-last arrays and their channel / row slices do), otherwise copied with
+    .contiguous().  Returns a (C, 3) float64 device tensor; two launches on the current stream, no host synchronisation.
+    as_numpy=True downloads it (one synchronisation).
+    """
+    require_device(x, 'channel_moments')
+    if x.dtype != torch.float32:
+        raise TypeError('channel_moments: x must be float32, got %s' % x.dtype)
+    axis = axis % x.dim()
+    dev = x.device
+    n_rows, rows_d = 0, None
+    if rows is not None:
+        if axis == 0:
+            raise ValueError('channel_moments: a row list selects entries of dim 0, which is the channel dim here')
+        if isinstance(rows, torch.Tensor):
+            if rows.dtype != torch.int32 or rows.device != dev or not rows.is_contiguous():
+                raise TypeError('channel_moments: a device row list must be contiguous int32 on the device of x')
+            rows_d = rows.reshape(-1)
+        else:
+            rh = np.asarray(rows, dtype=np.int64).reshape(-1)
+            if rh.size and (rh.min() < 0 or rh.max() >= int(x.shape[0])):
+                raise IndexError('channel_moments: row index out of range of the %d rows' % int(x.shape[0]))
+            rows_d = rh
+        n_rows = int(rows_d.numel() if isinstance(rows_d, torch.Tensor) else rows_d.size)
+    d = _chan_desc(x, axis, row0=rows is not None)
+    if d is None:
+        x = x.contiguous()
+        d = _chan_desc(x, axis, row0=rows is not None)
+    C = int(d.C)
+    with torch.cuda.device(dev):
+        out = torch.empty((C, 3), dtype=torch.float64, device=dev)
+        if C == 0:
+            return out.cpu().numpy() if as_numpy else out
+        if rows is not None and n_rows == 0:
+            out.zero_()
+            return out.cpu().numpy() if as_numpy else out
+        if rows_d is not None and not isinstance(rows_d, torch.Tensor):
+            rows_d = _int32_dev(rows_d, dev)
+        ctr = None
+        if center is not None:
+            if isinstance(center, torch.Tensor):
+                ctr = center.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+            else:
+                ctr = torch.from_numpy(np.ascontiguousarray(np.asarray(center, dtype=np.float64).reshape(-1))).to(dev)
+            if ctr.numel() != C:
+                raise ValueError('channel_moments: center has %d entries, the array %d channels' % (ctr.numel(), C))
+        nbytes = int(lib().dlwpcs_channel_moments_scratch_bytes(ctypes.byref(d), n_rows))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        check(lib().dlwpcs_channel_moments(ctypes.byref(d), x.data_ptr(), ptr(rows_d), n_rows, ptr(ctr), 1 if skipna else 0,
+                                           out.data_ptr(), ptr(scratch), nbytes, stream_ptr()), 'dlwpcs_channel_moments')
+    return out.cpu().numpy() if as_numpy else out
+
+
+def channel_affine(x, a, b, mode, axis=1, out=None):
+    """
+    out = x * a[c] + b[c] (mode nat.AFFINE_MUL_ADD) or (x - b[c]) / a[c] (nat.AFFINE_SUB_DIV) with c the index along `axis`:
+    fp32 device tensors, a and b of C entries, two separately rounded fp32 operations per element.  `out`: a float32 tensor or
+    view of x's shape with any layout (a permuted buffer changes the layout in the same pass; `out is x` works in place);
+    default a new contiguous tensor.  Views are read and written through their strides where leading dims, the channel dim
+    and the merged rest describe both sides; otherwise x is copied with .contiguous() and the result goes through a contiguous
+    temporary.  One launch on the current stream, no host synchronisation.  A descriptor the library does not serve raises
+    NotImplementedError.
+    """
+    require_device(x, 'channel_affine')
+    dev = x.device
+    axis = axis % x.dim()
+    for t, what in ((x, 'x'), (a, 'a'), (b, 'b')):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev:
+            raise TypeError('channel_affine: %s must be a float32 tensor on %s' % (what, dev))
+    C = int(x.shape[axis])
+    a, b = a.reshape(-1).contiguous(), b.reshape(-1).contiguous()
+    if a.numel() != C or b.numel() != C:
+        raise ValueError('channel_affine: tables of %d and %d entries, the array has %d channels' % (a.numel(), b.numel(), C))
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev or out.shape != x.shape:
+        raise ValueError('channel_affine: out must be a float32 tensor of shape %s on %s' % (tuple(x.shape), dev))
+    if out.numel() == 0:
+        return out
+    y = out
+    d = _chan_desc(x, axis, y)
+    if d is None:                           # the documented fallback: contiguous operands
+        x = x.contiguous()
+        y = out if out.is_contiguous() else torch.empty(x.shape, dtype=torch.float32, device=dev)
+        d = _chan_desc(x, axis, y)
+    with torch.cuda.device(dev):
+        check(lib().dlwpcs_channel_affine(ctypes.byref(d), x.data_ptr(), a.data_ptr(), b.data_ptr(), int(mode), y.data_ptr(),
+                                          stream_ptr()), 'dlwpcs_channel_affine')
+        if y is not out:
+            out.copy_(y)
+    return out

@@ -668,6 +668,53 @@ int dlwpcs_solar_fill(const double *row_tab, int64_t T, const double *cell_tab, 
                       int dtype, dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Per-variable data scaling (reference DLWP/model/preprocessing.py:645-682 data_to_series(scale_variables=True), :844-882
+ * mean_by_batch / std_by_batch; Tutorial 4 cell 19 undoes it on every forecast).  Both calls see an fp32 device array as
+ * (R rows, C channels, S inner elements), element (r, c, s) at r * row_stride + c * chan_stride + s * inner_stride, strides in
+ * ELEMENTS and >= 0:
+ *   channels-first (T, V, S):      R = T, C = V, strides (V * S, S, 1)
+ *   channels-last  (R * S, C):     the row extent folded into S: R = 1, strides (0, 1, C), or (S * C, 1, C)
+ * dst_* are the strides of the output of dlwpcs_channel_affine (dlwpcs_channel_moments ignores them).
+ *
+ * dlwpcs_channel_moments: out[c] = {n, s1, s2} (double[C][3]) over the selected rows and all S inner elements of channel c:
+ * n = the count, s1 = sum (x - center[c]), s2 = sum (x - center[c])^2, the difference formed in fp64, the sums fp64.
+ * center: fp64 device table of C entries, NULL = 0.  rows: int32 device list of n_rows source rows (the training subset;
+ * duplicates and any order are legal and counted as given; every entry in [0, R) -- TRUSTED), NULL = all R rows in order
+ * (n_rows is ignored).  skipna = 0: NaN propagates into s1 / s2 (numpy .sum()) and n counts every element; 1: NaN elements
+ * are left out of all three.  No floating-point atomics: launch 1 gives every (channel, column tile, row slab) a workgroup
+ * that writes one partial triple to scratch, launch 2 adds a channel's partials in index order -- the partition depends on
+ * the descriptor and n_rows only, so two calls give the same bits.  scratch >= dlwpcs_channel_moments_scratch_bytes(d, n_rows)
+ * (n_rows <= 0 there = all rows), 8-byte aligned.  16-byte loads when inner_stride == 1, S % 4 == 0 and every row / channel
+ * start is 16-byte aligned; one element per lane, any strides, otherwise.
+ *
+ * dlwpcs_channel_affine: dst(r, c, s) = src(r, c, s) * a[c] + b[c]   (DLWPCS_AFFINE_MUL_ADD: Tutorial 4 cell 19)
+ *                                    or (src(r, c, s) - b[c]) / a[c]   (DLWPCS_AFFINE_SUB_DIV: preprocessing.py:660)
+ * with fp32 device tables a, b of C entries.  Two separately rounded fp32 operations, never an fma; NaN / inf as IEEE gives
+ * them.  Source and destination have their own strides (channels-last in, channels-first out is cell 17 + 19 in one launch);
+ * dst == src with equal strides is legal, any other overlap is not.  Paths: both sides inner-contiguous with S % 4 == 0 and
+ * 16-byte aligned: 16-byte loads and stores along a row; both sides one flat channels-last stream (chan stride 1, inner stride
+ * C, rows back to back): 16-byte loads and stores over the stream, the tables in LDS; anything else: one element per lane,
+ * lanes along the destination's contiguous dim.  C > DLWPCS_AFFINE_MAX_CHANNELS or more than 2^31 - 1 elements in a row of
+ * the one-element path: DLWPCS_E_UNSUPPORTED.
+ * One launch (moments: two), no host synchronisation, no allocation.  A zero extent returns DLWPCS_OK without a launch
+ * (moments: out is zeroed).
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_AFFINE_MUL_ADD 0
+#define DLWPCS_AFFINE_SUB_DIV 1
+#define DLWPCS_AFFINE_MAX_CHANNELS 1024
+typedef struct dlwpcs_chan_desc {
+    int64_t R, C, S;
+    int64_t row_stride, chan_stride, inner_stride;
+    int64_t dst_row_stride, dst_chan_stride, dst_inner_stride;
+} dlwpcs_chan_desc;
+size_t dlwpcs_channel_moments_scratch_bytes(const dlwpcs_chan_desc *d, int64_t n_rows);
+int dlwpcs_channel_moments(const dlwpcs_chan_desc *d, const float *src, const int32_t *rows, int64_t n_rows,
+                           const double *center, int skipna, double *out, void *scratch, size_t scratch_bytes,
+                           dlwpcs_stream_t stream);
+int dlwpcs_channel_affine(const dlwpcs_chan_desc *d, const float *src, const float *a, const float *b, int mode, float *dst,
+                          dlwpcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Data-parallel exchange: ONE in-place sum of the flat fp32 gradient buffer over the ranks, through an RCCL
  * communicator the caller owns, enqueued on the CALLER's stream -- inside a captured training step the collective is a plain
  * node of the step's graph between dlwpcs_wgrad_batch (reduction into the buffer) and dlwpcs_wgrad_batch_apply.
