@@ -107,6 +107,12 @@ class ScoreDesc(ctypes.Structure):
                 ('keep_stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 4), ('red_stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 4)]
 
 
+class OverlapDesc(ctypes.Structure):
+    """struct dlwpcs_overlap_desc (include/dlwpcs.h)"""
+    _fields_ = [('N', ctypes.c_int32), ('n_lat', ctypes.c_int32), ('n_lon', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('frames', ((ctypes.c_double * 3) * 3) * 6), ('dust', ctypes.c_double)]
+
+
 class SparseMapDesc(ctypes.Structure):
     """struct dlwpcs_sparse_map_desc (include/dlwpcs.h)"""
     _fields_ = [('n_a', ctypes.c_int64), ('n_b', ctypes.c_int64), ('nnz', ctypes.c_int64), ('x_dtype', ctypes.c_int32),
@@ -211,6 +217,8 @@ PROTOTYPES = {
                                   c_void_p, c_size_t, c_void_p]),
     'dlwpcs_rows_gather': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_overlap_count': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_overlap_fill': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p]),
     'dlwpcs_adam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,
                                  c_float, c_float, c_float, c_void_p]),
     'dlwpcs_adam_step_fused': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,

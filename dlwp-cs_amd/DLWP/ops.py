@@ -1881,6 +1881,44 @@ def sparse_map_apply(m, x, space_axes, out=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------ #
+# Conservative map generation (DLWP/remap/overlap.py): overlap areas of lat-lon and cube cells, include/dlwpcs.h dlwpcs_overlap_desc
+# ------------------------------------------------------------------------------------------------------------------ #
+
+def overlap_csr(cube, ll, dust, device):
+    """
+    The overlap areas of the cells of a DLWP.remap LatLonGrid and CubeSphereGrid as device tensors (row_ptr int64
+    [n_lat * n_lon + 1], col int32, area float64): dlwpcs_overlap_count, an exclusive scan, dlwpcs_overlap_fill, on the current
+    stream of `device`.  The number of entries is read back between the two launches (one host synchronisation).
+    """
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise nat.NativeError('overlap_csr: %s is not a HIP device (device=None runs the host twin)' % dev)
+    d = nat.OverlapDesc()
+    d.N, d.n_lat, d.n_lon, d.dust = int(cube.N), int(ll.n_lat), int(ll.n_lon), float(dust)
+    fr = np.ascontiguousarray(cube.frames, dtype=np.float64)
+    ctypes.memmove(ctypes.addressof(d.frames), fr.ctypes.data, fr.nbytes)
+    n = int(ll.n_lat) * int(ll.n_lon)
+    with torch.cuda.device(dev):
+        sl = torch.from_numpy(np.ascontiguousarray(ll.sin_lat_edges, dtype=np.float64)).to(dev)
+        lo = torch.from_numpy(np.ascontiguousarray(ll.lon_edges_rad, dtype=np.float64)).to(dev)
+        counts = torch.empty(n, dtype=torch.int32, device=dev)
+        check(lib().dlwpcs_overlap_count(ctypes.byref(d), ptr(sl), ptr(lo), ptr(counts), stream_ptr()), 'dlwpcs_overlap_count')
+        row_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, dtype=torch.int64, out=row_ptr[1:])
+        nnz = int(row_ptr[-1].item())
+        col = torch.empty(nnz, dtype=torch.int32, device=dev)
+        area = torch.empty(nnz, dtype=torch.float64, device=dev)
+        check(lib().dlwpcs_overlap_fill(ctypes.byref(d), ptr(sl), ptr(lo), ptr(row_ptr), ptr(col), ptr(area), nnz, stream_ptr()),
+              'dlwpcs_overlap_fill')
+    return row_ptr, col, area
+
+
+def overlap_areas(cube, ll, dust, device):
+    """overlap_csr brought back to the host: (row_ptr int64, col int32, area float64) numpy arrays"""
+    return tuple(t.cpu().numpy() for t in overlap_csr(cube, ll, dust, device))
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
 # Per-variable scaling (DLWP/model/preprocessing.py): channel moments and the channel affine, include/dlwpcs.h dlwpcs_chan_desc
 # ------------------------------------------------------------------------------------------------------------------ #
 

@@ -2,14 +2,17 @@
 Remapping between the cubed sphere and a lat-lon grid with existing offline maps (reference DLWP/remap/cubesphere.py).
 
 The reference drives TempestRemap's executables on netCDF files.  Here the maps are read once (DLWP.remap.read_offline_map)
-and applied to arrays: device tensors by the dlwpcs_sparse_map_apply kernel where they lie, numpy arrays on the host.  The
-file-to-file methods need TempestRemap or xarray, which this stack does not have; they raise NotImplementedError.
+and applied to arrays: device tensors by the dlwpcs_sparse_map_apply kernel where they lie, numpy arrays on the host.  Maps
+that do not exist yet are made by `generate_maps` (closed-form conservative maps, DLWP.remap.overlap).  The file-to-file
+methods need TempestRemap or xarray, which this stack does not have; they raise NotImplementedError.
 """
 import os
 import sys
 
 from ..model.extensions import Forecast
-from .offline_map import OfflineMap, read_offline_map
+from .grid import CubeSphereGrid, LatLonGrid
+from .offline_map import OfflineMap, read_offline_map, write_offline_map
+from .overlap import conservative_maps
 
 _CUBE_DIMS = (('x0', 'x1', 'x2'), ('face', 'height', 'width'))
 _FILE_MSG = ('CubeSphereRemap.%s needs the TempestRemap executables or xarray, which this engine does not use; apply an '
@@ -38,6 +41,49 @@ class CubeSphereRemap(object):
         self._map_exists = False
         self._inverse_map_exists = False
         self._loaded = {}
+        self.cube_grid = None
+        self.latlon_grid = None
+
+    def generate_maps(self, lat=None, lon=None, res=None, inverse_lat=False, lon_begin=0., *, grid=None, latlon=None,
+                      device=None, map_name=None, inverse_map_name=None):
+        """
+        Make the forward (lat-lon -> cube) and inverse (cube -> lat-lon) first-order conservative maps and assign them, so that
+        remap_array / inverse_remap_array / inverse_remap_forecast work at once.  The grids are kept as `.cube_grid` and
+        `.latlon_grid` (cell centres for SolarForcing / TimeSeriesEstimator, cell areas).
+
+        :param lat, lon: int: number of cells in latitude and longitude (as GenerateRLLMesh --lat --lon)
+        :param res: int: number of cells on a side of each cube face
+        :param inverse_lat: the latitudes of the data descend from 90
+        :param lon_begin: the first longitude edge in degrees
+        :param grid: CubeSphereGrid in place of `res` (e.g. CubeSphereGrid.from_centres of an existing data set)
+        :param latlon: LatLonGrid in place of `lat`, `lon`, `inverse_lat` and `lon_begin`
+        :param device: a HIP device: the overlap areas are computed by the dlwpcs_overlap_* kernels; None: on the host
+        :param map_name, inverse_map_name: str: also write the map to this file (64-bit-offset netCDF, SCRIP layout)
+        :return: (forward, inverse) OfflineMap
+        """
+        if latlon is None:
+            if lat is None or lon is None:
+                raise ValueError('generate_maps needs lat and lon, or latlon=')
+            latlon = LatLonGrid.cells(int(lat), int(lon), inverse_lat=inverse_lat, lon_begin=lon_begin)
+        elif not isinstance(latlon, LatLonGrid):
+            raise TypeError('latlon must be a DLWP.remap.LatLonGrid')
+        if grid is None:
+            if res is None:
+                raise ValueError('generate_maps needs res, or grid=')
+            grid = CubeSphereGrid(int(res))
+        elif not isinstance(grid, CubeSphereGrid):
+            raise TypeError('grid must be a DLWP.remap.CubeSphereGrid')
+        forward, inverse = conservative_maps(grid, latlon, device=device)
+        forward.name = 'map_LL%dx%d_CS%d' % (latlon.n_lat, latlon.n_lon, grid.N)
+        inverse.name = 'map_CS%d_LL%dx%d' % (grid.N, latlon.n_lat, latlon.n_lon)
+        self._lat, self._lon, self._res = latlon.n_lat, latlon.n_lon, grid.N
+        self.cube_grid, self.latlon_grid = grid, latlon
+        if map_name is not None:
+            write_offline_map(forward, map_name)
+        if inverse_map_name is not None:
+            write_offline_map(inverse, inverse_map_name)
+        self.assign_maps(forward, inverse)
+        return forward, inverse
 
     def assign_maps(self, map_name=None, inverse_map_name=None):
         """

@@ -1,8 +1,8 @@
 """
-A small reader of netCDF classic files (CDF-1) and 64-bit-offset files (CDF-2), after the public "NetCDF Classic and 64-bit
-Offset Format" specification: big-endian header of dimensions, global attributes and variables, then the data of the
-fixed-size variables and the interleaved records.  numpy is the only dependency.  netCDF-4 (HDF5) and CDF-5 files are not
-read.
+A small reader of netCDF classic files (CDF-1) and 64-bit-offset files (CDF-2), and a writer of the latter, after the public
+"NetCDF Classic and 64-bit Offset Format" specification: big-endian header of dimensions, global attributes and variables,
+then the data of the fixed-size variables and the interleaved records.  numpy is the only dependency.  netCDF-4 (HDF5) and
+CDF-5 files are not read; the writer makes fixed-size variables only (no record dimension).
 """
 import os
 
@@ -159,3 +159,82 @@ class NetCDFClassic(object):
         if dt == np.dtype('S1'):
             return out.copy()
         return out.astype(dt.newbyteorder('='))
+
+
+_TYPE_IDS = {np.dtype(dt.str[1:]): t for t, dt in _TYPES.items() if t != 2}
+
+
+def _pad4(b):
+    return b + b'\0' * ((-len(b)) % 4)
+
+
+def _name(s):
+    b = s.encode('utf-8')
+    return np.array(len(b), '>u4').tobytes() + _pad4(b)
+
+
+def _attributes(attrs):
+    if not attrs:
+        return np.zeros(2, '>u4').tobytes()
+    out = np.array([NC_ATTRIBUTE, len(attrs)], '>u4').tobytes()
+    for k, v in attrs.items():
+        if isinstance(v, str):
+            raw, t, n = v.encode('utf-8'), 2, len(v.encode('utf-8'))
+        else:
+            a = np.atleast_1d(np.asarray(v))
+            if a.dtype not in _TYPE_IDS:
+                a = a.astype(np.int32 if np.issubdtype(a.dtype, np.integer) else np.float64)
+            raw, t, n = a.astype(_TYPES[_TYPE_IDS[a.dtype]]).tobytes(), _TYPE_IDS[a.dtype], a.size
+        out += _name(k) + np.array([t, n], '>u4').tobytes() + _pad4(raw)
+    return out
+
+
+def write_netcdf(path, dims, variables, attrs=None):
+    """
+    Write a 64-bit-offset (CDF-2) netCDF file of fixed-size variables.
+
+    :param dims: {name: length}, every length positive (a zero length would declare the record dimension)
+    :param variables: iterable of (name, dim names, array) or (name, dim names, array, attributes); int8 / int16 / int32 /
+        float32 / float64 arrays are stored as they are, other integers as int32 (checked) and other floats as float64
+    :param attrs: global attributes {name: str or numbers}
+    """
+    names = list(dims)
+    for d, n in dims.items():
+        if int(n) < 1 or int(n) >= 2 ** 31:
+            raise ValueError('dimension %s = %r: a fixed dimension has 1 .. 2^31 - 1 entries' % (d, n))
+    head = b'CDF\x02' + np.zeros(1, '>u4').tobytes()
+    head += np.array([NC_DIMENSION, len(names)], '>u4').tobytes() if names else np.zeros(2, '>u4').tobytes()
+    for d in names:
+        head += _name(d) + np.array(int(dims[d]), '>u4').tobytes()
+    head += _attributes(attrs)
+    entries = []
+    for var in variables:
+        vn, vd, arr = var[0], tuple(var[1]), np.asarray(var[2])
+        va = var[3] if len(var) > 3 else None
+        if arr.dtype not in _TYPE_IDS:
+            if np.issubdtype(arr.dtype, np.integer):
+                if arr.size and (arr.min() < -2 ** 31 or arr.max() >= 2 ** 31):
+                    raise ValueError('variable %s does not fit int32' % vn)
+                arr = arr.astype(np.int32)
+            else:
+                arr = arr.astype(np.float64)
+        shape = tuple(int(dims[d]) for d in vd)
+        if arr.size != int(np.prod(shape, dtype=np.int64)):
+            raise ValueError('variable %s has %d values, its dimensions %s hold %s' % (vn, arr.size, vd, shape))
+        t = _TYPE_IDS[arr.dtype]
+        raw = _pad4(np.ascontiguousarray(arr).astype(_TYPES[t]).tobytes())
+        if len(raw) >= 2 ** 32:
+            raise ValueError('variable %s is too large for the 64-bit-offset format' % vn)
+        meta = _name(vn) + np.array([len(vd)] + [names.index(d) for d in vd], '>u4').tobytes() + _attributes(va) + \
+            np.array([t, len(raw)], '>u4').tobytes()
+        entries.append((meta, raw))
+    head += np.array([NC_VARIABLE, len(entries)], '>u4').tobytes() if entries else np.zeros(2, '>u4').tobytes()
+    begin = len(head) + sum(len(m) + 8 for m, _ in entries)
+    with open(path, 'wb') as f:
+        body = b''
+        for meta, raw in entries:
+            body += meta + np.array(begin, '>u8').tobytes()
+            begin += len(raw)
+        f.write(head + body)
+        for _, raw in entries:
+            f.write(raw)

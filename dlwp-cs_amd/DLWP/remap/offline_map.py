@@ -9,7 +9,7 @@ import sys
 
 import numpy as np
 
-from .netcdf_classic import NetCDFClassic
+from .netcdf_classic import NetCDFClassic, write_netcdf
 
 _REQUIRED = ('row', 'col', 'S')
 _NETCDF4_MSG = ('%s is a netCDF-4 (HDF5) file, which is not read; convert it to the 64-bit-offset format with '
@@ -73,13 +73,15 @@ class OfflineMap(object):
     :param src_grid_dims, dst_grid_dims: SCRIP grid dims (fastest axis first): rank 1 of 6 N^2 cells is a cubed sphere
         (6, N, N) in face-major order; rank 2 is a lat-lon grid, whose orientation is checked against yc / xc
     :param yc_a, xc_a, yc_b, xc_b: cell-centre latitudes / longitudes in degrees (optional)
+    :param area_a, area_b, frac_b: cell areas in steradians of the two grids and the covered fraction of every destination
+        cell (optional; carried, not used by `apply`)
 
     Entries are sorted stably by row into CSR (`row_ptr` int32 [n_b + 1], `col` int32 0-based, `val` fp32, `val64` fp64);
     duplicate (row, col) pairs stay separate terms, empty rows are allowed.  Raises ValueError for entries that do not fit.
     """
 
     def __init__(self, row, col, S, n_a, n_b, src_grid_dims=None, dst_grid_dims=None, yc_a=None, xc_a=None, yc_b=None,
-                 xc_b=None, name=None):
+                 xc_b=None, name=None, area_a=None, area_b=None, frac_b=None):
         self.name = name
         self.n_a, self.n_b = int(n_a), int(n_b)
         if self.n_a < 0 or self.n_b < 0:
@@ -114,6 +116,11 @@ class OfflineMap(object):
         self.lat_a, self.lon_a, self.lat_b, self.lon_b = src.lat, src.lon, dst.lat, dst.lon
         self.yc_a, self.xc_a = self._ordered(yc_a, src.order), self._ordered(xc_a, src.order)
         self.yc_b, self.xc_b = self._ordered(yc_b, dst.order), self._ordered(xc_b, dst.order)
+        self.area_a, self.area_b = self._ordered(area_a, src.order), self._ordered(area_b, dst.order)
+        self.frac_b = self._ordered(frac_b, dst.order)
+        for a, n, nm in ((self.area_a, self.n_a, 'area_a'), (self.area_b, self.n_b, 'area_b'), (self.frac_b, self.n_b, 'frac_b')):
+            if a is not None and a.size != n:
+                raise ValueError('%s has %d entries for %d cells' % (nm, a.size, n))
         order = np.argsort(row0, kind='stable')
         self.row_ptr = np.zeros(self.n_b + 1, dtype=np.int32)
         np.cumsum(np.bincount(row0, minlength=self.n_b), out=self.row_ptr[1:])
@@ -213,8 +220,35 @@ def read_offline_map(path):
     for d in ('n_a', 'n_b'):
         if d not in nc.dims:
             raise ValueError('%s: required dimension %s missing' % (path, d))
-    opt = {v: (nc.read(v) if v in nc else None) for v in ('src_grid_dims', 'dst_grid_dims', 'yc_a', 'xc_a', 'yc_b', 'xc_b')}
-    m = OfflineMap(nc.read('row'), nc.read('col'), nc.read('S'), nc.dims['n_a'], nc.dims['n_b'],
-                   name=os.path.basename(path), **opt)
-    m.frac_b = m._ordered(nc.read('frac_b'), m._dst_order) if 'frac_b' in nc else None
-    return m
+    opt = {v: (nc.read(v) if v in nc else None) for v in ('src_grid_dims', 'dst_grid_dims', 'yc_a', 'xc_a', 'yc_b', 'xc_b',
+                                                          'area_a', 'area_b', 'frac_b')}
+    return OfflineMap(nc.read('row'), nc.read('col'), nc.read('S'), nc.dims['n_a'], nc.dims['n_b'],
+                      name=os.path.basename(path), **opt)
+
+
+def _scrip_dims(kind, shape):
+    return [int(shape[1]), int(shape[0])] if kind == 'latlon' else [int(np.prod(shape, dtype=np.int64))]
+
+
+def write_offline_map(m, path):
+    """
+    Write an OfflineMap as a 64-bit-offset netCDF file in the SCRIP layout that read_offline_map reads: n_a, n_b, n_s, row, col
+    (1-based), S (fp64), the grid dims (fastest axis first; a lat-lon grid is written lat-major, as the map holds it) and
+    whichever of yc_* / xc_* / area_* / frac_b the map carries.
+    """
+    if m.nnz < 1 or m.n_a < 1 or m.n_b < 1:
+        raise ValueError('%s has no entries or no cells: nothing to write' % m)
+    src, dst = _scrip_dims(m.src_kind, m.src_shape), _scrip_dims(m.dst_kind, m.dst_shape)
+    dims = {'n_a': m.n_a, 'n_b': m.n_b, 'n_s': m.nnz, 'src_grid_rank': len(src), 'dst_grid_rank': len(dst)}
+    row = np.repeat(np.arange(1, m.n_b + 1, dtype=np.int32), np.diff(m.row_ptr.astype(np.int64)))
+    variables = [('src_grid_dims', ('src_grid_rank',), np.array(src, np.int32)),
+                 ('dst_grid_dims', ('dst_grid_rank',), np.array(dst, np.int32))]
+    for nm, units in (('yc', 'degrees'), ('xc', 'degrees'), ('area', 'steradians')):
+        for side in 'ab':
+            a = getattr(m, '%s_%s' % (nm, side), None)
+            if a is not None:
+                variables.append(('%s_%s' % (nm, side), ('n_%s' % side,), a, {'units': units}))
+    if getattr(m, 'frac_b', None) is not None:
+        variables.append(('frac_b', ('n_b',), m.frac_b))
+    variables += [('row', ('n_s',), row), ('col', ('n_s',), m.col.astype(np.int32) + 1), ('S', ('n_s',), m.val64)]
+    write_netcdf(path, dims, variables, attrs={'title': 'first-order conservative offline map', 'normalization': 'destarea'})

@@ -609,6 +609,30 @@ typedef struct dlwpcs_sparse_map_desc {
 int dlwpcs_sparse_map_apply(const dlwpcs_sparse_map_desc *d, const int32_t *row_ptr, const int32_t *col, const float *val,
                             const void *x, float *y, dlwpcs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------- *
+ * Conservative offline maps made on the device (DLWP/remap/overlap.py is the host twin and states the maths): A[r, c], the
+ * area in steradians of (lat-lon cell r) intersected with (equiangular cubed-sphere cell c), in closed form and fp64, in CSR
+ * form over the lat-lon cells (lat-major).  The cube is given by its face frames {e0, eu, ev} (centre, width and height
+ * direction; a point of face f at edge tangents (x, y) is normalize(e0 + x eu + y ev), the cell edges lie at
+ * tan(-pi/4 + k pi / (2N)) with +-1 and 0 exact), the lat-lon grid by sin(latitude) of its n_lat + 1 edges (monotone either
+ * way, +-1 exact at a pole) and its n_lon + 1 ascending longitude edges in radians spanning 2 pi.
+ * Two phases, so that no atomic decides an order: dlwpcs_overlap_count writes counts[r], the number of entries of row r with
+ * A > dust * min(area_r, area_c) (cells that only share an edge give |A| of rounding size); the caller scans the counts
+ * exclusively into row_ptr[n_lat * n_lon + 1]; dlwpcs_overlap_fill writes col (cube cells (f * N + i) * N + j, ascending
+ * within a row) and area at row_ptr[r] ....  It never writes at or beyond nnz nor beyond a row's end, whatever row_ptr holds.
+ * One lane per lat-lon cell; candidates per face come from a bounding cap of the cell, not from all pairs.  The same call
+ * gives the same bits.  One launch each, no host synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct dlwpcs_overlap_desc {
+    int32_t N, n_lat, n_lon, reserved;
+    double frames[6][3][3];             /* [face][e0, eu, ev][x, y, z] */
+    double dust;                        /* >= 0; DLWP.remap uses 1e-10 */
+} dlwpcs_overlap_desc;
+int dlwpcs_overlap_count(const dlwpcs_overlap_desc *d, const double *sin_lat_edges, const double *lon_edges, int32_t *counts,
+                         dlwpcs_stream_t stream);
+int dlwpcs_overlap_fill(const dlwpcs_overlap_desc *d, const double *sin_lat_edges, const double *lon_edges,
+                        const int64_t *row_ptr, int32_t *col, double *area, int64_t nnz, dlwpcs_stream_t stream);
+
 int dlwpcs_adam_step(float *p, const float *g, float *m, float *v, size_t n, int32_t *step_dev,
                      float lr, float beta1, float beta2, float eps, float grad_scale, dlwpcs_stream_t stream);
 /* Same update as one launch: `state_dev` points to TWO device int32 {t-1, 0}; the second is a ticket counter (must be 0
