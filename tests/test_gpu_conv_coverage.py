@@ -388,10 +388,10 @@ _TL = 'conv_mfma_ws_kernel<unsigned short, 3, 16, 3, 1, 1, 4, 8, 2, false, false
 UNREACHABLE = {
     _TL: 'pre-masked padded-grid data gradient, > 64 channels, face > 320 px, SPLIT_N off: the gather form takes such layers '
          '(conv_mfma.hip conv_bwd_data_impl, DLWPCS_CONV_DGRAD_GATHER branch) unless dgrad_gather=0 as well',
-    'pw_head_train_kernel<1>': 'fused training tail dlwpcs_head_mse_step (conv_mfma.hip:1637), not launched by cs_conv; '
-                               'test_gpu_head_fold.py',
-    'pw_head_train_kernel<2>': 'fused training tail dlwpcs_head_mse_step (conv_mfma.hip:1638), not launched by cs_conv; '
-                               'test_gpu_head_fold.py',
+    'pw_head_train_kernel<1>': 'fused training tail dlwpcs_head_mse_step (conv_mfma.hip head_launch), not launched by cs_conv; '
+                               'test_gpu_pointwise_head.py',
+    'pw_head_train_kernel<2>': 'fused training tail dlwpcs_head_mse_step (conv_mfma.hip head_launch), not launched by cs_conv; '
+                               'test_gpu_pointwise_head.py',
     'wgrad_batch_kernel': 'batched weight gradient of a whole backward pass (wgrad_batch.hip, ops.flush_wgrad_batch), '
                           'not per-layer cs_conv; test_gpu_wgrad_batch.py',
     'wb_reduce_kernel': 'reduction of the batched weight gradient (wgrad_batch.hip), not per-layer cs_conv; '

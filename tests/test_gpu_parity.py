@@ -769,6 +769,66 @@ def _adam_fused_case(rng, n):
     assert rel_err(pb[:k].cpu().numpy(), pr.numpy()) < 1e-6
 
 
+def test_adam_fused_on_unaligned_views_on_nothing_and_on_every_element():
+    """dlwpcs_adam_step_fused through the C ABI: (1) p, g, m, v as views one float into their buffers with n % 4 == 0 (the scalar
+    instantiation's alignment fallback) give bitwise the result of aligned buffers (the 16-B vector instantiation) and touch
+    nothing around the views; (2) n = 0 only increments the step; (3) n = 300001 against the oracle over ALL elements"""
+    from DLWP import _native as nat
+    lib = nat.lib()
+    rng = np.random.default_rng(53)
+    hyper = (1e-3, 0.9, 0.999, 1e-7, 0.5)
+    h32 = [float(np.float32(h)) for h in hyper]           # what the kernel is given: 1 - beta2 differs from 0.001 by 5e-5 of it in fp32
+    SENT = -4.3e8
+
+    def step(p, g, m, v, n, state, flags=0):
+        nat.check(lib.dlwpcs_adam_step_fused(nat.ptr(p), nat.ptr(g), nat.ptr(m), nat.ptr(v), n, nat.ptr(state), *hyper, flags,
+                                             nat.stream_ptr()), 'adam_step_fused')
+        torch.cuda.synchronize()
+
+    n = 4 * 1001
+    host = [rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32),
+            (0.1 * rng.standard_normal(n)).astype(np.float32), (0.01 * rng.random(n)).astype(np.float32)]
+    al = [to_dev(a) for a in host]
+    bufs = [torch.full((n + 8,), SENT, dtype=torch.float32, device=_dev()) for _ in host]
+    views = [b[1:1 + n] for b in bufs]
+    for vw, a in zip(views, al):
+        vw.copy_(a)
+        assert vw.data_ptr() % 16 == 4
+    sa = torch.tensor([6, 0], dtype=torch.int32, device=_dev())
+    sb = sa.clone()
+    step(*al, n, sa)
+    step(*views, n, sb, nat.ADAM_ZERO_GRAD)
+    assert sa.tolist() == [7, 0] and sb.tolist() == [7, 0]
+    for k in (0, 2, 3):
+        assert torch.equal(views[k], al[k]) and not torch.equal(al[k], to_dev(host[k]))
+    assert torch.equal(al[1], to_dev(host[1])) and float(views[1].abs().max()) == 0.0          # g: kept / cleared
+    for b in bufs:
+        assert float(b[0]) == SENT and bool((b[1 + n:] == SENT).all())
+    # (2) nothing to update: the step moves on, nothing else does
+    before = [b.clone() for b in bufs]
+    step(*views, 0, sb)
+    assert sb.tolist() == [8, 0] and all(torch.equal(b, c) for b, c in zip(bufs, before))
+    s1 = torch.tensor([3], dtype=torch.int32, device=_dev())
+    nat.check(lib.dlwpcs_adam_step(nat.ptr(views[0]), nat.ptr(views[1]), nat.ptr(views[2]), nat.ptr(views[3]), 0, nat.ptr(s1),
+                                   *hyper, nat.stream_ptr()), 'adam_step')
+    torch.cuda.synchronize()
+    assert s1.item() == 4 and all(torch.equal(b, c) for b, c in zip(bufs, before))
+    # (3) every element against the oracle
+    n = 300001
+    p0 = rng.standard_normal(n).astype(np.float32)
+    p, m, v = to_dev(p0), torch.zeros(n, device=_dev()), torch.zeros(n, device=_dev())
+    state = torch.zeros(2, dtype=torch.int32, device=_dev())
+    pr = torch.tensor(p0, dtype=torch.float64)
+    mr, vr = torch.zeros_like(pr), torch.zeros_like(pr)
+    for it in range(4):
+        g = rng.standard_normal(n).astype(np.float32)
+        step(p, to_dev(g), m, v, n, state)
+        orc.adam_step(pr, torch.tensor(0.5 * g.astype(np.float64)), mr, vr, it + 1, lr=h32[0], b1=h32[1], b2=h32[2], eps=h32[3])
+    assert state.tolist() == [4, 0]
+    assert rel_err(p.cpu().numpy(), pr.numpy()) < 1e-6
+    assert rel_err(m.cpu().numpy(), mr.numpy()) < 1e-6 and rel_err(v.cpu().numpy(), vr.numpy()) < 1e-6
+
+
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 def test_avgpool_skip_backward_is_one_pass(dtype):
     """ops.avgpool2_skip: (pooled, alias); gradient = d_alias + avgpool2_bwd(d_pooled) in one kernel, equal to the two

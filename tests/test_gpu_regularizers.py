@@ -69,6 +69,59 @@ def test_constraints_match_keras_formulas(shape, axis):
         constraints.MaxNorm(1.0, axis=2).apply(torch.zeros(shape, device=_dev())) if len(shape) > 2 else (_ for _ in ()).throw(NotImplementedError())
 
 
+@pytest.mark.parametrize('n', [7, 1025])
+def test_l1l2_with_a_null_output(n):
+    """penalty only (g = NULL), gradient only (penalty = NULL); 1025 = one element past the workgroup's 1024 lanes"""
+    from DLWP import _native as nat
+    rng = np.random.default_rng(n + 1)
+    w = rng.standard_normal(n).astype(np.float32)
+    w[::5] = 0.0
+    g0 = rng.standard_normal(n).astype(np.float32)
+    l1, l2 = 0.003, 0.004
+    w64 = w.astype(np.float64)
+    wd = torch.tensor(w, device=_dev())
+    pen = torch.full((3,), 0.5, dtype=torch.float32, device=_dev())
+    nat.check(nat.lib().dlwpcs_l1l2_regularize(nat.ptr(wd), 0, n, l1, l2, 2.0, nat.ptr(pen[1:]), nat.stream_ptr()), 'l1l2')
+    torch.cuda.synchronize()
+    ref_pen = 0.5 + l1 * np.abs(w64).sum() + l2 * (w64 ** 2).sum()
+    assert abs(float(pen[1]) - ref_pen) <= 1e-5 * abs(ref_pen) and float(pen[0]) == 0.5 and float(pen[2]) == 0.5
+    gd = torch.tensor(np.concatenate([[9.0], g0, [9.0]]).astype(np.float32), device=_dev())
+    nat.check(nat.lib().dlwpcs_l1l2_regularize(nat.ptr(wd), nat.ptr(gd[1:]), n, l1, l2, 2.0, 0, nat.stream_ptr()), 'l1l2')
+    torch.cuda.synchronize()
+    got = gd.cpu().numpy()
+    np.testing.assert_allclose(got[1:-1], g0 + 2.0 * (l1 * np.sign(w64) + 2.0 * l2 * w64), rtol=1e-6, atol=1e-7)
+    assert got[0] == 9.0 and got[-1] == 9.0 and np.array_equal(wd.cpu().numpy(), w)
+
+
+_KINDS = (('max_norm', 1, 2.0, 0.0, 1.0), ('non_neg', 2, 0.0, 0.0, 1.0), ('unit_norm', 3, 0.0, 0.0, 1.0),
+          ('min_max', 4, 0.5, 1.5, 0.7))
+
+
+@pytest.mark.parametrize('rows', [1, 255, 257])
+@pytest.mark.parametrize('cols', [1, 3])
+@pytest.mark.parametrize('kind,tag,a,b,rate', _KINDS)
+def test_constraints_at_the_lane_boundary_and_on_a_zero_column(rows, cols, kind, tag, a, b, rate):
+    """one workgroup of 256 lanes per column: rows below, at and past it; a column of zeros comes out as zeros, never NaN;
+    MinMaxNorm(rate = 0.7) pulls a column below min_value up"""
+    from DLWP import _native as nat
+    rng = np.random.default_rng(rows * 10 + cols)
+    w = (rng.standard_normal((rows, cols)) * 1.5).astype(np.float32)
+    w[:, 0] *= np.float32(0.3 / np.sqrt((w[:, 0].astype(np.float64) ** 2).sum()))     # norm 0.3: below min_value = 0.5
+    if cols > 1:
+        w[:, 1] = 0.0
+    wd = torch.tensor(w, device=_dev())
+    nat.check(nat.lib().dlwpcs_weight_constraint(nat.ptr(wd), rows, cols, tag, a, b, rate, nat.stream_ptr()), 'weight_constraint')
+    torch.cuda.synchronize()
+    got = wd.cpu().numpy()
+    assert np.isfinite(got).all()
+    np.testing.assert_allclose(got, _constraint_ref(w, kind, a, b, rate, rows), rtol=2e-6, atol=1e-7)
+    if cols > 1:
+        assert np.all(got[:, 1] == 0.0)
+    if kind == 'min_max':
+        norm = np.sqrt((got[:, 0].astype(np.float64) ** 2).sum())
+        assert abs(norm - (0.7 * 0.5 + 0.3 * 0.3)) <= 1e-5                           # rate * min_value + (1 - rate) * norm
+
+
 def test_layer_trains_with_regularizer_and_constraint():
     """one Adam step of pad + CubeSphereConv2D(kernel_regularizer=l2, kernel_constraint=MaxNorm): the reported loss is mse + penalty,
     the update moves against mse-gradient + penalty-gradient (checked through the first Adam step: -lr * sign(total gradient)), and the
