@@ -243,6 +243,15 @@ PROTOTYPES = {
     'dlwpcs_channel_moments': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
                                        c_void_p]),
     'dlwpcs_channel_affine': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'dlwpcs_channel_range_scratch_bytes': (c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    'dlwpcs_channel_range': (c_int, [c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
+    'dlwpcs_pack_i16': (c_int, [c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_unpack_i16': (c_int, [c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
+    'dlwpcs_batch_gather_i16': (c_int, [c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                        c_void_p]),
     'dlwpcs_comm_load': (c_int, [ctypes.c_char_p]),
     'dlwpcs_comm_unique_id': (c_int, [c_void_p]),
     'dlwpcs_comm_init': (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int]),

@@ -7,4 +7,5 @@ and transforms are built).
 from .models import DLWPFunctional                                  # noqa: F401
 from .generators import ArrayDataGenerator, tf_data_generator      # noqa: F401
 from .extensions import TimeSeriesEstimator                          # noqa: F401
+from .packing import PackedSeries                                    # noqa: F401
 from .preprocessing import VariableScaler, mean_by_batch, std_by_batch, variable_statistics   # noqa: F401

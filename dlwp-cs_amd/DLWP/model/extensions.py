@@ -18,6 +18,7 @@ Not built (raises NotImplementedError): imputation, generators whose inputs are 
 import numpy as np
 
 from .models import DLWPFunctional
+from .packing import PackedSeries
 
 
 class Forecast(object):
@@ -253,7 +254,7 @@ class TimeSeriesEstimator(object):
         (keep_time_dim=False layout); the value at (f_hour, time) is the generator's array at the row of time + f_hour (its
         output variables, channels_last), NaN where that row lies outside the data.  `.lat` is the latitude (dims x0, x1, x2)
         when the estimator knows it.  keep_on_device: fp32 device values; with a device-resident generator the gather reads
-        HBM only (one dlwpcs_batch_gather launch).
+        HBM only (one dlwpcs_batch_gather launch; dlwpcs_batch_gather_i16 over a DLWP.model.PackedSeries).
         """
         if int(steps) < 1:
             raise ValueError('must use positive integer for steps')
@@ -304,6 +305,8 @@ class TimeSeriesEstimator(object):
         (DLWP.verify.daily_climatology of the array's rows at `sample_times`).  samples: restrict to these rows of the array.
         keep_on_device: fp32 device values; with a device-resident generator the channels-first array is reduced in HBM
         straight into the channels-last result (dlwpcs_group_mean), nothing is copied or uploaded but the row grouping.
+        A generator over a DLWP.model.PackedSeries: the output variables are first decoded into an fp32 temporary of
+        (rows, output variables, *space) -- beside the codes in HBM with a device-resident generator -- and that is reduced.
         """
         from ..verify import _climatology
         g = self.generator
@@ -317,7 +320,11 @@ class TimeSeriesEstimator(object):
         dev_data = getattr(g, '_dev', None)
         arr = dev_data['array'] if keep_on_device and dev_data is not None else g.array
         step = int(vout[1] - vout[0]) if len(vout) > 1 else 1
-        if len(vout) and step > 0 and np.array_equal(vout, vout[0] + step * np.arange(len(vout))):
+        if isinstance(arr, PackedSeries):
+            arr = arr.unpack(variables=vout)                    # codes are not values: the fp32 temporary of the docstring
+            if not keep_on_device and not isinstance(arr, np.ndarray):
+                arr = arr.cpu().numpy()
+        elif len(vout) and step > 0 and np.array_equal(vout, vout[0] + step * np.arange(len(vout))):
             arr = arr[:, int(vout[0]):int(vout[-1]) + 1:step]   # a view: the output variables are evenly spaced
         elif hasattr(arr, 'index_select'):
             arr = arr.index_select(1, dev_data['vout'].long())

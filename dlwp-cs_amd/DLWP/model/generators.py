@@ -20,11 +20,13 @@ Two execution paths behind the same API:
     6-hourly C48 ERA5 set of 7 variables is 22 GB of the 288 GB) and `generate()` returns device tensors assembled by one
     gather kernel per tensor (`dlwpcs_batch_gather`: fancy-index + time-major channel packing + channels_last transpose +
     optional bf16 rounding in one pass) -- no host work, no PCIe traffic per batch.  `DLWPFunctional.fit_generator`
-    accepts either kind.
+    accepts either kind.  An `array` given as a `DLWP.model.PackedSeries` stays in HBM as int16 codes, half the bytes, and
+    the gathers decode it on the way (`dlwpcs_batch_gather_i16`).
 """
 import numpy as np
 
 from ..util import SolarForcing, to_bool
+from .packing import PackedSeries
 
 
 def delete_nan_samples(predictors, targets, large_fill_value=False, threshold=None):
@@ -67,7 +69,9 @@ class ArrayDataGenerator(object):
                  drop_remainder=False, device=None, dtype=None):
         """
         :param model: DLWP model instance (metadata only: is_convolutional, is_recurrent, impute)
-        :param array: ndarray (time, variable, *space)
+        :param array: ndarray (time, variable, *space), or a DLWP.model.PackedSeries of that shape: the series as int16
+            codes, half the bytes; with `device` the codes are what is uploaded and `dlwpcs_batch_gather_i16` decodes them
+            into each batch, on the host its rows are decoded as they are indexed (the same bits either way)
         :param rank: number of spatial dimensions (3 for cubed-sphere data: face, height, width)
         :param device: None for host numpy batches, or a torch device / True to keep the data in HBM and assemble
             batches with the gather kernel (convolutional, non-recurrent models)
@@ -313,11 +317,14 @@ class ArrayDataGenerator(object):
         dev = backend.device() if device is True else torch.device(device)
         self.device = dev
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)   # noqa: E731
-        d = {'array': up(self.array), 'vin': torch.from_numpy(self._input_vars.astype(np.int32)).to(dev),
+        # a PackedSeries goes up as the int16 codes it holds (plus its two small tables) and the gathers decode: no fp32 copy
+        packed = isinstance(self.array, PackedSeries)
+        d = {'array': self.array.to_device(dev) if packed else up(self.array),
+             'vin': torch.from_numpy(self._input_vars.astype(np.int32)).to(dev),
              'vout': torch.from_numpy(self._output_vars.astype(np.int32)).to(dev),
              'zero': torch.zeros(1, dtype=torch.int32, device=dev), 'ops': ops, 'torch': torch,
              'pdtype': backend.torch_dtype(dtype)}
-        if self._remove_nan and bool(torch.isnan(d['array']).any().item()):
+        if self._remove_nan and (d['array'].has_fill() if packed else bool(torch.isnan(d['array']).any().item())):
             raise NotImplementedError('remove_nan with NaNs present: use the host path (device=None)')
         if self._add_insolation and isinstance(self.insolation_array, SolarForcing):
             # described, not stored: two small tables, every value is computed where it is written (dlwpcs_solar_fill)

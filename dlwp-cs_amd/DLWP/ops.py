@@ -1511,8 +1511,12 @@ def batch_gather(array, samples, var_idx, out, n_steps, t_off, t_stride, c_off, 
     """
     array (T, V, *space) fp32 device tensor; samples (B,) / var_idx (nv,) int32 device tensors; out (B, *space, Ctot) or
     (B, Ctot, *space), float32 or bfloat16, written in place: channel c_off + n*c_stride + j <- array[samples + t_off +
-    n*t_stride, var_idx[j]].
+    n*t_stride, var_idx[j]].  `array` may also be a packed device source -- an object with `q` (T, V, *space) int16, `scale`
+    and `offset` (V,) float32 device tensors, such as a device-resident DLWP.model.PackedSeries: the same gather out of the
+    codes, decoded on the way (dlwpcs_batch_gather_i16).
     """
+    if not isinstance(array, torch.Tensor) and hasattr(array, 'q'):
+        return _batch_gather_i16(array, samples, var_idx, out, n_steps, t_off, t_stride, c_off, c_stride, channels_last)
     for t in (array, out):
         require_device(t, 'batch_gather')
     if array.dtype != torch.float32 or not array.is_contiguous() or not out.is_contiguous():
@@ -1526,6 +1530,106 @@ def batch_gather(array, samples, var_idx, out, n_steps, t_off, t_stride, c_off, 
     check(lib().dlwpcs_batch_gather(ptr(array), T, V, S, ptr(samples), B, ptr(var_idx), int(var_idx.numel()),
                                     int(n_steps), int(t_off), int(t_stride), ptr(out), Ctot, int(c_off), int(c_stride),
                                     1 if channels_last else 0, nat.dtype_tag(out), stream_ptr()), 'dlwpcs_batch_gather')
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
+# The resident series as int16 codes (DLWP/model/packing.py): x = q * scale[v] + offset[v], -32768 = NaN; include/dlwpcs.h
+# ------------------------------------------------------------------------------------------------------------------ #
+
+def _packed_tables(scale, offset, V, dev, what):
+    for t, name in ((scale, 'scale'), (offset, 'offset')):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or \
+                t.numel() != V:
+            raise TypeError('%s: %s must be a contiguous float32 tensor of %d entries on %s' % (what, name, V, dev))
+
+
+def _tvs(x, what):
+    if x.dim() < 2:
+        raise ValueError('%s: expected (time, variable, *space), got shape %s' % (what, tuple(x.shape)))
+    T, V = int(x.shape[0]), int(x.shape[1])
+    return T, V, (x.numel() // (T * V) if T * V else 0)
+
+
+def _batch_gather_i16(src, samples, var_idx, out, n_steps, t_off, t_stride, c_off, c_stride, channels_last):
+    q = src.q
+    require_device(out, 'batch_gather')
+    if not isinstance(q, torch.Tensor) or q.dtype != torch.int16 or q.device != out.device:
+        raise nat.NativeError('batch_gather: a packed source holds its int16 codes on the device of `out` (no CPU fallback)')
+    if not q.is_contiguous() or not out.is_contiguous():
+        raise TypeError('batch_gather: codes and out must be contiguous')
+    T, V, S = _tvs(q, 'batch_gather')
+    _packed_tables(src.scale, src.offset, V, q.device, 'batch_gather')
+    B = int(samples.numel())
+    Ctot = int(out.shape[-1] if channels_last else out.shape[1])
+    if out.numel() != B * S * Ctot:
+        raise ValueError('batch_gather: out shape %s does not match batch %d, space %d' % (tuple(out.shape), B, S))
+    check(lib().dlwpcs_batch_gather_i16(ptr(q), T, V, S, ptr(src.scale), ptr(src.offset), ptr(samples), B, ptr(var_idx),
+                                        int(var_idx.numel()), int(n_steps), int(t_off), int(t_stride), ptr(out), Ctot, int(c_off),
+                                        int(c_stride), 1 if channels_last else 0, nat.dtype_tag(out), stream_ptr()),
+          'dlwpcs_batch_gather_i16')
+    return out
+
+
+def channel_range(x):
+    """
+    (range, nonfinite) of the contiguous fp32 device tensor x (T, V, *space): range (V, 2) float32 = {min, max} over the finite
+    elements of every variable ({+inf, -inf} when there are none), nonfinite (V,) int64 = the count of NaN / inf elements.
+    Device tensors; two launches on the current stream, no host synchronisation.
+    """
+    require_device(x, 'channel_range')
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError('channel_range: x must be contiguous float32')
+    T, V, S = _tvs(x, 'channel_range')
+    dev = x.device
+    with torch.cuda.device(dev):
+        rng = torch.empty((V, 2), dtype=torch.float32, device=dev)
+        bad = torch.empty((V,), dtype=torch.int64, device=dev)
+        nbytes = int(lib().dlwpcs_channel_range_scratch_bytes(T, V, S))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        check(lib().dlwpcs_channel_range(ptr(x), T, V, S, ptr(rng), ptr(bad), ptr(scratch), nbytes, stream_ptr()),
+              'dlwpcs_channel_range')
+    return rng, bad
+
+
+def pack_i16(x, scale, offset, out=None):
+    """
+    int16 codes of the contiguous fp32 device tensor x (T, V, *space): clamp(rint((x - offset[v]) / scale[v]), -32767, 32767),
+    -32768 for NaN / inf.  scale, offset: (V,) float32 device tensors.  One launch.
+    """
+    require_device(x, 'pack_i16')
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError('pack_i16: x must be contiguous float32')
+    T, V, S = _tvs(x, 'pack_i16')
+    _packed_tables(scale, offset, V, x.device, 'pack_i16')
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.int16, device=x.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.int16 or out.device != x.device or out.shape != x.shape or \
+            not out.is_contiguous():
+        raise ValueError('pack_i16: out must be a contiguous int16 tensor of shape %s on %s' % (tuple(x.shape), x.device))
+    with torch.cuda.device(x.device):
+        check(lib().dlwpcs_pack_i16(ptr(x), T, V, S, ptr(scale), ptr(offset), ptr(out), stream_ptr()), 'dlwpcs_pack_i16')
+    return out
+
+
+def unpack_i16(q, scale, offset, out=None):
+    """
+    fp32 values of the contiguous int16 device tensor q (T, V, *space): float(q) * scale[v] + offset[v] as two rounded fp32
+    operations, NaN for -32768.  scale, offset: (V,) float32 device tensors.  One launch.
+    """
+    if not isinstance(q, torch.Tensor) or not q.is_cuda:
+        raise nat.NativeError('unpack_i16: the codes must be a tensor on a HIP device (no CPU fallback)')
+    if q.dtype != torch.int16 or not q.is_contiguous():
+        raise TypeError('unpack_i16: q must be contiguous int16')
+    T, V, S = _tvs(q, 'unpack_i16')
+    _packed_tables(scale, offset, V, q.device, 'unpack_i16')
+    if out is None:
+        out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != q.device or out.shape != q.shape or \
+            not out.is_contiguous():
+        raise ValueError('unpack_i16: out must be a contiguous float32 tensor of shape %s on %s' % (tuple(q.shape), q.device))
+    with torch.cuda.device(q.device):
+        check(lib().dlwpcs_unpack_i16(ptr(q), T, V, S, ptr(scale), ptr(offset), ptr(out), stream_ptr()), 'dlwpcs_unpack_i16')
     return out
 
 

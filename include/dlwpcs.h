@@ -739,6 +739,49 @@ int dlwpcs_channel_affine(const dlwpcs_chan_desc *d, const float *src, const flo
                           dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * The resident series in 16-bit packed form (the CF / netCDF convention, the one ERA5 is distributed in):
+ *   x = q * scale[v] + offset[v]
+ * with q an int16 code in [-32767, 32767], code -32768 = missing (decodes to NaN), scale and offset fp32 device tables of V
+ * entries, scale != 0 (it may be negative).  All arrays are contiguous (T, V, S).  Every arithmetic step below is ONE rounded
+ * fp32 operation, never an fma, so numpy's float32 arithmetic gives the same bits.
+ *
+ * dlwpcs_channel_range: range[v] = {min, max} (float[V][2]) over the FINITE elements of variable v, {+inf, -inf} when it has
+ * none; nonfinite[v] (int64[V]) = the number of NaN / +-inf elements.  Exact: neither depends on the order.  Two launches
+ * (per-workgroup partials in scratch, then one workgroup per variable); scratch >= dlwpcs_channel_range_scratch_bytes(T, V, S),
+ * 8-byte aligned.  16-byte loads when S % 4 == 0 and src is 16-byte aligned, one element per lane otherwise.  T == 0 or S == 0
+ * writes the empty range; V == 0 returns DLWPCS_OK without a launch.
+ *
+ * dlwpcs_pack_i16: dst = clamp(rint((src - offset[v]) / scale[v]), -32767, 32767): subtract, IEEE divide, round half to even,
+ * clamp; a NaN or +-inf source element gives -32768.
+ * dlwpcs_unpack_i16: dst = float(src) * scale[v], then + offset[v]; -32768 gives NaN (0x7fc00000).
+ * Both: one launch; a lane moves 8 elements with 16-byte accesses when S % 8 == 0 and both pointers are 16-byte aligned, single
+ * elements otherwise.  A zero extent returns DLWPCS_OK without a launch.
+ *
+ * dlwpcs_batch_gather_i16: the decoding twin of dlwpcs_batch_gather -- same arguments, output addressing, limits and error codes --
+ * out of an int16 array:
+ *   channels_last : out[b][s][c_off + n*c_stride + j] = decode(array[samples[b] + t_off + n*t_stride][var_idx[j]][s])
+ *   channels_first: out[b][c_off + n*c_stride + j][s] = (same)
+ * decode(q) = float(q) * scale[var_idx[j]] + offset[var_idx[j]] as above, the fp32 value then stored as `dtype`: a bf16 output
+ * is the round-to-nearest-even of the fp32 output (the NaN of a fill code: 0x7fc0).  Three forms.  channels_last, the gathered channels being the whole output row
+ * (c_off == 0, c_stride == nv, Ctot == n_steps * nv), S % 8 == 0, array and out 16-byte aligned, n_steps * nv * 257 floats of LDS
+ * <= 64 KiB: 256 pixels x all channels per workgroup, a lane loads 16 bytes = 8 codes, the output is written as 16-byte vectors.
+ * Any other channels_last call (any S, a channel window inside a wider row, an unaligned pointer): 64 pixels x all channels
+ * through a padded LDS tile, one code per lane.  channels_first: rows copied along s, 8 codes per lane when S % 8 == 0 and both
+ * pointers are 16-byte aligned, one otherwise.  The samples are TRUSTED, as in dlwpcs_batch_gather.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t dlwpcs_channel_range_scratch_bytes(int64_t T, int64_t V, int64_t S);
+int dlwpcs_channel_range(const float *src, int64_t T, int64_t V, int64_t S, float *range, int64_t *nonfinite, void *scratch,
+                         size_t scratch_bytes, dlwpcs_stream_t stream);
+int dlwpcs_pack_i16(const float *src, int64_t T, int64_t V, int64_t S, const float *scale, const float *offset, int16_t *dst,
+                    dlwpcs_stream_t stream);
+int dlwpcs_unpack_i16(const int16_t *src, int64_t T, int64_t V, int64_t S, const float *scale, const float *offset, float *dst,
+                      dlwpcs_stream_t stream);
+int dlwpcs_batch_gather_i16(const int16_t *array, int64_t T, int V, int64_t S, const float *scale, const float *offset,
+                            const int32_t *samples_dev, int B, const int32_t *var_idx_dev, int nv, int n_steps, int t_off,
+                            int t_stride, void *out, int Ctot, int c_off, int c_stride, int channels_last, int dtype,
+                            dlwpcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Data-parallel exchange: ONE in-place sum of the flat fp32 gradient buffer over the ranks, through an RCCL
  * communicator the caller owns, enqueued on the CALLER's stream -- inside a captured training step the collective is a plain
  * node of the step's graph between dlwpcs_wgrad_batch (reduction into the buffer) and dlwpcs_wgrad_batch_apply.
