@@ -113,6 +113,12 @@ class OverlapDesc(ctypes.Structure):
                 ('frames', ((ctypes.c_double * 3) * 3) * 6), ('dust', ctypes.c_double)]
 
 
+class CubeBilinearDesc(ctypes.Structure):
+    """struct dlwpcs_cube_bilinear_desc (include/dlwpcs.h)"""
+    _fields_ = [('N', ctypes.c_int32), ('reserved', ctypes.c_int32), ('n_points', ctypes.c_int64),
+                ('frames', ((ctypes.c_double * 3) * 3) * 6), ('edge', ((ctypes.c_int32 * 3) * 4) * 6)]
+
+
 class SparseMapDesc(ctypes.Structure):
     """struct dlwpcs_sparse_map_desc (include/dlwpcs.h)"""
     _fields_ = [('n_a', ctypes.c_int64), ('n_b', ctypes.c_int64), ('nnz', ctypes.c_int64), ('x_dtype', ctypes.c_int32),
@@ -219,6 +225,7 @@ PROTOTYPES = {
     'dlwpcs_sparse_map_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_count': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_fill': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p]),
+    'dlwpcs_cube_bilinear': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_adam_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,
                                  c_float, c_float, c_float, c_void_p]),
     'dlwpcs_adam_step_fused': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_float, c_float,

@@ -2023,6 +2023,49 @@ def overlap_areas(cube, ll, dust, device):
 
 
 # ------------------------------------------------------------------------------------------------------------------ #
+# Bilinear sampling of the cube at points (DLWP/remap/bilinear.py): include/dlwpcs.h dlwpcs_cube_bilinear_desc
+# ------------------------------------------------------------------------------------------------------------------ #
+
+def cube_bilinear(cube, lat, lon, device):
+    """
+    The cells and weights that sample a field on a DLWP.remap CubeSphereGrid at the points (lat, lon) in degrees, as device
+    tensors (col int32 (n, 4), w float64 (n, 4)): one dlwpcs_cube_bilinear launch on the current stream of `device`.  lat / lon
+    that are tensors on that device are read where they lie; anything else is checked on the host and uploaded.  ValueError
+    for non-finite input or |lat| > 90, before the launch (tensors on the device are checked there: one read-back).
+    """
+    from .remap.bilinear import _checked_points, cube_edges
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise nat.NativeError('cube_bilinear: %s is not a HIP device (device=None runs the host twin)' % dev)
+    with torch.cuda.device(dev):
+        dev = torch.device('cuda', torch.cuda.current_device())
+        if all(isinstance(x, torch.Tensor) and x.device == dev for x in (lat, lon)):
+            if lat.shape != lon.shape:
+                raise ValueError('lat and lon must have one shape, got %s and %s' % (tuple(lat.shape), tuple(lon.shape)))
+            la, lo = (x.detach().to(torch.float64).reshape(-1).contiguous() for x in (lat, lon))
+            if la.numel():
+                ok = torch.stack([torch.isfinite(la).all() & torch.isfinite(lo).all(), (la.abs() <= 90.).all()]).tolist()
+                if not ok[0]:
+                    raise ValueError('lat and lon must be finite')
+                if not ok[1]:
+                    raise ValueError('latitudes must lie within [-90, 90]')
+        else:
+            la, lo = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (lat, lon))
+            la, lo = (torch.from_numpy(np.array(x, dtype=np.float64)).to(dev) for x in _checked_points(la, lo))
+        n = int(la.numel())
+        d = nat.CubeBilinearDesc()
+        d.N, d.n_points = int(cube.N), n
+        fr = np.ascontiguousarray(cube.frames, dtype=np.float64)
+        ctypes.memmove(ctypes.addressof(d.frames), fr.ctypes.data, fr.nbytes)
+        ed = np.ascontiguousarray(cube_edges(), dtype=np.int32)
+        ctypes.memmove(ctypes.addressof(d.edge), ed.ctypes.data, ed.nbytes)
+        col = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        w = torch.empty((n, 4), dtype=torch.float64, device=dev)
+        check(lib().dlwpcs_cube_bilinear(ctypes.byref(d), ptr(la), ptr(lo), ptr(col), ptr(w), stream_ptr()), 'dlwpcs_cube_bilinear')
+    return col, w
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
 # Per-variable scaling (DLWP/model/preprocessing.py): channel moments and the channel affine, include/dlwpcs.h dlwpcs_chan_desc
 # ------------------------------------------------------------------------------------------------------------------ #
 

@@ -3,7 +3,8 @@ Remapping between the cubed sphere and a lat-lon grid with existing offline maps
 
 The reference drives TempestRemap's executables on netCDF files.  Here the maps are read once (DLWP.remap.read_offline_map)
 and applied to arrays: device tensors by the dlwpcs_sparse_map_apply kernel where they lie, numpy arrays on the host.  Maps
-that do not exist yet are made by `generate_maps` (closed-form conservative maps, DLWP.remap.overlap).  The file-to-file
+that do not exist yet are made by `generate_maps` (closed-form conservative maps, DLWP.remap.overlap).  Smooth output on a fine
+lat-lon grid and values at a list of points come from `generate_sampling_map` (bilinear, DLWP.remap.bilinear).  The file-to-file
 methods need TempestRemap or xarray, which this stack does not have; they raise NotImplementedError.
 """
 import os
@@ -13,10 +14,23 @@ from ..model.extensions import Forecast
 from .grid import CubeSphereGrid, LatLonGrid
 from .offline_map import OfflineMap, read_offline_map, write_offline_map
 from .overlap import conservative_maps
+from .bilinear import bilinear_map
 
 _CUBE_DIMS = (('x0', 'x1', 'x2'), ('face', 'height', 'width'))
 _FILE_MSG = ('CubeSphereRemap.%s needs the TempestRemap executables or xarray, which this engine does not use; apply an '
              'existing offline map to arrays with remap_array / inverse_remap_array / inverse_remap_forecast instead')
+
+
+def _cube_axis(dims):
+    """first of the three consecutive cube dims of a labelled forecast"""
+    dims, a0 = tuple(dims), None
+    for names in _CUBE_DIMS:
+        for i in range(len(dims) - 2):
+            if dims[i:i + 3] == names:
+                a0 = i
+    if a0 is None:
+        raise ValueError("forecast dims %s have none of ('x0', 'x1', 'x2') / ('face', 'height', 'width')" % (dims,))
+    return a0
 
 
 class CubeSphereRemap(object):
@@ -43,6 +57,7 @@ class CubeSphereRemap(object):
         self._loaded = {}
         self.cube_grid = None
         self.latlon_grid = None
+        self.sampling_map = None
 
     def generate_maps(self, lat=None, lon=None, res=None, inverse_lat=False, lon_begin=0., *, grid=None, latlon=None,
                       device=None, map_name=None, inverse_map_name=None):
@@ -160,6 +175,71 @@ class CubeSphereRemap(object):
         out = Forecast(vals, new_dims, coords, name=forecast.name)
         out.lat = Forecast(coords['lat'], ('lat',), {'lat': coords['lat']}, name='lat')
         out.lon = Forecast(coords['lon'], ('lon',), {'lon': coords['lon']}, name='lon')
+        return out
+
+    # ---------------------------------------------------------------------------------------------------------------- #
+    # bilinear sampling of the cube: smooth lat-lon output, values at points
+    def generate_sampling_map(self, lat=None, lon=None, *, latlon=None, grid=None, res=None, device=None, map_name=None):
+        """
+        Make the bilinear sampling map from the cube (DLWP.remap.bilinear: continuous across face edges and corners) and keep
+        it as `.sampling_map` for sample_array / sample_forecast.  The conservative maps are not touched.
+
+        :param lat, lon: arrays of one shape: the points to sample at, in degrees (any finite longitude)
+        :param latlon: LatLonGrid in place of the points: its cell centres are sampled and the result has (lat, lon) axes
+        :param grid: CubeSphereGrid; or `res`: cells on a side of each cube face; default: the grid of generate_maps
+        :param device: a HIP device: the weights are computed by the dlwpcs_cube_bilinear kernel; None: on the host
+        :param map_name: str: also write the map to this file (64-bit-offset netCDF, SCRIP layout)
+        :return: OfflineMap
+        """
+        if grid is None:
+            if res is not None:
+                grid = CubeSphereGrid(int(res))
+            elif self.cube_grid is not None:
+                grid = self.cube_grid
+            else:
+                raise ValueError('generate_sampling_map needs res, or grid=')
+        elif not isinstance(grid, CubeSphereGrid):
+            raise TypeError('grid must be a DLWP.remap.CubeSphereGrid')
+        if latlon is not None and not isinstance(latlon, LatLonGrid):
+            raise TypeError('latlon must be a DLWP.remap.LatLonGrid')
+        m = bilinear_map(grid, lat, lon, latlon=latlon, device=device)
+        m.name = ('sample_CS%d_LL%dx%d' % (grid.N, latlon.n_lat, latlon.n_lon) if latlon is not None
+                  else 'sample_CS%d_P%d' % (grid.N, m.n_b))
+        if map_name is not None:
+            write_offline_map(m, map_name)
+        self.sampling_map = m
+        return m
+
+    def _sampling(self):
+        if self.sampling_map is None:
+            raise ValueError("No sampling map has been defined; use the 'generate_sampling_map' function first")
+        return self.sampling_map
+
+    def sample_array(self, x, axes=(-3, -2, -1)):
+        """
+        Sample the cubed sphere with the sampling map: the (face, height, width) axes of x are replaced by (n,) for a point
+        list or (lat, lon) for a lat-lon grid.  numpy input: host path, the input's float dtype.  HIP tensor (fp32 or bf16):
+        fp32 device result, one launch.
+        """
+        return self._sampling().apply(x, axes)
+
+    def sample_forecast(self, forecast):
+        """
+        Sample a labelled cubed-sphere forecast (space dims as for inverse_remap_forecast).  A lat-lon sampling map gives what
+        inverse_remap_forecast gives, smooth; a point list gives the dim 'point' with the coords 'lat' and 'lon' along it
+        (`.lat` / `.lon` are Forecasts of dims ('point',)).  The values stay on the device when they came from there.
+        """
+        m = self._sampling()
+        dims = tuple(forecast.dims)
+        a0 = _cube_axis(dims)
+        vals = m.apply(forecast.values, (a0, a0 + 1, a0 + 2))
+        grid = m.dst_kind == 'latlon'
+        new_dims = dims[:a0] + (('lat', 'lon') if grid else ('point',)) + dims[a0 + 3:]
+        coords = {d: c for d, c in forecast.coords.items() if d in new_dims}
+        coords['lat'], coords['lon'] = (m.lat_b.copy(), m.lon_b.copy()) if grid else (m.yc_b.copy(), m.xc_b.copy())
+        out = Forecast(vals, new_dims, coords, name=forecast.name)
+        out.lat = Forecast(coords['lat'], ('lat',) if grid else ('point',), {'lat': coords['lat']}, name='lat')
+        out.lon = Forecast(coords['lon'], ('lon',) if grid else ('point',), {'lon': coords['lon']}, name='lon')
         return out
 
     # file-to-file methods of the reference: TempestRemap executables / xarray

@@ -31,14 +31,14 @@ class _Grid(object):
     """shape of one side of a map, its kind ('cube', 'latlon' or 'cells'), 1-D lat / lon for a lat-lon grid, and the
     permutation (file cell index of each cell in `shape` order, or None) that puts a lon-major file into (lat, lon) order"""
 
-    def __init__(self, n, dims, yc, xc, side):
+    def __init__(self, n, dims, yc, xc, side, cells=False):
         self.order = None
         self.lat = self.lon = None
         dims = None if dims is None else [int(d) for d in np.ravel(dims)]
         if dims is not None and int(np.prod(dims, dtype=np.int64)) != n:
             raise ValueError('%s_grid_dims %s do not multiply to n_%s = %d' % (side, dims, 'a' if side == 'src' else 'b', n))
         if dims is None or len(dims) == 1:
-            s = _cube_side(n)
+            s = None if cells else _cube_side(n)
             self.kind, self.shape = ('cube', (6, s, s)) if s else ('cells', (n,))
         elif len(dims) == 2:
             self.kind = 'latlon'
@@ -75,13 +75,14 @@ class OfflineMap(object):
     :param yc_a, xc_a, yc_b, xc_b: cell-centre latitudes / longitudes in degrees (optional)
     :param area_a, area_b, frac_b: cell areas in steradians of the two grids and the covered fraction of every destination
         cell (optional; carried, not used by `apply`)
+    :param dst_cells: a rank-1 destination is a list of n_b cells or points ('cells') even when n_b is 6 N^2
 
     Entries are sorted stably by row into CSR (`row_ptr` int32 [n_b + 1], `col` int32 0-based, `val` fp32, `val64` fp64);
     duplicate (row, col) pairs stay separate terms, empty rows are allowed.  Raises ValueError for entries that do not fit.
     """
 
     def __init__(self, row, col, S, n_a, n_b, src_grid_dims=None, dst_grid_dims=None, yc_a=None, xc_a=None, yc_b=None,
-                 xc_b=None, name=None, area_a=None, area_b=None, frac_b=None):
+                 xc_b=None, name=None, area_a=None, area_b=None, frac_b=None, dst_cells=False):
         self.name = name
         self.n_a, self.n_b = int(n_a), int(n_b)
         if self.n_a < 0 or self.n_b < 0:
@@ -104,7 +105,7 @@ class OfflineMap(object):
         if not np.all(np.isfinite(S)):
             raise ValueError('S holds %d non-finite weights' % int((~np.isfinite(S)).sum()))
         src = _Grid(self.n_a, src_grid_dims, yc_a, xc_a, 'src')
-        dst = _Grid(self.n_b, dst_grid_dims, yc_b, xc_b, 'dst')
+        dst = _Grid(self.n_b, dst_grid_dims, yc_b, xc_b, 'dst', cells=bool(dst_cells))
         row0, col0 = row - 1, col - 1
         if src.order is not None:
             col0 = np.argsort(src.order)[col0]

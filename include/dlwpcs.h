@@ -633,6 +633,31 @@ int dlwpcs_overlap_count(const dlwpcs_overlap_desc *d, const double *sin_lat_edg
 int dlwpcs_overlap_fill(const dlwpcs_overlap_desc *d, const double *sin_lat_edges, const double *lon_edges,
                         const int64_t *row_ptr, int32_t *col, double *area, int64_t nnz, dlwpcs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------- *
+ * Bilinear sampling of a cubed-sphere field at arbitrary points (DLWP/remap/bilinear.py is the host twin and states the maths):
+ * for every point (lat, lon in degrees; any finite longitude) the four cells (f * N + i) * N + j and weights of the face of the
+ * cube's DUAL mesh that holds it.  The dual mesh has the cell centres as vertices and great-circle arcs between them as sides:
+ * per cube face the quadrilaterals of neighbouring centres, per cube edge a strip of quadrilaterals of the cells on both sides,
+ * per cube vertex the triangle of the three corner cells.  In a quadrilateral V0..V3 the weights are the bilinear factors of
+ * the (s, t) with (1-s)(1-t) V0 + s(1-t) V1 + s t V2 + (1-s) t V3 = lambda P; in a triangle the barycentric coordinates of the
+ * radial projection of P, and the fourth slot repeats the third cell with weight exactly 0.  Weights are >= 0 and sum to 1; the
+ * interpolant is continuous across cube edges and corners.  The cube is given by its face frames as in dlwpcs_overlap_desc and by
+ * its topology: per face and side (0: width index 0, 1: width N - 1, 2: height 0, 3: height N - 1) the neighbour face, the
+ * neighbour's side that is the same cube edge, and 1 when positions along the edge run the other way there.
+ * One lane per point, fp64; one launch, no host synchronisation, no allocation, no atomics; the same call gives the same bits.
+ * Every col written lies in [0, 6 N^2) whatever the inputs hold; a non-finite point gets cell 0 and NaN weights.
+ * n_points == 0: DLWPCS_OK without a launch.  N < 1, frames that are not orthonormal to 1e-9, edge entries out of range:
+ * DLWPCS_E_INVALID.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct dlwpcs_cube_bilinear_desc {
+    int32_t N, reserved;
+    int64_t n_points;
+    double frames[6][3][3];             /* [face][e0, eu, ev][x, y, z] */
+    int32_t edge[6][4][3];              /* [face][side]{neighbour face, its side, reversed} */
+} dlwpcs_cube_bilinear_desc;
+int dlwpcs_cube_bilinear(const dlwpcs_cube_bilinear_desc *d, const double *lat_deg, const double *lon_deg,
+                         int32_t *col /* [4 n_points] */, double *w /* [4 n_points] */, dlwpcs_stream_t stream);
+
 int dlwpcs_adam_step(float *p, const float *g, float *m, float *v, size_t n, int32_t *step_dev,
                      float lr, float beta1, float beta2, float eps, float grad_scale, dlwpcs_stream_t stream);
 /* Same update as one launch: `state_dev` points to TWO device int32 {t-1, 0}; the second is a ticket counter (must be 0
