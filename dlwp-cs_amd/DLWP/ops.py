@@ -641,7 +641,12 @@ class _CSConv(torch.autograd.Function):
             if ctx.defer_ring0 and dsrc0 is not None and pm0 is None and halo_ring_info(dn) is not None:
                 ring = halo_ring_info(dn)
                 dn.flags |= nat.CONV_DEFER_RING0
-                ws = _workspace(nbytes, dev, 'ring%d' % len(_pending_ring))      # stays intact until the pooling adjoint ran
+                # The ring stays intact until the pooling adjoint ran.  A node that also defers its reduction keeps the workspace
+                # of its 'defer' role, which lives until flush_deferred_reduce(): the adjoint takes its entry out of _pending_ring,
+                # so the next ring node is given the same 'ring' role again -- its launches would overwrite the partial sums a
+                # reduce item of this node still points to.
+                if not defer:
+                    ws = _workspace(nbytes, dev, 'ring%d' % len(_pending_ring))
             if dsrc0 is not None or dsrc1 is not None:
                 wq = ctx.packed[3] if ctx.packed is not None else w_eq
                 pm = pm0 if pm0 is not None else pm1

@@ -5,6 +5,10 @@ a weak out-of-bounds canary only (the caching allocator usually keeps slack mapp
 one real over-read found this round: dead gather slots of a short band indexing past the halo table -- that one showed up
 as a rare memory fault when the GPU suite was looped on fresh boxes, see conv_mfma.hip `lookup`); what it does pin is that
 no kernel depends on what lies behind or before its operands, nor on their position inside an allocation.
+
+What the kernels WRITE -- outputs, workspaces, the flat gradient buffer -- is pinned by test_gpu_hostile_mem.py: exact-size
+workspaces and output tensors, poisoned with NaN and surrounded by guard bands that are checked after every call
+(tests/hostile_mem.py).
 """
 import numpy as np
 import pytest
