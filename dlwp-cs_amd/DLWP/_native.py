@@ -20,6 +20,8 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), 'lib', 'libdlwpcs%s.so' % ('_' +
 
 F32 = 0
 BF16 = 1
+I16 = 2                                 # dlwpcs_missing_count only
+MAP_RENORMALIZE = 1
 MSE_TARGET_F32 = 0x100
 MSE_OVERWRITE = 0x200
 ADAM_ZERO_GRAD = 1
@@ -223,6 +225,9 @@ PROTOTYPES = {
                                   c_void_p, c_size_t, c_void_p]),
     'dlwpcs_rows_gather': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
+                                               c_void_p]),
+    'dlwpcs_missing_count': (c_int, [c_void_p, c_int, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p]),
     'dlwpcs_overlap_count': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_fill': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p]),
     'dlwpcs_cube_bilinear': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

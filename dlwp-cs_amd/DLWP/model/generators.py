@@ -73,6 +73,11 @@ class ArrayDataGenerator(object):
             codes, half the bytes; with `device` the codes are what is uploaded and `dlwpcs_batch_gather_i16` decodes them
             into each batch, on the host its rows are decoded as they are indexed (the same bits either way)
         :param rank: number of spatial dimensions (3 for cubed-sphere data: face, height, width)
+        :param remove_nan: drop the samples whose predictors or targets hold a NaN.  With `device`, True is served only when
+            the resident series has no missing value at all (NotImplementedError otherwise); 'device' (the host path reads it
+            as True) counts the missing values of every (time, variable) plane once (`dlwpcs_missing_count`), keeps the
+            counts as `.missing_counts` and one flag per sample as `.valid_samples`, and leaves the flagged samples out of
+            every batch before the gathers: the batches equal the host path's
         :param device: None for host numpy batches, or a torch device / True to keep the data in HBM and assemble
             batches with the gather kernel (convolutional, non-recurrent models)
         :param dtype: 'float32' | 'bfloat16' | None: dtype of the device PREDICTORS (None: the engine's compute dtype when
@@ -126,6 +131,8 @@ class ArrayDataGenerator(object):
 
         self.device = None
         self._dev = None
+        # remove_nan='device' (device path): one flag per sample and the (time, variable) missing-value counts behind them
+        self.valid_samples = self.missing_counts = None
         if device is not None and device is not False:
             self._to_device(device, dtype)
 
@@ -324,19 +331,54 @@ class ArrayDataGenerator(object):
              'vout': torch.from_numpy(self._output_vars.astype(np.int32)).to(dev),
              'zero': torch.zeros(1, dtype=torch.int32, device=dev), 'ops': ops, 'torch': torch,
              'pdtype': backend.torch_dtype(dtype)}
-        if self._remove_nan and (d['array'].has_fill() if packed else bool(torch.isnan(d['array']).any().item())):
+        if self._remove_nan == 'device':
+            # one counting pass over what is resident, (T, V) counts downloaded once, one flag per sample on the host
+            self.missing_counts = ops.missing_counts(d['array']).cpu().numpy()
+        elif self._remove_nan and (d['array'].has_fill() if packed else bool(torch.isnan(d['array']).any().item())):
             raise NotImplementedError('remove_nan with NaNs present: use the host path (device=None)')
+        sol_counts = None                       # (a computed SolarForcing has no holes)
         if self._add_insolation and isinstance(self.insolation_array, SolarForcing):
             # described, not stored: two small tables, every value is computed where it is written (dlwpcs_solar_fill)
             d['sol_row'], d['sol_cell'] = self.insolation_array.tables(dev)
         elif self._add_insolation:
             d['sol'] = up(self.insolation_array).unsqueeze(1)                      # (T, 1, *space)
+            if self._remove_nan == 'device':
+                sol_counts = ops.missing_counts(d['sol']).cpu().numpy()[:, 0]
+        if self._remove_nan == 'device':
+            self.valid_samples = self.sample_validity(self.missing_counts, sol_counts)
         if self.constants is not None:
             c = up(self.constants)                                                  # (Cc, *space)
             if self.channels_last:
                 c = c.permute(tuple(range(1, 1 + self.rank)) + (0,)).contiguous()
             d['const'] = c.to(d['pdtype'])
         self._dev = d
+
+    def sample_validity(self, counts, insolation_counts=None):
+        """
+        One boolean per sample: False where `remove_nan` drops it.  counts: (T, V) missing values per (row, variable)
+        plane of the array (ops.missing_counts / ops.missing_counts_host); insolation_counts: (T,) of a stored insolation array.
+        A sample is dropped when a row of its predictor window has a hole in an input variable or in the insolation that goes
+        into the predictors, or a row of any target window has one in an output variable: the cells `_generate_host` inspects.
+        """
+        its, iv = self._input_time_steps, self._interval
+        counts = np.asarray(counts)
+        # every window start whose rows lie in the series (the samples `_generate_device` accepts: n_sample of them when
+        # interval is 1, interval - 1 more otherwise)
+        last = max([iv * (its - 1)] + [t_off + iv * (steps - 1) for t_off, steps in self._windows()])
+        n = max(int(counts.shape[0]) - last, 0)
+        s = np.arange(n, dtype=np.int64)
+        bad_in = counts[:, self._input_vars].sum(axis=1) > 0
+        bad_out = counts[:, self._output_vars].sum(axis=1) > 0
+        if insolation_counts is not None:
+            sol = np.asarray(insolation_counts).reshape(-1)[:bad_in.size] > 0
+            bad_in[:sol.size] |= sol
+        bad = np.zeros(n, dtype=bool)
+        for k in range(its):
+            bad |= bad_in[s + k * iv]
+        for t_off, steps in self._windows():
+            for k in range(steps):
+                bad |= bad_out[s + t_off + k * iv]
+        return ~bad
 
     def _generate_device(self, samples, smp_dev=None):
         d = self._dev
@@ -358,6 +400,12 @@ class ArrayDataGenerator(object):
             if 'sol_row' in d and hi + last >= int(d['sol_row'].shape[0]):
                 raise IndexError('index %d is out of bounds for the %d rows of the solar forcing'
                                  % (hi + last, int(d['sol_row'].shape[0])))
+        if n and self.valid_samples is not None:
+            # remove_nan='device': the samples with a hole leave before the gathers, as the host path drops them after its own
+            keep = self.valid_samples[samples]
+            if not keep.all():
+                samples, smp_dev = samples[keep], None
+                n = len(samples)
         # (pinned + non_blocking: a pageable upload is a SYNCHRONOUS copy on the current stream, i.e. the host waited here for the
         # training step of the previous batch to finish before it could even enqueue this batch's gathers: generator-fed training
         # ran at 1.25 ms per step where the step itself takes 0.65 -- round 6)
@@ -374,19 +422,25 @@ class ArrayDataGenerator(object):
             return torch.empty(((n,) + lead + space + (c,)) if cl else ((n,) + lead + (c,) + space), dtype=dt,
                                device=self.device)
 
+        def gather(*args):
+            if n:                               # (every sample of the batch dropped: empty tensors, no launch)
+                ops.batch_gather(*args)
+
         def solar(rows, out, n_steps, t_stride, c_off, c_stride):
+            if not n:
+                return
             if 'sol' in d:
                 ops.batch_gather(d['sol'], rows, d['zero'], out, n_steps, 0, t_stride, c_off, c_stride, cl)
             else:
                 ops.solar_fill(d['sol_row'], d['sol_cell'], rows, out, n_steps, 0, t_stride, c_off, c_stride, cl)
         p = empty(cin, d['pdtype'])
-        ops.batch_gather(d['array'], smp, d['vin'], p, its, 0, iv, 0, vin_n + add, cl)
+        gather(d['array'], smp, d['vin'], p, its, 0, iv, 0, vin_n + add, cl)
         if add:
             solar(smp, p, its, iv, vin_n, vin_n + add)
         targets = []
         for t_off, steps in self._windows():
             t = empty(steps * self._output_size, torch.float32)
-            ops.batch_gather(d['array'], smp, d['vout'], t, steps, t_off, iv, 0, self._output_size, cl)
+            gather(d['array'], smp, d['vout'], t, steps, t_off, iv, 0, self._output_size, cl)
             targets.append(t)
         plist = [p]
         if self._sequence is not None and add:

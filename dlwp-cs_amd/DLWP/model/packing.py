@@ -225,6 +225,14 @@ class PackedSeries(object):
             return bool((self.q == FILL).any().item())
         return bool((self.q == FILL).any())
 
+    def missing_counts(self):
+        """(time, variable) int32: the number of missing-value codes of every plane -- numpy for host codes, a device tensor
+        from one dlwpcs_missing_count pass for device codes"""
+        from .. import ops
+        if _is_tensor(self.q):
+            return ops.missing_counts(self)
+        return ops.missing_counts_host(self.q)
+
     # ------------------------------------------------------------------------------------------------------------- #
     def _decode_rows(self, q, variables=None):
         """decoded fp32 of a block of code rows (n, V, *space), optionally of the listed variables only: numpy for host codes,

@@ -1638,6 +1638,43 @@ def unpack_i16(q, scale, offset, out=None):
     return out
 
 
+def missing_counts_host(array):
+    """
+    numpy twin of `missing_counts`: (T, V) int32, the number of NaN elements of every (time, variable) plane of a float array
+    (T, V, *space) -- any payload, either sign; +-inf is data -- or of -32768 codes of an int16 array.
+    """
+    a = np.asarray(array)
+    if a.ndim < 2:
+        raise ValueError('missing_counts: expected (time, variable, *space), got shape %s' % (tuple(a.shape),))
+    if a.dtype == np.int16:
+        bad = a == -32768
+    elif np.issubdtype(a.dtype, np.floating):
+        bad = np.isnan(a)
+    else:
+        raise TypeError('missing_counts: float data or int16 codes, got %s' % a.dtype)
+    return bad.reshape(a.shape[0], a.shape[1], -1).sum(axis=2, dtype=np.int64).astype(np.int32)
+
+
+def missing_counts(array):
+    """
+    (T, V) int32 device tensor: the number of missing elements of every (time, variable) plane of `array`, a contiguous fp32
+    device tensor (T, V, *space) (missing = NaN) or a packed device source with int16 codes `.q` (missing = the code -32768).
+    One dlwpcs_missing_count launch on the current stream, no host synchronisation; numpy twin: `missing_counts_host`.
+    """
+    q = getattr(array, 'q', array)
+    if not isinstance(q, torch.Tensor) or not q.is_cuda:
+        raise nat.NativeError('missing_counts: the data must be a tensor on a HIP device (no CPU fallback; missing_counts_host is '
+                              'the numpy twin)')
+    if q.dtype not in (torch.float32, torch.int16) or not q.is_contiguous():
+        raise TypeError('missing_counts: contiguous float32 data or int16 codes, got %s' % q.dtype)
+    T, V, S = _tvs(q, 'missing_counts')
+    count = torch.empty((T, V), dtype=torch.int32, device=q.device)
+    with torch.cuda.device(q.device):
+        check(lib().dlwpcs_missing_count(ptr(q), nat.I16 if q.dtype == torch.int16 else nat.F32, T * V, S, ptr(count), stream_ptr()),
+              'dlwpcs_missing_count')
+    return count
+
+
 def solar_fill(row_tab, cell_tab, samples, out, n_steps, t_off, t_stride, c_off, c_stride, channels_last=True):
     """
     The computing twin of `batch_gather(insolation[:, None], samples, [0], out, ...)`: channel c_off + n*c_stride of `out`
@@ -1917,12 +1954,20 @@ def _fold(dims):
     return out
 
 
-def sparse_map_apply(m, x, space_axes, out=None):
+def sparse_map_apply(m, x, space_axes, out=None, skipna=False, min_valid=0.5, renormalize=True, frac_out=None):
     """
     y = m applied to the source grid in the consecutive `space_axes` of the fp32 / bf16 device tensor x (DLWP.remap.OfflineMap;
     the axes hold m.src_shape, or one axis of m.n_a cells), which the result replaces with m.dst_shape.  One launch on the
     current stream, no host synchronisation.  `out`: a float32 tensor or view of the result's shape to write into (e.g. a
     permuted channels_last buffer); otherwise a new contiguous fp32 tensor is returned.
+
+    skipna=True (dlwpcs_sparse_map_apply_masked; the other keywords need it): a NaN in x is a missing value and is left out of
+    its rows' sums.  An output with holes among its entries is NaN when the weight of its present entries is below `min_valid`
+    (in [0, 1]; 0.5: the majority of the row) of the row's weight, when none is present, or when min_valid is 1; otherwise it
+    is the sum over the present entries, scaled by (row weight / present weight) with `renormalize`.  Where nothing is missing
+    the result has the bits of the plain launch.  `frac_out`: a float32 tensor or view of the result's shape that receives
+    the present share of every output's weight (1 where nothing is missing, 0 for a row without entries), or True to allocate
+    it; with it the return value is (y, frac).  The map must hold no negative weight.
 
     Views are read and written in place through their strides: after merging, the dim of smallest output stride is the inner
     dim of the descriptor (lanes span it) when x is also denser along it than along the space axis, and the other dims are up
@@ -1933,20 +1978,33 @@ def sparse_map_apply(m, x, space_axes, out=None):
     require_device(x, 'sparse_map_apply')
     if x.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError('sparse_map_apply: x must be float32 or bfloat16, got %s' % x.dtype)
+    if not skipna and frac_out is not None and frac_out is not False:
+        raise ValueError('sparse_map_apply: frac_out needs skipna=True')
+    if skipna:
+        m.check_skipna(min_valid)
     a0, a1 = m._space(tuple(x.shape), space_axes)
     dev = x.device
     row_ptr, col, val = m.to(dev)
     shape = tuple(x.shape[:a0]) + tuple(m.dst_shape) + tuple(x.shape[a1:])
     b1 = a0 + len(m.dst_shape)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
+
+    def result(t, name):
+        if t is None or t is True:
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        require_device(t, 'sparse_map_apply')
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError('sparse_map_apply: %s must be a float32 tensor of shape %s on %s, got %s %s on %s'
+                             % (name, shape, dev, t.dtype, tuple(t.shape), t.device))
+        return t
+    out = result(out, 'out')
+    frac = result(frac_out, 'frac_out') if skipna and frac_out is not None and frac_out is not False else None
+    if frac is not None and frac.stride() != out.stride():
+        # the kernel writes both through one set of strides: a fraction of another layout goes through a twin of `out`
+        frac_user, frac = frac, torch.empty_strided(shape, out.stride(), dtype=torch.float32, device=dev)
     else:
-        require_device(out, 'sparse_map_apply')
-        if out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != dev:
-            raise ValueError('sparse_map_apply: out must be a float32 tensor of shape %s on %s, got %s %s on %s'
-                             % (shape, dev, out.dtype, tuple(out.shape), out.device))
+        frac_user = frac
     if out.numel() == 0:
-        return out
+        return out if frac is None else (out, frac_user)
 
     def describe(xv, yv):
         xs = _space_stride(xv.shape[a0:a1], xv.stride()[a0:a1])
@@ -1975,18 +2033,28 @@ def sparse_map_apply(m, x, space_axes, out=None):
         d.inner_ext, d.x_inner_stride, d.y_inner_stride = (rest[inner] if inner is not None else (1, 0, 0))
         return d
 
-    y = out
+    y, f = out, frac
     d = describe(x, y)
     if d is None:                       # the documented fallback: contiguous operands
         x = x.contiguous()
         y = out if out.is_contiguous() else torch.empty(shape, dtype=torch.float32, device=dev)
+        if frac is not None:
+            f = frac if y is out else torch.empty(shape, dtype=torch.float32, device=dev)
         d = describe(x, y)
     with torch.cuda.device(dev):
-        check(lib().dlwpcs_sparse_map_apply(ctypes.byref(d), row_ptr.data_ptr(), ptr(col), ptr(val), x.data_ptr(),
-                                            y.data_ptr(), stream_ptr()), 'dlwpcs_sparse_map_apply')
+        if skipna:
+            check(lib().dlwpcs_sparse_map_apply_masked(ctypes.byref(d), row_ptr.data_ptr(), ptr(col), ptr(val), x.data_ptr(),
+                                                       y.data_ptr(), ptr(f), float(min_valid),
+                                                       nat.MAP_RENORMALIZE if renormalize else 0, stream_ptr()),
+                  'dlwpcs_sparse_map_apply_masked')
+        else:
+            check(lib().dlwpcs_sparse_map_apply(ctypes.byref(d), row_ptr.data_ptr(), ptr(col), ptr(val), x.data_ptr(),
+                                                y.data_ptr(), stream_ptr()), 'dlwpcs_sparse_map_apply')
         if y is not out:
             out.copy_(y)
-    return out
+        if f is not frac_user:
+            frac_user.copy_(f)
+    return out if frac is None else (out, frac_user)
 
 
 # ------------------------------------------------------------------------------------------------------------------ #

@@ -21,6 +21,15 @@ _FILE_MSG = ('CubeSphereRemap.%s needs the TempestRemap executables or xarray, w
              'existing offline map to arrays with remap_array / inverse_remap_array / inverse_remap_forecast instead')
 
 
+def _missing_kw(kw, frac=True):
+    """the missing-value keywords of OfflineMap.apply that the array / forecast methods hand through"""
+    known = ('skipna', 'min_valid', 'renormalize') + (('frac_out',) if frac else ())
+    for k in kw:
+        if k not in known:
+            raise TypeError('unexpected keyword %r (missing-value keywords: %s)' % (k, ', '.join(known)))
+    return kw
+
+
 def _cube_axis(dims):
     """first of the three consecutive cube dims of a labelled forecast"""
     dims, a0 = tuple(dims), None
@@ -135,28 +144,32 @@ class CubeSphereRemap(object):
         self._loaded[which] = m
         return m
 
-    def remap_array(self, x, axes=(-2, -1)):
+    def remap_array(self, x, axes=(-2, -1), **missing):
         """
         Lat-lon -> cubed sphere with the forward map: the (lat, lon) axes of x are replaced in place by (face, height, width).
         numpy input: host path, the input's float dtype.  HIP tensor (fp32 or bf16): fp32 device result, one launch.
+        skipna, min_valid, renormalize, frac_out: NaN cells are missing values, left out of the sums (OfflineMap.apply).
         """
-        return self._get('forward').apply(x, axes)
+        return self._get('forward').apply(x, axes, **_missing_kw(missing))
 
-    def inverse_remap_array(self, x, axes=(-3, -2, -1)):
+    def inverse_remap_array(self, x, axes=(-3, -2, -1), **missing):
         """
         Cubed sphere -> lat-lon with the inverse map: the (face, height, width) axes of x are replaced by (lat, lon).
         numpy input: host path, the input's float dtype.  HIP tensor (fp32 or bf16): fp32 device result, one launch.
+        skipna, min_valid, renormalize, frac_out: NaN cells are missing values, left out of the sums (OfflineMap.apply).
         """
-        return self._get('inverse').apply(x, axes)
+        return self._get('inverse').apply(x, axes, **_missing_kw(missing))
 
-    def inverse_remap_forecast(self, forecast):
+    def inverse_remap_forecast(self, forecast, **missing):
         """
         Inverse-remap a labelled cubed-sphere forecast (a Forecast whose space dims are 'x0', 'x1', 'x2' as from
         TimeSeriesEstimator.predict / verification, or 'face', 'height', 'width' as from add_metadata_to_forecast_cs).
         Returns a Forecast with 'lat', 'lon' in their place and the map's coordinates; the values stay on the device when they
         came from there.  `.lat` / `.lon` are Forecasts of dims ('lat',) / ('lon',), so forecast_error(..., weighted=True)
-        weights by latitude.  NaN cells (a verification past the end of the data) propagate to every row they feed.
+        weights by latitude.  NaN cells (a verification past the end of the data) propagate to every row they feed, unless
+        skipna=True (with min_valid, renormalize as in OfflineMap.apply) leaves them out of the sums.
         """
+        missing = _missing_kw(missing, frac=False)
         dims = tuple(forecast.dims)
         a0 = None
         for names in _CUBE_DIMS:
@@ -168,7 +181,7 @@ class CubeSphereRemap(object):
         m = self._get('inverse')
         if m.dst_kind != 'latlon' or m.lat_b is None:
             raise ValueError('the inverse map %s has no lat-lon destination with cell centres (yc_b / xc_b)' % m)
-        vals = m.apply(forecast.values, (a0, a0 + 1, a0 + 2))
+        vals = m.apply(forecast.values, (a0, a0 + 1, a0 + 2), **missing)
         new_dims = dims[:a0] + ('lat', 'lon') + dims[a0 + 3:]
         coords = {d: c for d, c in forecast.coords.items() if d in new_dims}
         coords['lat'], coords['lon'] = m.lat_b.copy(), m.lon_b.copy()
@@ -215,24 +228,27 @@ class CubeSphereRemap(object):
             raise ValueError("No sampling map has been defined; use the 'generate_sampling_map' function first")
         return self.sampling_map
 
-    def sample_array(self, x, axes=(-3, -2, -1)):
+    def sample_array(self, x, axes=(-3, -2, -1), **missing):
         """
         Sample the cubed sphere with the sampling map: the (face, height, width) axes of x are replaced by (n,) for a point
         list or (lat, lon) for a lat-lon grid.  numpy input: host path, the input's float dtype.  HIP tensor (fp32 or bf16):
         fp32 device result, one launch.
+        skipna, min_valid, renormalize, frac_out: NaN cells are missing values, left out of the sums (OfflineMap.apply).
         """
-        return self._sampling().apply(x, axes)
+        return self._sampling().apply(x, axes, **_missing_kw(missing))
 
-    def sample_forecast(self, forecast):
+    def sample_forecast(self, forecast, **missing):
         """
         Sample a labelled cubed-sphere forecast (space dims as for inverse_remap_forecast).  A lat-lon sampling map gives what
         inverse_remap_forecast gives, smooth; a point list gives the dim 'point' with the coords 'lat' and 'lon' along it
         (`.lat` / `.lon` are Forecasts of dims ('point',)).  The values stay on the device when they came from there.
+        skipna, min_valid, renormalize: NaN cells are missing values, left out of the sums (OfflineMap.apply).
         """
+        missing = _missing_kw(missing, frac=False)
         m = self._sampling()
         dims = tuple(forecast.dims)
         a0 = _cube_axis(dims)
-        vals = m.apply(forecast.values, (a0, a0 + 1, a0 + 2))
+        vals = m.apply(forecast.values, (a0, a0 + 1, a0 + 2), **missing)
         grid = m.dst_kind == 'latlon'
         new_dims = dims[:a0] + (('lat', 'lon') if grid else ('point',)) + dims[a0 + 3:]
         coords = {d: c for d, c in forecast.coords.items() if d in new_dims}

@@ -168,22 +168,100 @@ class OfflineMap(object):
             raise ValueError('space axes %s have shape %s; the map reads %s' % (tuple(axes), got, self.src_shape))
         return ax[0], ax[-1] + 1
 
-    def apply(self, x, axes, out=None):
+    def check_skipna(self, min_valid):
+        """what skipna=True asks of the map and of min_valid (ValueError otherwise): no negative weight -- the share of a row's
+        weight that is present must grow with every present entry -- and 0 <= min_valid <= 1"""
+        if not (0.0 <= float(min_valid) <= 1.0):
+            raise ValueError('min_valid = %r must lie in [0, 1]' % (min_valid,))
+        neg = getattr(self, '_has_negative', None)
+        if neg is None:
+            neg = self._has_negative = bool(self.val.size and self.val.min() < 0)
+        if neg:
+            raise ValueError('%s holds negative weights: skipna=True serves maps with weights >= 0 only' % self)
+
+    def apply(self, x, axes, out=None, skipna=False, min_valid=0.5, renormalize=True, frac_out=None):
         """
         Apply the map to the source grid held in the consecutive `axes` of x; they are replaced by the destination grid
         (dst_shape).  numpy input: the host path (fp64 sums, the input's float dtype back).  HIP tensor: one
         dlwpcs_sparse_map_apply launch on the current stream, fp32 result (`out`: a float32 tensor or view to write to).
+
+        skipna=True: NaN in x is a missing value (see `apply_host`; on the device dlwpcs_sparse_map_apply_masked).  frac_out:
+        True, or on the device a float32 tensor to write to: the present share of every output's weight is returned too, as
+        (y, frac).
         """
         if isinstance(x, np.ndarray) or not _is_tensor(x):
             if out is not None:
                 raise ValueError('out= is for device tensors')
-            return self.apply_host(np.asarray(x), axes)
+            if frac_out is not None and frac_out is not True and frac_out is not False:
+                raise ValueError('frac_out= a tensor is for device tensors; frac_out=True returns it')
+            return self.apply_host(np.asarray(x), axes, skipna=skipna, min_valid=min_valid, renormalize=renormalize,
+                                   frac_out=frac_out)
         from .. import ops
-        return ops.sparse_map_apply(self, x, axes, out=out)
+        return ops.sparse_map_apply(self, x, axes, out=out, skipna=skipna, min_valid=min_valid, renormalize=renormalize,
+                                    frac_out=frac_out)
 
-    def apply_host(self, x, axes):
-        """numpy restatement of the kernel with fp64 accumulation; float inputs keep their dtype, others give float64"""
+    def apply_host(self, x, axes, skipna=False, min_valid=0.5, renormalize=True, frac_out=None):
+        """
+        numpy restatement of the kernel with fp64 accumulation; float inputs keep their dtype, others give float64.
+
+        skipna=True restates dlwpcs_sparse_map_apply_masked (include/dlwpcs.h): a NaN in x is missing, an entry whose fp32 weight
+        is 0 is not there.  Which outputs are missing is decided exactly as the kernel decides it -- `wval` and `wall`, the fp32
+        sums in CSR order of the fp32 weights of the present / of all entries; missing iff an entry is missing and
+        (wval < float32(min_valid) * wall, or none is present, or min_valid >= 1) -- so host and device agree on every NaN.
+        The values keep fp64: the sum over the present entries, times (all weight / present weight) in fp64 with `renormalize`.
+        frac_out=True: (y, frac) with frac = wval / wall in float32 (1 where nothing is missing, 0 for a row without entries).
+        """
         x = np.asarray(x)
+        if not skipna:
+            if frac_out is not None and frac_out is not False:
+                raise ValueError('frac_out needs skipna=True')
+            return self._apply_host_plain(x, axes)
+        self.check_skipna(min_valid)
+        a0, a1 = self._space(x.shape, axes)
+        pre, post = x.shape[:a0], x.shape[a1:]
+        P, Q = int(np.prod(pre, dtype=np.int64)), int(np.prod(post, dtype=np.int64))
+        xs = x.reshape(P, self.n_a, Q)
+        f32 = np.float32
+        acc = np.zeros((P, self.n_b, Q), dtype=np.float64)
+        wval64 = np.zeros((P, self.n_b, Q), dtype=np.float64)
+        wall64 = np.zeros(self.n_b, dtype=np.float64)
+        wval = np.zeros((P, self.n_b, Q), dtype=f32)
+        wall = np.zeros(self.n_b, dtype=f32)
+        nval = np.zeros((P, self.n_b, Q), dtype=np.int32)
+        nmiss = np.zeros((P, self.n_b, Q), dtype=np.int32)
+        lengths = np.diff(self.row_ptr.astype(np.int64))
+        for s in range(int(lengths.max()) if lengths.size else 0):
+            rows = np.nonzero(lengths > s)[0]
+            j = self.row_ptr[rows].astype(np.int64) + s
+            there = self.val[j] != 0                            # decided on the fp32 weight, as on the device
+            rows, j = rows[there], j[there]
+            if not rows.size:
+                continue
+            xv = xs[:, self.col[j], :].astype(np.float64)
+            ok = ~np.isnan(xv)
+            v32, v64 = self.val[j][None, :, None], self.val64[j][None, :, None]
+            acc[:, rows, :] += np.where(ok, v64 * np.where(ok, xv, 0.0), 0.0)
+            wval64[:, rows, :] += np.where(ok, v64, 0.0)
+            wall64[rows] += self.val64[j]
+            wval[:, rows, :] = wval[:, rows, :] + np.where(ok, v32, f32(0))       # one rounded fp32 addition per entry
+            wall[rows] = wall[rows] + self.val[j]
+            nval[:, rows, :] += ok
+            nmiss[:, rows, :] += ~ok
+        need = (f32(min_valid) * wall)[None, :, None]           # one rounded fp32 multiplication
+        holes = nmiss > 0
+        missing = holes & ((wval < need) | (nval == 0) | (f32(min_valid) >= f32(1)))
+        y = acc
+        with np.errstate(all='ignore'):
+            if renormalize:
+                y = np.where(holes, acc * (wall64[None, :, None] / wval64), acc)
+            y = np.where(missing, np.nan, y)
+            frac = np.where((nval + nmiss) > 0, wval / wall[None, :, None], f32(0)).astype(f32)
+        dt = x.dtype if np.issubdtype(x.dtype, np.floating) else np.float64
+        shape = pre + tuple(self.dst_shape) + post
+        y = y.reshape(shape).astype(dt, copy=False)
+        return (y, frac.reshape(shape)) if frac_out else y
+
+    def _apply_host_plain(self, x, axes):
         a0, a1 = self._space(x.shape, axes)
         pre, post = x.shape[:a0], x.shape[a1:]
         P, Q = int(np.prod(pre, dtype=np.int64)), int(np.prod(post, dtype=np.int64))
@@ -196,6 +274,53 @@ class OfflineMap(object):
             y[:, rows, :] += self.val64[j][None, :, None] * xs[:, self.col[j], :].astype(np.float64)
         dt = x.dtype if np.issubdtype(x.dtype, np.floating) else np.float64
         return y.reshape(pre + tuple(self.dst_shape) + post).astype(dt, copy=False)
+
+    def masked(self, mask, min_valid=0.5, renormalize=True):
+        """
+        (map, frac): this map with a FIXED mask over its source cells (True / non-zero = missing, shape self.src_shape or
+        (n_a,)) folded into the weights once, on the host: the entries of masked cells are dropped, the others scaled by
+        (all weight / present weight) of their row in fp64 with `renormalize`, and a row that `apply(..., skipna=True,
+        min_valid=min_valid)` would give as NaN for a field with NaN at the mask -- the same fp32 decision -- becomes EMPTY.
+        The plain kernel then serves a fixed land-sea mask at no cost per call: the new map applied to a field with any
+        finite value at the masked cells gives what the dynamic form gives with NaN there, and 0 where that gives NaN.
+        frac: float32 of self.dst_shape, the present share of every row's weight (1 for an untouched row, 0 for a row without
+        entries); rows with 0 < frac and no entries left are the dropped ones.
+        """
+        self.check_skipna(min_valid)
+        mask = np.asarray(mask).astype(bool).reshape(-1)
+        if mask.size != self.n_a:
+            raise ValueError('mask has %d cells; the map reads %d' % (mask.size, self.n_a))
+        f32 = np.float32
+        rows = np.repeat(np.arange(self.n_b, dtype=np.int64), np.diff(self.row_ptr.astype(np.int64)))
+        there = self.val != 0
+        ok = there & ~mask[self.col]
+        wall, wval = np.zeros(self.n_b, dtype=f32), np.zeros(self.n_b, dtype=f32)
+        wall64, wval64 = np.zeros(self.n_b, dtype=np.float64), np.zeros(self.n_b, dtype=np.float64)
+        start = self.row_ptr[:-1].astype(np.int64)
+        lengths = np.diff(self.row_ptr.astype(np.int64))
+        for s in range(int(lengths.max()) if lengths.size else 0):
+            r = np.nonzero(lengths > s)[0]
+            j = start[r] + s
+            wall[r] = wall[r] + np.where(there[j], self.val[j], f32(0))
+            wval[r] = wval[r] + np.where(ok[j], self.val[j], f32(0))
+            wall64[r] += np.where(there[j], self.val64[j], 0.0)
+            wval64[r] += np.where(ok[j], self.val64[j], 0.0)
+        nval = np.bincount(rows[ok], minlength=self.n_b)
+        nmiss = np.bincount(rows[there & ~ok], minlength=self.n_b)
+        holes = nmiss > 0
+        dropped = holes & ((wval < f32(min_valid) * wall) | (nval == 0) | (f32(min_valid) >= f32(1)))
+        with np.errstate(all='ignore'):
+            frac = np.where((nval + nmiss) > 0, wval / wall, f32(0)).astype(f32)
+            factor = np.where(holes & ~dropped, wall64 / wval64, 1.0) if renormalize else np.ones(self.n_b)
+        keep = ok & ~dropped[rows]
+        out = OfflineMap(rows[keep] + 1, self.col[keep].astype(np.int64) + 1, self.val64[keep] * factor[rows[keep]], self.n_a, self.n_b,
+                         name=self.name, dst_cells=self.dst_kind == 'cells')
+        # the grids as this map holds them (already in (lat, lon) / face order: nothing to re-derive from file conventions)
+        for a in ('src_shape', 'dst_shape', '_dst_order', 'src_kind', 'dst_kind', 'lat_a', 'lon_a', 'lat_b', 'lon_b', 'yc_a', 'xc_a',
+                  'yc_b', 'xc_b', 'area_a', 'area_b'):
+            setattr(out, a, getattr(self, a))
+        out.frac_b = frac.astype(np.float64)
+        return out, frac.reshape(self.dst_shape)
 
 
 def _is_tensor(x):

@@ -143,6 +143,115 @@ int make_geom(const dlwpcs_sparse_map_desc *d, MapGeom &G, bool &empty) {
     return DLWPCS_OK;
 }
 
+// The same map applied to data with holes (dlwpcs_sparse_map_apply_masked): a NaN source value is MISSING, an entry of weight 0 is
+// not there at all.  Same lanes, tiles, XCD dealing and outer slices as sparse_map_kernel, same gathers (all issued before the
+// first fma, dead slots re-reading slice o0); what a gathered value contributes is chosen by selects on `a == a`, never by a
+// branch.  Per output: acc, the fma chain over the present entries; wval, their weights added in CSR order; the counts of present
+// and missing entries; per lane: wall, the weights of all entries added in CSR order (adding the +0 of a skipped entry changes no
+// bit).  Where nothing is missing wval == wall bitwise and acc is sparse_map_kernel's chain: the same bits as the plain launch.
+template <typename T>
+__global__ __launch_bounds__(MR_THREADS) void sparse_map_masked_kernel(MapGeom G, const int32_t *__restrict__ row_ptr,
+                                                                       const int32_t *__restrict__ col,
+                                                                       const float *__restrict__ val, const T *__restrict__ x,
+                                                                       float *__restrict__ y, float *__restrict__ frac,
+                                                                       float min_valid, int renorm) {
+#pragma clang fp contract(off)
+    for (int64_t b = blockIdx.x; b < G.nblk; b += gridDim.x) {
+        const int64_t w = G.remap ? (int64_t)xcd_remap((uint32_t)b, (uint32_t)G.nblk) : b;
+        const int64_t chunk = w / G.n_tiles;
+        const int32_t tile = (int32_t)(w - chunk * G.n_tiles);
+        const int32_t idx = tile * MR_THREADS + (int32_t)threadIdx.x;
+        if (idx >= G.n_lanes) continue;
+        int32_t r, k;
+        if (G.kfast) {
+            r = (int32_t)((uint32_t)idx / (uint32_t)G.K);
+            k = idx - r * G.K;
+        } else {
+            k = (int32_t)((uint32_t)idx / (uint32_t)G.n_b);
+            r = idx - k * G.n_b;
+        }
+        const int64_t o0 = chunk * MR_U;
+        int64_t i2 = o0 % G.ext[2], q = o0 / G.ext[2];
+        int64_t i1 = q % G.ext[1], i0 = q / G.ext[1];
+        int64_t xoff[MR_U], yoff[MR_U];
+        bool live[MR_U];
+#pragma unroll
+        for (int u = 0; u < MR_U; ++u) {
+            live[u] = o0 + u < G.n_outer;
+            xoff[u] = i0 * G.xo[0] + i1 * G.xo[1] + i2 * G.xo[2] + (int64_t)k * G.xk;
+            yoff[u] = i0 * G.yo[0] + i1 * G.yo[1] + i2 * G.yo[2] + (int64_t)r * G.ys + (int64_t)k * G.yk;
+            if (++i2 == G.ext[2]) {
+                i2 = 0;
+                if (++i1 == G.ext[1]) { i1 = 0; ++i0; }
+            }
+        }
+#pragma unroll
+        for (int u = 1; u < MR_U; ++u)
+            if (!live[u]) xoff[u] = xoff[0];
+        float acc[MR_U], wval[MR_U];
+        int32_t nval[MR_U], nmiss[MR_U];
+#pragma unroll
+        for (int u = 0; u < MR_U; ++u) { acc[u] = 0.f; wval[u] = 0.f; nval[u] = 0; nmiss[u] = 0; }
+        float wall = 0.f;
+        const int32_t j1 = row_ptr[r + 1];
+        int32_t j = row_ptr[r];
+        for (; j + 1 < j1; j += 2) {
+            const int64_t c0 = (int64_t)col[j] * G.xs, c1 = (int64_t)col[j + 1] * G.xs;
+            const float v0 = val[j], v1 = val[j + 1];
+            float a0[MR_U], a1[MR_U];
+#pragma unroll
+            for (int u = 0; u < MR_U; ++u) {
+                a0[u] = load_x(x + xoff[u] + c0);
+                a1[u] = load_x(x + xoff[u] + c1);
+            }
+            const bool e0 = v0 != 0.f, e1 = v1 != 0.f;
+            wall += e0 ? v0 : 0.f;
+            wall += e1 ? v1 : 0.f;
+#pragma unroll
+            for (int u = 0; u < MR_U; ++u) {
+                const bool p0 = e0 & (a0[u] == a0[u]), p1 = e1 & (a1[u] == a1[u]);
+                const float t0 = fmaf(v0, a0[u], acc[u]);
+                acc[u] = p0 ? t0 : acc[u];
+                const float t1 = fmaf(v1, a1[u], acc[u]);
+                acc[u] = p1 ? t1 : acc[u];
+                wval[u] += p0 ? v0 : 0.f;
+                wval[u] += p1 ? v1 : 0.f;
+                nval[u] += (int32_t)p0 + (int32_t)p1;
+                nmiss[u] += (int32_t)(e0 & !p0) + (int32_t)(e1 & !p1);
+            }
+        }
+        if (j < j1) {
+            const int64_t c0 = (int64_t)col[j] * G.xs;
+            const float v0 = val[j];
+            float a0[MR_U];
+#pragma unroll
+            for (int u = 0; u < MR_U; ++u) a0[u] = load_x(x + xoff[u] + c0);
+            const bool e0 = v0 != 0.f;
+            wall += e0 ? v0 : 0.f;
+#pragma unroll
+            for (int u = 0; u < MR_U; ++u) {
+                const bool p0 = e0 & (a0[u] == a0[u]);
+                const float t0 = fmaf(v0, a0[u], acc[u]);
+                acc[u] = p0 ? t0 : acc[u];
+                wval[u] += p0 ? v0 : 0.f;
+                nval[u] += (int32_t)p0;
+                nmiss[u] += (int32_t)(e0 & !p0);
+            }
+        }
+        const float need = min_valid * wall;        // one rounded multiply: the host twin takes the same decision
+#pragma unroll
+        for (int u = 0; u < MR_U; ++u) {
+            if (!live[u]) continue;
+            const bool holes = nmiss[u] > 0;
+            const bool missing = holes && (wval[u] < need || nval[u] == 0 || min_valid >= 1.f);
+            const float scale = (renorm && holes) ? wall / wval[u] : 1.f;
+            const float out = (renorm && holes) ? acc[u] * scale : acc[u];
+            y[yoff[u]] = missing ? __uint_as_float(0x7fc00000u) : out;
+            if (frac) frac[yoff[u]] = (nval[u] + nmiss[u] > 0) ? wval[u] / wall : 0.f;
+        }
+    }
+}
+
 }  // namespace
 
 }  // namespace dlwpcs
@@ -165,4 +274,29 @@ extern "C" int dlwpcs_sparse_map_apply(const dlwpcs_sparse_map_desc *d, const in
     else
         hipLaunchKernelGGL((sparse_map_kernel<float>), grid, dim3(MR_THREADS), 0, s, G, row_ptr, col, val, (const float *)x, y);
     return check_launch("sparse_map");
+}
+
+extern "C" int dlwpcs_sparse_map_apply_masked(const dlwpcs_sparse_map_desc *d, const int32_t *row_ptr, const int32_t *col,
+                                              const float *val, const void *x, float *y, float *frac, float min_valid, int flags,
+                                              dlwpcs_stream_t stream) {
+    MapGeom G;
+    bool empty = false;
+    int rc = make_geom(d, G, empty);
+    if (rc != DLWPCS_OK) return rc;
+    if (!(min_valid >= 0.f && min_valid <= 1.f))
+        return fail(DLWPCS_E_INVALID, "sparse_map_masked: min_valid %g is not in [0, 1]", (double)min_valid);
+    if (flags & ~DLWPCS_MAP_RENORMALIZE) return fail(DLWPCS_E_INVALID, "sparse_map_masked: unknown flags 0x%x", flags);
+    if (empty) return DLWPCS_OK;
+    if (!row_ptr || !x || !y || (d->nnz > 0 && (!col || !val))) return fail(DLWPCS_E_INVALID, "sparse_map_masked: null operand");
+    const dim3 grid((unsigned)(G.nblk < MR_MAX_GRID ? G.nblk : MR_MAX_GRID));
+    hipStream_t s = (hipStream_t)stream;
+    const int renorm = (flags & DLWPCS_MAP_RENORMALIZE) ? 1 : 0;
+    const bool bf = d->x_dtype == DLWPCS_BF16;
+    if (bf)
+        hipLaunchKernelGGL((sparse_map_masked_kernel<bf16_t>), grid, dim3(MR_THREADS), 0, s, G, row_ptr, col, val,
+                           (const bf16_t *)x, y, frac, min_valid, renorm);
+    else
+        hipLaunchKernelGGL((sparse_map_masked_kernel<float>), grid, dim3(MR_THREADS), 0, s, G, row_ptr, col, val, (const float *)x, y,
+                           frac, min_valid, renorm);
+    return check_launch("sparse_map_masked");
 }

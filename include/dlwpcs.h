@@ -609,6 +609,31 @@ typedef struct dlwpcs_sparse_map_desc {
 int dlwpcs_sparse_map_apply(const dlwpcs_sparse_map_desc *d, const int32_t *row_ptr, const int32_t *col, const float *val,
                             const void *x, float *y, dlwpcs_stream_t stream);
 
+/* The same map over data with holes: a NaN in x is a MISSING value (+-inf is data), and an entry with val[j] == 0 is not there at
+ * all (the bilinear maps' triangle rows repeat a cell with weight exactly 0: neither present nor missing).  For destination row r
+ * and one (outer, inner) position, over the row's non-zero entries in CSR order:
+ *   acc   the fp32 fma chain of val[j] * x[col[j]] over the entries whose x is not NaN (grouped as dlwpcs_sparse_map_apply's)
+ *   wval  the fp32 sum of val[j] over those entries;   wall  the fp32 sum of val[j] over all of them
+ *   nmiss the number of entries whose x is NaN
+ * y is MISSING (a quiet NaN) iff nmiss > 0 and (wval < min_valid * wall [one fp32 multiply], or every entry is missing, or
+ * min_valid >= 1); otherwise y = acc * (wall / wval) with DLWPCS_MAP_RENORMALIZE, y = acc without.  Where nothing is missing
+ * wval == wall bitwise and y has the bits of dlwpcs_sparse_map_apply.  frac (NULL, or fp32 with y's shape and strides) receives
+ * wval / wall: exactly 1 where nothing is missing, 0 for a row without non-zero entries (whose y is 0).
+ * The decision is fp32 additions in a fixed order, one multiply and one compare: DLWP.remap.OfflineMap.apply_host takes the
+ * same one bit for bit.  min_valid must lie in [0, 1]; the weights are expected to be >= 0 (the host refuses others).
+ * One launch, no LDS, no atomics, no host synchronisation, no allocation (capturable); bitwise repeatable. */
+#define DLWPCS_MAP_RENORMALIZE 1
+int dlwpcs_sparse_map_apply_masked(const dlwpcs_sparse_map_desc *d, const int32_t *row_ptr, const int32_t *col,
+                                   const float *val, const void *x, float *y, float *frac, float min_valid, int flags,
+                                   dlwpcs_stream_t stream);
+
+/* Missing values per plane of a contiguous (n_planes, plane) array: count[p] = the number of NaN elements (dtype DLWPCS_F32: any
+ * payload, either sign; +-inf is not counted) or of -32768 codes (dtype DLWPCS_I16, the packed series' missing code) of plane p.
+ * x needs the alignment of its element only, plane may be any size < 2^31.  One streaming pass; every count is written by exactly
+ * one workgroup (no atomics: count need not be zeroed).  One launch, no host synchronisation, no allocation. */
+#define DLWPCS_I16 2                  /* dlwpcs_missing_count only: int16 codes */
+int dlwpcs_missing_count(const void *x, int dtype, int64_t n_planes, int64_t plane, int32_t *count, dlwpcs_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------- *
  * Conservative offline maps made on the device (DLWP/remap/overlap.py is the host twin and states the maths): A[r, c], the
  * area in steradians of (lat-lon cell r) intersected with (equiangular cubed-sphere cell c), in closed form and fp64, in CSR
