@@ -139,6 +139,13 @@ class RowsDesc(ctypes.Structure):
                 ('src_stride', ctypes.c_int64 * SCORE_MAX_DIMS), ('out_stride', ctypes.c_int64 * SCORE_MAX_DIMS)]
 
 
+class ZonalSpectrumDesc(ctypes.Structure):
+    """struct dlwpcs_zonal_spectrum_desc (include/dlwpcs.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ('L', 'n_wave', 'n_dims', 'remove_mean')] + \
+               [('ext', ctypes.c_int64 * SCORE_MAX_DIMS), ('kept', ctypes.c_int32 * SCORE_MAX_DIMS),
+                ('stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 3)]
+
+
 AFFINE_MUL_ADD, AFFINE_SUB_DIV = 0, 1
 AFFINE_MAX_CHANNELS = 1024
 
@@ -228,6 +235,8 @@ PROTOTYPES = {
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),
     'dlwpcs_missing_count': (c_int, [c_void_p, c_int, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p]),
+    'dlwpcs_zonal_spectrum_scratch_bytes': (c_size_t, [c_void_p]),
+    'dlwpcs_zonal_spectrum': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_count': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_fill': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p]),
     'dlwpcs_cube_bilinear': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1820,6 +1820,151 @@ def score_reduce(method, operands, shape, reduced, lagged=None, out_f32=False, i
 
 
 # ------------------------------------------------------------------------------------------------------------------ #
+# Zonal spectra (DLWP/verify.py zonal_spectrum / zonal_cross_spectrum / zonal_coherence), include/dlwpcs.h dlwpcs_zonal_spectrum
+# ------------------------------------------------------------------------------------------------------------------ #
+
+SPECTRUM_MAX_L = 1728
+_twiddles = {}              # (L, device) -> (L, 2) float32 device tensor {cos, -sin}(2 pi m / L)
+
+
+def spectrum_twiddle_host(L):
+    """(L, 2) float32: cos and -sin of 2 pi m / L for m < L, evaluated in float64 and rounded once"""
+    ang = 2.0 * np.pi * np.arange(int(L), dtype=np.float64) / float(L)
+    return np.stack([np.cos(ang), -np.sin(ang)], axis=1).astype(np.float32)
+
+
+def spectrum_twiddle(L, device):
+    """the twiddle table of dlwpcs_zonal_spectrum for rows of L longitudes on `device`, made once and kept"""
+    key = (int(L), str(torch.device(device)))
+    hit = _twiddles.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise nat.NativeError('zonal_spectrum: first use of L = %d inside a graph capture (run it once eagerly first)' % L)
+        hit = torch.from_numpy(spectrum_twiddle_host(L)).to(device)
+        _twiddles[key] = hit
+    return hit
+
+
+def spectrum_dims(shape, strides, reduced):
+    """
+    The leading dims of dlwpcs_zonal_spectrum_desc: [(extent, (stride per operand), kept)] for the logical leading `shape`,
+    per-operand `strides` in elements (0 = broadcast) and the set `reduced` of averaged axes.  Unit axes are dropped; neighbours
+    with the same flag are merged where every operand allows it (outer stride == inner stride * inner extent).  Pure Python.
+    """
+    shape = tuple(int(e) for e in shape)
+    reduced = set(int(r) % len(shape) for r in reduced) if shape else set()
+    out = []
+    for i, e in enumerate(shape):
+        if e == 1:
+            continue
+        st, kept = tuple(int(s[i]) for s in strides), i not in reduced
+        if out and out[-1][2] == kept and all(ps == cs * e for ps, cs in zip(out[-1][1], st)):
+            out[-1] = (out[-1][0] * e, st, kept)
+        else:
+            out.append((e, st, kept))
+    return out
+
+
+def spectrum_desc(L, dims, n_wave=None, remove_mean=False):
+    """nat.ZonalSpectrumDesc of rows of L longitudes with the leading `dims` of spectrum_dims"""
+    if len(dims) > nat.SCORE_MAX_DIMS:
+        raise NotImplementedError('zonal_spectrum: more than %d leading dims after merging' % nat.SCORE_MAX_DIMS)
+    d = nat.ZonalSpectrumDesc()
+    d.L, d.n_wave, d.n_dims, d.remove_mean = int(L), int(n_wave or 0), len(dims), 1 if remove_mean else 0
+    for i, (e, st, kept) in enumerate(dims):
+        d.ext[i], d.kept[i] = e, 1 if kept else 0
+        for k in range(3):
+            d.stride[k][i] = st[k]
+    return d
+
+
+def spectrum_launch(d, a, b, w, out, skipped=None):
+    """dlwpcs_zonal_spectrum on the current stream: device tensors a, b (None: single form), w (None: unit weights) addressed
+    by the descriptor, into the float32 tensor `out` and the int32 tensor `skipped` (None: not wanted)"""
+    dev = a.device
+    tw = spectrum_twiddle(d.L, dev)
+    nbytes = int(lib().dlwpcs_zonal_spectrum_scratch_bytes(ctypes.byref(d)))
+    scratch = _workspace(nbytes, dev, 'spectrum') if nbytes else None
+    with torch.cuda.device(dev):
+        check(lib().dlwpcs_zonal_spectrum(ctypes.byref(d), ptr(a), ptr(b) or None, ptr(w) or None, ptr(tw), ptr(scratch) or None,
+                                          ptr(out), ptr(skipped) or None, stream_ptr()), 'dlwpcs_zonal_spectrum')
+    return out
+
+
+def _lon_last(t, lon_axis):
+    """t with its longitude axis last and unit-stride: a view where that is possible, else one copy"""
+    t = t.movedim(lon_axis, -1)
+    if t.shape[-1] > 1 and t.stride(-1) != 1:
+        t = t.contiguous()
+    return t
+
+
+def zonal_spectrum(a, b=None, lon_axis=-1, reduced=(), weights=None, n_wave=None, remove_mean=False, counts=False):
+    """
+    One-sided zonal power spectrum of the float32 device tensor `a` along `lon_axis`, P_k = c_k |X_k|^2 / L^2 (c_k = 1 for k = 0
+    and the Nyquist wavenumber of an even L, else 2), as the weighted mean over the axes `reduced` (axes of `a`, the longitude
+    axis not among them) of the rows whose values are all finite.  weights: a float32 device tensor that broadcasts against the
+    leading shape (a's shape without the longitude axis) by numpy's trailing-axis rule.  n_wave: the first n_wave wavenumbers
+    only (default: all L // 2 + 1).  remove_mean: subtract every row's mean first and report P_0 as that mean squared.
+    Returns a float32 device tensor (kept axes..., K); with b (same shape as a), the pair form: (4, kept axes..., K) = P_aa, P_bb,
+    co-spectrum and quadrature spectrum.  counts=True: also the int32 tensor (kept axes...) of rows that did not count.
+    At most two launches on the current stream, no host synchronisation (the twiddle table of an L is uploaded at its first use).
+    """
+    require_device(a, 'zonal_spectrum')
+    ops = [a] if b is None else [a, b]
+    for t in ops:
+        require_device(t, 'zonal_spectrum')
+        if t.dtype != torch.float32:
+            raise TypeError('zonal_spectrum: operands must be float32, got %s' % t.dtype)
+        if t.device != a.device or t.shape != a.shape:
+            raise ValueError('zonal_spectrum: the two operands must have one shape and one device')
+    if a.dim() < 1:
+        raise ValueError('zonal_spectrum: the input needs a longitude axis')
+    ops = [_lon_last(t, lon_axis) for t in ops]
+    L = int(ops[0].shape[-1])
+    if L < 2:
+        raise ValueError('zonal_spectrum: %d longitudes (at least 2)' % L)
+    if L > SPECTRUM_MAX_L:
+        raise NotImplementedError('zonal_spectrum: %d longitudes, the kernel serves 2 .. %d' % (L, SPECTRUM_MAX_L))
+    K = L // 2 + 1
+    if n_wave is not None:
+        if not 1 <= int(n_wave) <= K:
+            raise ValueError('zonal_spectrum: n_wave = %s outside 1 .. L // 2 + 1 = %d' % (n_wave, K))
+        K = int(n_wave)
+    lead = tuple(int(e) for e in ops[0].shape[:-1])
+    nd = len(lead)
+    lon = int(lon_axis) % a.dim()
+    red = set()
+    for r in reduced:
+        r = int(r)
+        if r < -a.dim() or r >= a.dim() or r % a.dim() == lon:
+            raise ValueError('zonal_spectrum: reduced axis %d is out of range or the longitude axis' % r)
+        r %= a.dim()
+        red.add(r if r < lon else r - 1)                # its place among the leading axes
+    strides = [tuple(int(s) for s in t.stride()[:-1]) for t in ops]
+    if b is None:
+        strides.append((0,) * nd)
+    w = None
+    if weights is not None:
+        require_device(weights, 'zonal_spectrum')
+        if weights.dtype != torch.float32 or weights.device != a.device:
+            raise TypeError('zonal_spectrum: the weights must be a float32 tensor on the device of the data')
+        w = weights
+        if w.dim() > nd or any(int(e) not in (1, lead[nd - w.dim() + i]) for i, e in enumerate(w.shape)):
+            raise ValueError('zonal_spectrum: weights %s do not broadcast against the leading shape %s' % (tuple(w.shape), lead))
+        strides.append((0,) * (nd - w.dim()) + tuple(int(w.stride(i)) if int(w.shape[i]) != 1 else 0 for i in range(w.dim())))
+    else:
+        strides.append((0,) * nd)
+    kept_shape = [lead[i] for i in range(nd) if i not in red]
+    out = torch.empty(([] if b is None else [4]) + kept_shape + [K], dtype=torch.float32, device=a.device)
+    cnt = torch.empty(kept_shape, dtype=torch.int32, device=a.device) if counts else None
+    if out.numel():
+        d = spectrum_desc(L, spectrum_dims(lead, strides, red), n_wave, remove_mean)
+        spectrum_launch(d, ops[0], ops[1] if b is not None else None, w, out, cnt)
+    return (out, cnt) if counts else out
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
 # Climatologies (DLWP/verify.py): grouped mean over rows and indexed row gather, include/dlwpcs.h dlwpcs_rows_desc
 # ------------------------------------------------------------------------------------------------------------------ #
 

@@ -635,6 +635,44 @@ int dlwpcs_sparse_map_apply_masked(const dlwpcs_sparse_map_desc *d, const int32_
 int dlwpcs_missing_count(const void *x, int dtype, int64_t n_planes, int64_t plane, int32_t *count, dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Zonal power spectra and cross-spectra (DLWP/verify.py zonal_spectrum, zonal_cross_spectrum, zonal_coherence): a score that
+ * depends on scale.  For a real row x[0..L-1] along longitude (unit stride),
+ *   X_k = sum_j x_j exp(-2 pi i jk / L),  P_k = c_k |X_k|^2 / L^2,  c_k = 1 for k = 0 and for k = L/2 when L is even, else 2,
+ * for k < K = n_wave (0: all L/2 + 1, where sum_k P_k = mean_j x_j^2).  The leading axes arrive as n_dims merged dims with an
+ * extent, an element stride per operand (0: a, 1: b, 2: w; 0 = broadcast) and a flag: kept dims index the GROUPS (row-major
+ * in the order given), the others the rows of a group, over which the result is the weighted mean
+ *   sum w P_k / sum w   over the rows that COUNT: rows whose L values are all finite (pair form: in a and in b).
+ * Unlike dlwpcs_missing_count an infinity makes a row missing too: it has no finite transform.  skipped (may be NULL) receives the
+ * number of rows of every group that did not count.  A group without a counted row, or with sum w == 0, gives NaN.  w NULL: unit
+ * weights; the weights are expected to be finite.  remove_mean: the row's mean (fp64 sum, rounded to fp32) is subtracted before
+ * the transform and P_0 is reported as the fp64 mean squared -- the error of the other wavenumbers then scales with the
+ * anomaly's variance instead of the offset's square.
+ *   b == NULL: out (groups, K) fp32.    b != NULL, the pair form: out (4, groups, K) = P_aa, P_bb, the co-spectrum
+ *   c_k Re(A_k conj B_k) / L^2 and the quadrature spectrum c_k Im(A_k conj B_k) / L^2; out[0] has the bits of the single form on a.
+ * The transform runs as an exact-fp32 matrix product with twiddles read from `twiddle`: 2 L floats, {cos, -sin}(2 pi m / L) for
+ * m < L interleaved, each evaluated in fp64 and rounded once (the caller makes it once per L; 8-byte aligned).  The rows' terms
+ * are added one by one in row order in fp64; a row that does not count adds nothing.  Few groups of very many rows are cut into
+ * slabs (then scratch >= dlwpcs_zonal_spectrum_scratch_bytes(d) bytes, 8-byte aligned, holds one fp64 partial per slab and a
+ * second launch adds them in order); otherwise the scratch size is 0 and one launch does everything.  At most two launches, no
+ * atomics, bitwise repeatable, no host synchronisation, no allocation.  2 <= L <= 1728 (DLWPCS_E_UNSUPPORTED beyond);
+ * |X_k|^2 must stay below the fp32 range.  a, b and w need the alignment of their elements only; 16-byte loads are used when
+ * L % 4 == 0, every stride of a and b is a multiple of 4 and both pointers are 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct dlwpcs_zonal_spectrum_desc {
+    int32_t L;                   /* longitudes per row */
+    int32_t n_wave;              /* wavenumbers served, 1 .. L/2 + 1; 0: all */
+    int32_t n_dims;              /* leading dims, at most DLWPCS_SCORE_MAX_DIMS */
+    int32_t remove_mean;
+    int64_t ext[DLWPCS_SCORE_MAX_DIMS];
+    int32_t kept[DLWPCS_SCORE_MAX_DIMS];          /* 1: indexes the groups, 0: averaged */
+    int64_t stride[3][DLWPCS_SCORE_MAX_DIMS];     /* elements: a, b, w */
+} dlwpcs_zonal_spectrum_desc;
+size_t dlwpcs_zonal_spectrum_scratch_bytes(const dlwpcs_zonal_spectrum_desc *d);
+int dlwpcs_zonal_spectrum(const dlwpcs_zonal_spectrum_desc *d, const float *a, const float *b /* NULL: single form */,
+                          const float *w /* NULL: unit weights */, const float *twiddle, void *scratch, float *out,
+                          int32_t *skipped /* may be NULL */, dlwpcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Conservative offline maps made on the device (DLWP/remap/overlap.py is the host twin and states the maths): A[r, c], the
  * area in steradians of (lat-lon cell r) intersected with (equiangular cubed-sphere cell c), in closed form and fp64, in CSR
  * form over the lat-lon cells (lat-major).  The cube is given by its face frames {e0, eu, ev} (centre, width and height
