@@ -227,6 +227,7 @@ PROTOTYPES = {
     'dlwpcs_score': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'dlwpcs_score_indexed': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int,
                                      c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_score_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p]),
     'dlwpcs_group_mean_scratch_bytes': (c_size_t, [c_void_p, c_int, ctypes.c_int64, c_int]),
     'dlwpcs_group_mean': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_void_p, c_void_p,
                                   c_void_p, c_size_t, c_void_p]),

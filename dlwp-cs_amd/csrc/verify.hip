@@ -494,20 +494,41 @@ void launch(const Plan &P, const float *a, const float *b, const float *c, const
                            P.G.kc, P.G.slabs, P.G.out_f32, out);
 }
 
-// the entry points' common tail: operand checks, load widths from the pointers, launch
-template <bool IDX>
-int run(const dlwpcs_score_desc *d, Plan &P, const float *a, const float *b, const float *c, const float *w, void *out,
-        int out_f32, void *scratch, size_t scratch_bytes, const int32_t *row_tab, dlwpcs_stream_t stream) {
-    if (!out || !b || (d->method != DLWPCS_SCORE_MEAN && !a)) return fail(DLWPCS_E_INVALID, "score: null operand");
-    const size_t need = P.G.slabs > 1 ? (size_t)(P.groups * P.G.slabs * P.G.kc * SC_NM) * sizeof(double) : 0;
-    if (need && (!scratch || scratch_bytes < need))
-        return fail(DLWPCS_E_INVALID, "score: scratch of %zu bytes, need %zu", scratch_bytes, need);
+// the entry points' common head: the indexed form's own refusals, then the plan of the shapes and strides
+int plan_of(const dlwpcs_score_desc *d, Plan &P, bool indexed, int64_t table_row_stride) {
+    if (!indexed) return make_plan(d, P);
+    if (!d) return fail(DLWPCS_E_INVALID, "score: null descriptor");
+    if (d->method == DLWPCS_SCORE_MEAN) return fail(DLWPCS_E_INVALID, "score_indexed: the mean has no indexed operand");
+    const int indexed_op = idx_operand(d->method);
+    if ((d->lead_stride[indexed_op] != 0 || d->t_stride[indexed_op] != 0))
+        return fail(DLWPCS_E_INVALID, "score_indexed: the indexed operand's lead and time strides must be 0");
+    return make_plan(d, P, indexed_op, table_row_stride);
+}
+
+// what the operand pointers settle (NULL and alignment only, nothing is read): required operands, the mean's a, the load
+// widths, which of c / w exist.  run() launches exactly what this leaves in P; dlwpcs_score_plan_info reports it.
+int settle(const dlwpcs_score_desc *d, Plan &P, const float *&a, const float *b, const float *c, const float *w) {
+    if (!b || (d->method != DLWPCS_SCORE_MEAN && !a)) return fail(DLWPCS_E_INVALID, "score: null operand");
+    if (P.G.idx_op >= 0 && !(P.G.idx_op == 0 ? a : c)) return fail(DLWPCS_E_INVALID, "score_indexed: null table");
     if (d->method == DLWPCS_SCORE_MEAN) a = b;
     if (P.vec && ((((uintptr_t)a) & 15) || (((uintptr_t)b) & 15))) P.vec = false;
     if (P.G.cmode == AUX_VEC && (((uintptr_t)c) & 15)) P.G.cmode = AUX_ELEM;
     if (P.G.wmode == AUX_VEC && (((uintptr_t)w) & 15)) P.G.wmode = AUX_ELEM;
     P.G.has_c = c != nullptr;
     P.G.has_w = w != nullptr;
+    return DLWPCS_OK;
+}
+
+// the entry points' common tail: settle the operands, check the scratch, launch
+template <bool IDX>
+int run(const dlwpcs_score_desc *d, Plan &P, const float *a, const float *b, const float *c, const float *w, void *out,
+        int out_f32, void *scratch, size_t scratch_bytes, const int32_t *row_tab, dlwpcs_stream_t stream) {
+    if (!out) return fail(DLWPCS_E_INVALID, "score: null operand");
+    const int rc = settle(d, P, a, b, c, w);
+    if (rc != DLWPCS_OK) return rc;
+    const size_t need = P.G.slabs > 1 ? (size_t)(P.groups * P.G.slabs * P.G.kc * SC_NM) * sizeof(double) : 0;
+    if (need && (!scratch || scratch_bytes < need))
+        return fail(DLWPCS_E_INVALID, "score: scratch of %zu bytes, need %zu", scratch_bytes, need);
     P.G.out_f32 = out_f32 != 0;
     if (P.n_out == 0) return DLWPCS_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -540,7 +561,7 @@ extern "C" size_t dlwpcs_score_scratch_bytes(const dlwpcs_score_desc *d) {
 extern "C" int dlwpcs_score(const dlwpcs_score_desc *d, const float *a, const float *b, const float *c, const float *w, void *out,
                             int out_f32, void *scratch, size_t scratch_bytes, dlwpcs_stream_t stream) {
     Plan P;
-    int rc = make_plan(d, P);
+    int rc = plan_of(d, P, false, 0);
     if (rc != DLWPCS_OK) return rc;
     return run<false>(d, P, a, b, c, w, out, out_f32, scratch, scratch_bytes, nullptr, stream);
 }
@@ -548,14 +569,29 @@ extern "C" int dlwpcs_score(const dlwpcs_score_desc *d, const float *a, const fl
 extern "C" int dlwpcs_score_indexed(const dlwpcs_score_desc *d, const float *a, const float *b, const float *c, const float *w,
                                     const int32_t *row_dev, int64_t table_row_stride, void *out, int out_f32,
                                     void *scratch, size_t scratch_bytes, dlwpcs_stream_t stream) {
-    if (!d) return fail(DLWPCS_E_INVALID, "score: null descriptor");
-    if (d->method == DLWPCS_SCORE_MEAN) return fail(DLWPCS_E_INVALID, "score_indexed: the mean has no indexed operand");
-    const int indexed_op = idx_operand(d->method);
-    if ((d->lead_stride[indexed_op] != 0 || d->t_stride[indexed_op] != 0))
-        return fail(DLWPCS_E_INVALID, "score_indexed: the indexed operand's lead and time strides must be 0");
     Plan P;
-    int rc = make_plan(d, P, indexed_op, table_row_stride);
+    int rc = plan_of(d, P, true, table_row_stride);
     if (rc != DLWPCS_OK) return rc;
-    if (!row_dev || !(indexed_op == 0 ? a : c)) return fail(DLWPCS_E_INVALID, "score_indexed: null table");
+    if (!row_dev) return fail(DLWPCS_E_INVALID, "score_indexed: null table");
     return run<true>(d, P, a, b, c, w, out, out_f32, scratch, scratch_bytes, row_dev, stream);
+}
+
+extern "C" int dlwpcs_score_plan_info(const dlwpcs_score_desc *d, const void *a, const void *b, const void *c, const void *w,
+                                      int indexed, int64_t table_row_stride, int32_t info[8]) {
+    if (!info) return fail(DLWPCS_E_INVALID, "score_plan_info: null info");
+    Plan P;
+    int rc = plan_of(d, P, indexed != 0, table_row_stride);
+    if (rc != DLWPCS_OK) return rc;
+    const float *pa = (const float *)a;
+    rc = settle(d, P, pa, (const float *)b, (const float *)c, (const float *)w);
+    if (rc != DLWPCS_OK) return rc;
+    const dim3 grid = grid_of(P.G.nblk);
+    info[0] = P.column ? 2 : P.vec ? 1 : 0;
+    info[1] = P.G.slabs;
+    info[2] = P.G.has_c ? P.G.cmode : -1;
+    info[3] = P.G.has_w ? P.G.wmode : -1;
+    info[4] = (int32_t)grid.x;
+    info[5] = (int32_t)grid.y;
+    info[6] = info[7] = 0;
+    return DLWPCS_OK;
 }

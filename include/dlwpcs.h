@@ -545,6 +545,15 @@ int dlwpcs_score(const dlwpcs_score_desc *d, const float *a, const float *b, con
 int dlwpcs_score_indexed(const dlwpcs_score_desc *d, const float *a, const float *b, const float *c, const float *w,
                          const int32_t *row_dev, int64_t table_row_stride, void *out, int out_f32,
                          void *scratch, size_t scratch_bytes, dlwpcs_stream_t stream);
+/* Which code dlwpcs_score (indexed = 0) or dlwpcs_score_indexed (indexed != 0) would run for these arguments.  Host only: no
+ * launch, no device call; the pointers are looked at for NULL and for 16-byte alignment and never dereferenced.  info[0] = the
+ * kernel form (0: a workgroup per output group, one element per lane and load; 1: the same with 16-byte loads of a and b; 2: one
+ * lane per output), info[1] = slabs per group (> 1: partial sums in scratch and a second launch), info[2] / info[3] = how the
+ * 16-byte form reads c / w (-1: operand absent, 0: element by element, 1: 16-byte loads, 2: one load per cell of 4 channels),
+ * info[4] / info[5] = the grid of the first launch, info[6] = info[7] = 0.  Returns what the entry point would return for the
+ * same descriptor and operands. */
+int dlwpcs_score_plan_info(const dlwpcs_score_desc *d, const void *a, const void *b, const void *c, const void *w,
+                           int indexed, int64_t table_row_stride, int32_t info[8]);
 
 /* ------------------------------------------------------------------------------------------------------------- *
  * Climatologies (reference DLWP/verify.py:167-214 monthly_climo_error, :426-456 daily_climatology / daily_climo_time_series).
