@@ -28,6 +28,7 @@ ADAM_ZERO_GRAD = 1
 HEAD_DEFER_STAGE2 = 2
 LOSS_MSE, LOSS_MAE, LOSS_ACC = 0, 1, 2
 REG_NONE, REG_MSE, REG_MAE, REG_GLOBAL = 0, 1, 2, 3
+NORM_ALL, NORM_VALID = 0, 1             # dlwpcs_loss_masked_fwd_bwd: divide by n / by the number of valid elements
 ACT_NONE = 0
 ACT_LEAKY_CLIP = 1
 CONV_ACCUMULATE_WGRAD = 1
@@ -221,6 +222,8 @@ PROTOTYPES = {
                                    c_void_p]),
     'dlwpcs_loss_scratch_bytes': (c_size_t, []),
     'dlwpcs_loss_fwd_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
+    'dlwpcs_loss_masked_fwd_bwd': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
+                                           c_void_p, c_void_p]),
     'dlwpcs_head_loss_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int, c_float, c_float, c_void_p]),
     'dlwpcs_score_scratch_bytes': (c_size_t, [c_void_p]),
@@ -236,6 +239,7 @@ PROTOTYPES = {
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),
     'dlwpcs_missing_count': (c_int, [c_void_p, c_int, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p]),
+    'dlwpcs_fill_missing': (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_int, c_int, c_void_p]),
     'dlwpcs_zonal_spectrum_scratch_bytes': (c_size_t, [c_void_p]),
     'dlwpcs_zonal_spectrum': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_count': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -11,7 +11,8 @@ reference module `DLWP/custom.py`, dispatching to hand-written HIP kernels (libd
 
 plus the training callbacks the reference scripts pass to `fit` (reference DLWP/custom.py:33-208), re-hosted on the
 TF-free shim in `DLWP.keras`, and the training losses latitude_weighted_loss / anomaly_correlation(_loss) (reference
-DLWP/custom.py:1543-1676), which Model.compile runs as HIP kernels.
+DLWP/custom.py:1543-1676), which Model.compile runs as HIP kernels, and masked_loss, which lets either of 'mse' / 'mae' ignore
+NaN targets.
 """
 
 import numpy as np
@@ -608,3 +609,65 @@ def anomaly_correlation_loss(mean=None, regularize_mean='mse', reverse=True):
 
     acc_loss._dlwpcs_loss = LossSpec('acc', None, mean, regularize_mean, bool(reverse))
     return acc_loss
+
+
+# ==================================================================================================================== #
+# Losses for targets with holes (no counterpart in the reference)
+# ==================================================================================================================== #
+
+def _inner_of_masked(loss_function):
+    """the LossSpec masked_loss wraps: 'mse' / 'mae' by name or function, or a latitude_weighted_loss of either"""
+    inner = spec_of(loss_function)
+    if inner is not None and inner.kind == 'acc':
+        raise NotImplementedError('masked_loss: a masked anomaly-correlation loss is not built (its sums run over the whole '
+                                  'batch: a hole would have to leave all of them)')
+    if inner is None or inner.kind not in ('mse', 'mae') or inner.masked is not None:
+        raise ValueError("masked_loss wraps 'mse' / 'mae' (DLWP.keras.losses, by name or function) or a latitude_weighted_loss "
+                         "of either, got %r" % (loss_function,))
+    return inner
+
+
+def masked_loss(loss_function=mean_squared_error, normalize='valid'):
+    """
+    Create a loss function that ignores the elements whose TARGET is NaN (a field with holes: sea-surface temperature over
+    land).  An element is a hole iff y_true is NaN there; y_pred is never inspected, and at a hole it contributes nothing --
+    neither to the loss nor to the gradient (which is 0 there), whatever its value.  +-inf targets are data.
+
+    :param loss_function: 'mse' / 'mae', mean_squared_error / mean_absolute_error (DLWP.keras.losses), or the result of
+        latitude_weighted_loss(...) of either
+    :param normalize: 'valid' (default): the sum of the terms divided by the number of valid elements of the batch (a nan-mean;
+        0 when nothing is valid); 'all': divided by the number of all elements, i.e. a hole counts as a perfect prediction.
+        The weighted forms divide by the same number (the weight field has mean 1).  'all' is exact under data-parallel
+        averaging; 'valid' is refused there (per-rank nan-means averaged over ranks are a different loss).
+    :return: callable loss function `masked_loss`.  On host arrays (numpy or torch) it returns an array of y_pred's shape
+        without the last axis whose plain mean is the loss, so that keras' reduction over the rest gives the value.
+    """
+    if normalize not in ('all', 'valid'):
+        raise ValueError("'normalize' must be one of 'all' or 'valid'")
+    inner = _inner_of_masked(loss_function)
+    weights = inner.weights
+
+    def masked_loss(y_true, y_pred):
+        hole = y_true != y_true
+        if hasattr(y_pred, 'detach'):
+            import torch
+            d = torch.where(hole, torch.zeros_like(y_pred), y_pred - y_true)      # (a select: a NaN y_pred at a hole is dropped)
+        else:
+            d = np.where(hole, 0., y_pred - y_true)
+        if weights is not None:
+            d = d * _xp_like(weights, y_pred)
+        term = d * d if inner.kind == 'mse' else _abs(d)
+        rows = term.sum(-1)
+        if normalize == 'all':
+            return rows / y_pred.shape[-1]
+        count = (~hole).sum()
+        n_rows = max(int(np.prod(tuple(rows.shape))), 1)
+        if int(count) == 0:
+            return rows * 0
+        if hasattr(count, 'detach'):
+            return rows * (n_rows / count.to(rows.dtype))       # (an integer tensor would divide in float32)
+        return rows * rows.dtype.type(n_rows / float(count))
+
+    masked_loss._dlwpcs_loss = inner._replace(masked=normalize)
+    masked_loss.normalize = normalize
+    return masked_loss

@@ -51,9 +51,10 @@ def get(identifier):
 
 # ---- what the engine runs for a loss (DLWP.keras.Model.compile) ---------------------------------------------------------
 # kind 'mse' / 'mae' / 'acc'; weights: the latitude weight field of DLWP.custom.latitude_weighted_loss (or None); clim: the
-# climatology of DLWP.custom.anomaly_correlation_loss, shape (1, ...) (or None); regularize / reverse: the anomaly-correlation options
-LossSpec = collections.namedtuple('LossSpec', ['kind', 'weights', 'clim', 'regularize', 'reverse'],
-                                  defaults=(None, None, None, True))
+# climatology of DLWP.custom.anomaly_correlation_loss, shape (1, ...) (or None); regularize / reverse: the anomaly-correlation options;
+# masked: None, or the normalisation of DLWP.custom.masked_loss ('all' / 'valid': NaN targets are holes)
+LossSpec = collections.namedtuple('LossSpec', ['kind', 'weights', 'clim', 'regularize', 'reverse', 'masked'],
+                                  defaults=(None, None, None, True, None))
 
 
 def spec_of(loss):

@@ -617,7 +617,7 @@ class Model(object):
                                           "DLWP.keras.losses.mean_absolute_error" % (l,))
             if sp is None:
                 raise NotImplementedError("loss %r: the DLWP-CS engine provides 'mse', 'mae' (DLWP.keras.losses) and the "
-                                          "losses of DLWP.custom: latitude_weighted_loss, anomaly_correlation(_loss)" % (l,))
+                                          "losses of DLWP.custom: latitude_weighted_loss, anomaly_correlation(_loss), masked_loss" % (l,))
             if sp.regularize == 'spatial':
                 raise NotImplementedError("anomaly-correlation regularize_mean='spatial': a per-sample reduction over the layout's "
                                           "last two axes (reference DLWP/custom.py:1604-1606,1657-1659) the DLWP-CS engine does "
@@ -625,6 +625,11 @@ class Model(object):
             if sp.kind == 'acc' and parallel.world()[1] > 1:
                 raise NotImplementedError('the anomaly-correlation loss is a ratio of sums over the WHOLE batch: per-rank values '
                                           'averaged across %d data-parallel ranks are a different loss (train it on one rank)'
+                                          % parallel.world()[1])
+            if sp.masked == 'valid' and parallel.world()[1] > 1:
+                raise NotImplementedError("masked_loss(normalize='valid') divides by the number of valid elements of the WHOLE "
+                                          "batch: per-rank nan-means averaged across %d data-parallel ranks are a different loss "
+                                          "(train it on one rank, or use normalize='all', which is exact under averaging)"
                                           % parallel.world()[1])
             specs.append(sp)
         self.loss = loss
@@ -643,7 +648,7 @@ class Model(object):
         self._flatten_parameters()
         # loss fields (latitude weights, climatology) on the model's device, once; plain 'mse' keeps its own kernels
         dev = self._flat_params.device if self._flat_params is not None else torch.device('cpu')
-        self._dev_losses = [None if (sp.kind == 'mse' and sp.weights is None) else
+        self._dev_losses = [None if (sp.kind == 'mse' and sp.weights is None and sp.masked is None) else
                             ops.DeviceLoss(sp, tuple(o.shape[1:]), self._cf_model, dev)
                             for sp, o in zip(specs, self.outputs)]
         self._graphs.clear()

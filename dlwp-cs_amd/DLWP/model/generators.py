@@ -66,7 +66,7 @@ class ArrayDataGenerator(object):
     def __init__(self, model, array, rank=2, batch_size=32, input_slice=None, output_slice=None,
                  input_time_steps=1, output_time_steps=1, sequence=None, interval=1,
                  shuffle=False, remove_nan=True, insolation_array=None, constants=None, channels_last=False,
-                 drop_remainder=False, device=None, dtype=None):
+                 drop_remainder=False, device=None, dtype=None, fill_inputs=None):
         """
         :param model: DLWP model instance (metadata only: is_convolutional, is_recurrent, impute)
         :param array: ndarray (time, variable, *space), or a DLWP.model.PackedSeries of that shape: the series as int16
@@ -82,6 +82,11 @@ class ArrayDataGenerator(object):
             batches with the gather kernel (convolutional, non-recurrent models)
         :param dtype: 'float32' | 'bfloat16' | None: dtype of the device PREDICTORS (None: the engine's compute dtype when
             the generator is created); targets are always float32 (the loss is computed in fp32)
+        :param fill_inputs: None, or the value that replaces the NaNs of the PREDICTORS' data channels: one float, or one per
+            input variable (repeated over the input time steps).  The insolation channels are left alone and targets are never
+            filled (DLWP.custom.masked_loss ignores their holes).  On the device it is one `dlwpcs_fill_missing` launch behind
+            the predictor gather, on the host np.where with the same rounding: the batches are equal bit for bit.  Not
+            together with `remove_nan`: the two answer the same question differently
         (all other parameters: see the reference class)
         """
         for name, v in (('rank', rank), ('input_time_steps', input_time_steps), ('output_time_steps', output_time_steps),
@@ -110,6 +115,15 @@ class ArrayDataGenerator(object):
         self._output_time_steps = int(output_time_steps)
         self._interval = int(interval)
         self.drop_remainder = to_bool(drop_remainder)
+        self._fill_inputs = None
+        if fill_inputs is not None:
+            if remove_nan:
+                raise ValueError('fill_inputs and remove_nan answer the same question differently: pass remove_nan=False to '
+                                 'fill the missing predictors')
+            f = np.asarray(fill_inputs, dtype=np.float32).reshape(-1)
+            if f.size not in (1, self._input_size):
+                raise ValueError('fill_inputs: one value or one per input variable (%d), got %d' % (self._input_size, f.size))
+            self._fill_inputs = np.ascontiguousarray(np.broadcast_to(f, (self._input_size,)))
         self.on_epoch_end()
 
         self.insolation_array = insolation_array
@@ -269,6 +283,9 @@ class ArrayDataGenerator(object):
             return np.stack([np.asarray(source[samples + t_off + k * iv])[:, var] for k in range(steps)], axis=1)
 
         p = window(arr, vin, 0, its)
+        if self._fill_inputs is not None:
+            fill = self._fill_inputs.reshape((1, 1, -1) + (1,) * len(space)).astype(p.dtype)
+            p = np.where(np.isnan(p), fill, p)
         solar = []
         if self._add_insolation:
             seq = self._sequence if self._sequence is not None else 1
@@ -331,6 +348,11 @@ class ArrayDataGenerator(object):
              'vout': torch.from_numpy(self._output_vars.astype(np.int32)).to(dev),
              'zero': torch.zeros(1, dtype=torch.int32, device=dev), 'ops': ops, 'torch': torch,
              'pdtype': backend.torch_dtype(dtype)}
+        if self._fill_inputs is not None:
+            # one value per predictor channel (time-major: channel = t * (V_in + insolation) + v).  The fill runs between the data
+            # gather and the insolation's, so an insolation channel is overwritten afterwards whatever its entry says
+            row = np.concatenate([self._fill_inputs, np.zeros(self._add_insolation, dtype=np.float32)])
+            d['fill'] = torch.from_numpy(np.tile(row, self._input_time_steps)).to(dev)
         if self._remove_nan == 'device':
             # one counting pass over what is resident, (T, V) counts downloaded once, one flag per sample on the host
             self.missing_counts = ops.missing_counts(d['array']).cpu().numpy()
@@ -435,6 +457,8 @@ class ArrayDataGenerator(object):
                 ops.solar_fill(d['sol_row'], d['sol_cell'], rows, out, n_steps, 0, t_stride, c_off, c_stride, cl)
         p = empty(cin, d['pdtype'])
         gather(d['array'], smp, d['vin'], p, its, 0, iv, 0, vin_n + add, cl)
+        if n and 'fill' in d:
+            ops.fill_missing(p, d['fill'], cl)
         if add:
             solar(smp, p, its, iv, vin_n, vin_n + add)
         targets = []

@@ -1263,6 +1263,7 @@ def mse_mae(y, t, weight=1.0):
 # ---- the other training losses (DLWP.keras.losses / DLWP.custom: 'mae', latitude-weighted, anomaly correlation) ----------
 _KINDS = {'mse': nat.LOSS_MSE, 'mae': nat.LOSS_MAE, 'acc': nat.LOSS_ACC}
 _REGS = {None: nat.REG_NONE, 'mse': nat.REG_MSE, 'mae': nat.REG_MAE, 'global': nat.REG_GLOBAL}
+_NORMS = {'all': nat.NORM_ALL, 'valid': nat.NORM_VALID}
 
 
 def _loss_field(a, sample_shape, channels_first, what):
@@ -1295,7 +1296,13 @@ class DeviceLoss(object):
             raise NotImplementedError("anomaly-correlation regularize_mean=%r: the DLWP-CS engine builds None / 'mse' / 'mae' / "
                                       "'global' ('spatial' averages over the layout's last two axes per sample: reference "
                                       "DLWP/custom.py:1604-1606,1657-1659)" % (spec.regularize,))
+        masked = getattr(spec, 'masked', None)
+        if masked is not None and masked not in _NORMS:
+            raise ValueError("masked loss: normalize must be 'all' or 'valid', got %r" % (masked,))
+        if masked is not None and spec.kind == 'acc':
+            raise NotImplementedError('a masked anomaly-correlation loss is not built')
         self.spec = spec
+        self.masked = masked            # None, 'all' or 'valid': NaN targets are holes (dlwpcs_loss_masked_fwd_bwd)
         self.kind, self.reg, self.reverse = _KINDS[spec.kind], _REGS[spec.regularize], bool(spec.reverse)
         self.w = self.c = None
         self.wdiv = self.wper = self.cdiv = self.cper = 0
@@ -1316,8 +1323,9 @@ class DeviceLoss(object):
         return L
 
     def fused_ok(self, cout, cells):
-        """Does the fused head (dlwpcs_head_loss_step) serve it: 'mse' / 'mae' with no weight or a per-cell one."""
-        return (self.kind in (nat.LOSS_MSE, nat.LOSS_MAE) and self.c is None
+        """Does the fused head (dlwpcs_head_loss_step) serve it: 'mse' / 'mae' with no weight or a per-cell one, not masked
+        (a masked loss runs as pw_fwd -> dlwpcs_loss_masked_fwd_bwd -> pw_dgrad, like the anomaly correlation)."""
+        return (self.masked is None and self.kind in (nat.LOSS_MSE, nat.LOSS_MAE) and self.c is None
                 and (self.w is None or (self.wdiv == cout and self.wper == cells)))
 
 
@@ -1325,7 +1333,8 @@ _loss_scratch = {}
 
 
 class _Loss(torch.autograd.Function):
-    """returns a (2,) tensor: [loss_weight * loss, mae] (dlwpcs_loss_fwd_bwd); gradient flows through element 0 only."""
+    """returns a (2,) tensor: [loss_weight * loss, mae] (dlwpcs_loss_fwd_bwd, or dlwpcs_loss_masked_fwd_bwd for a masked
+    DeviceLoss); gradient flows through element 0 only."""
 
     @staticmethod
     def forward(ctx, y, t, dl, weight):
@@ -1354,8 +1363,12 @@ class _Loss(torch.autograd.Function):
         out = torch.empty(2, dtype=torch.float32, device=y.device)
         dy = torch.empty_like(y) if ctx.needs_input_grad[0] else None
         L = dl.desc(weight, 1)
-        check(lib().dlwpcs_loss_fwd_bwd(ctypes.byref(L), ptr(y), ptr(t), ptr(dy), ptr(out), y.numel(), tag, ptr(scratch),
-                                        stream_ptr()), 'dlwpcs_loss_fwd_bwd')
+        if dl.masked is not None:
+            check(lib().dlwpcs_loss_masked_fwd_bwd(ctypes.byref(L), ptr(y), ptr(t), _NORMS[dl.masked], ptr(dy), ptr(out), None,
+                                                   y.numel(), tag, ptr(scratch), stream_ptr()), 'dlwpcs_loss_masked_fwd_bwd')
+        else:
+            check(lib().dlwpcs_loss_fwd_bwd(ctypes.byref(L), ptr(y), ptr(t), ptr(dy), ptr(out), y.numel(), tag, ptr(scratch),
+                                            stream_ptr()), 'dlwpcs_loss_fwd_bwd')
         ctx.save_for_backward(dy)
         return out
 
@@ -1673,6 +1686,38 @@ def missing_counts(array):
         check(lib().dlwpcs_missing_count(ptr(q), nat.I16 if q.dtype == torch.int16 else nat.F32, T * V, S, ptr(count), stream_ptr()),
               'dlwpcs_missing_count')
     return count
+
+
+def fill_missing(x, fill, channels_last=True):
+    """
+    Replace the NaNs of the batch x in place (dlwpcs_fill_missing; one launch on the current stream, no host synchronisation) and
+    return x: a contiguous float32 or bfloat16 device tensor (n, ..., C) (channels_last) or (n, C, ...).  fill: one value, or one
+    per channel -- a sequence, or a float32 device tensor of C values (made once by a caller that fills every batch); a bfloat16
+    element receives the value rounded to nearest even.  Every element that is not NaN keeps its bits.
+    """
+    require_device(x, 'fill_missing')
+    if x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous() or x.dim() < 2:
+        raise TypeError('fill_missing: a contiguous float32 / bfloat16 batch (n, ..., C) or (n, C, ...), got %s %s'
+                        % (x.dtype, tuple(x.shape)))
+    C = int(x.shape[-1] if channels_last else x.shape[1])
+    if isinstance(fill, torch.Tensor):
+        if fill.dtype != torch.float32 or fill.device != x.device or not fill.is_contiguous():
+            raise TypeError('fill_missing: the fill table must be a contiguous float32 tensor on %s' % (x.device,))
+        f = fill.reshape(-1)
+    else:
+        f = torch.as_tensor(np.asarray(fill, dtype=np.float32).reshape(-1), device=x.device)
+    if f.numel() == 1:
+        div, period = 1, 1
+    elif f.numel() == C:
+        # channels_last: the channel is the fastest index; channels_first: one channel spans the sample's space
+        div, period = (1, C) if channels_last else (int(x[0, 0].numel()), C)
+    else:
+        raise ValueError('fill_missing: %d fill values for %d channels' % (f.numel(), C))
+    if x.numel():
+        with torch.cuda.device(x.device):
+            check(lib().dlwpcs_fill_missing(ptr(x), nat.dtype_tag(x), x.numel(), ptr(f), div, period, stream_ptr()),
+                  'dlwpcs_fill_missing')
+    return x
 
 
 def solar_fill(row_tab, cell_tab, samples, out, n_steps, t_off, t_stride, c_off, c_stride, channels_last=True):

@@ -7,7 +7,7 @@
 // may start anywhere, so each plane is cut at the 16-byte lines of the ADDRESS: up to 16 B / element - 1 head elements and as
 // many tail elements are read one by one (one lane each), everything between as 16-byte vectors, MC_UNROLL of them in flight per
 // lane.  A lane's count goes over the wave by shuffles, over the four waves through LDS, in a fixed order (integer sums: the
-// order changes no bit anyway).
+// order changes no bit anyway).  dlwpcs_fill_missing (below) cuts its array the same way.
 #include "common.h"
 
 namespace dlwpcs {
@@ -74,6 +74,85 @@ __global__ void __launch_bounds__(MC_THREADS) missing_count_kernel(const T *__re
     }
 }
 
+// ---- dlwpcs_fill_missing: x[e] = fill[(e / div) % per] where x[e] is NaN, in place ----------------------------------------
+// The same cut at the 16-byte lines of the address: head and tail elements one lane each (workgroup 0), everything between as
+// 16-byte vectors, MC_UNROLL loads in flight per lane, every vector stored back (an element that is not NaN with its own bits).  The
+// field index of a vector's first element is divided once and stepped along the vector (n < 2^32).
+constexpr int FM_MAX_GRID = 2048;
+
+struct FillIdx {
+    uint32_t div, per, q, r;
+    __device__ __forceinline__ FillIdx(uint32_t e, uint32_t d, uint32_t p) : div(d), per(p) {
+        const uint32_t c = e / d;
+        q = c % p; r = e - c * d;
+    }
+    __device__ __forceinline__ void step() { if (++r == div) { r = 0; if (++q == per) q = 0; } }
+};
+
+__device__ __forceinline__ uint32_t fill_f32(uint32_t u, float f) { return is_nan_bits(u) ? __float_as_uint(f) : u; }
+__device__ __forceinline__ uint32_t fill_bf16(uint32_t h, float f) { return (h & 0x7fffu) > 0x7f80u ? (uint32_t)f2bf(f) : h; }
+
+template <typename T> __device__ __forceinline__ void fill_elem(T *p, uint32_t e, const float *fill, uint32_t div, uint32_t per);
+template <> __device__ __forceinline__ void fill_elem<float>(float *p, uint32_t e, const float *fill, uint32_t div, uint32_t per) {
+    const uint32_t u = __float_as_uint(*p);
+    if (is_nan_bits(u)) *p = fill[(e / div) % per];
+}
+template <> __device__ __forceinline__ void fill_elem<bf16_t>(bf16_t *p, uint32_t e, const float *fill, uint32_t div, uint32_t per) {
+    if ((*p & 0x7fffu) > 0x7f80u) *p = f2bf(fill[(e / div) % per]);
+}
+
+template <typename T> __device__ __forceinline__ uint32_t fill_word(uint32_t w, const float *fill, FillIdx &ix);
+template <> __device__ __forceinline__ uint32_t fill_word<float>(uint32_t w, const float *fill, FillIdx &ix) {
+    const uint32_t o = fill_f32(w, fill[ix.q]);
+    ix.step();
+    return o;
+}
+template <> __device__ __forceinline__ uint32_t fill_word<bf16_t>(uint32_t w, const float *fill, FillIdx &ix) {
+    const uint32_t lo = fill_bf16(w & 0xffffu, fill[ix.q]);
+    ix.step();
+    const uint32_t hi = fill_bf16(w >> 16, fill[ix.q]);
+    ix.step();
+    return lo | (hi << 16);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(MC_THREADS) fill_missing_kernel(T *__restrict__ x, uint32_t n, const float *__restrict__ fill,
+                                                                  uint32_t div, uint32_t per) {
+    constexpr uint32_t VE = 16 / (uint32_t)sizeof(T);
+    uint32_t head = ((16u - (uint32_t)((uintptr_t)x & 15u)) & 15u) / (uint32_t)sizeof(T);
+    if (head > n) head = n;
+    const uint32_t nvec = (n - head) / VE;
+    const uint32_t tail0 = head + nvec * VE;
+    const uint32_t tid = threadIdx.x;
+    if (blockIdx.x == 0) {
+        if (tid < head) fill_elem<T>(x + tid, tid, fill, div, per);
+        if (tail0 + tid < n) fill_elem<T>(x + tail0 + tid, tail0 + tid, fill, div, per);      // (no wrap: n < 2^32 - 256, host)
+    }
+    uint4 *v = reinterpret_cast<uint4 *>(x + head);
+    // a lane's MC_UNROLL vectors of one sweep lie a whole grid apart: a launch of fewer than MC_UNROLL grids of vectors still
+    // spreads over every workgroup (one vector per lane), a large one keeps MC_UNROLL loads in flight per lane
+    const uint64_t lanes = (uint64_t)gridDim.x * MC_THREADS;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * MC_THREADS + tid; i0 < nvec; i0 += lanes * MC_UNROLL) {
+        uint4 w[MC_UNROLL];
+#pragma unroll
+        for (int u = 0; u < MC_UNROLL; ++u) {
+            const uint64_t iu = i0 + (uint64_t)u * lanes;
+            if (iu < nvec) w[u] = v[iu];
+        }
+#pragma unroll
+        for (int u = 0; u < MC_UNROLL; ++u) {
+            const uint64_t iu = i0 + (uint64_t)u * lanes;
+            if (iu < nvec) {
+                FillIdx ix(head + (uint32_t)iu * VE, div, per);
+                uint4 o;
+                o.x = fill_word<T>(w[u].x, fill, ix); o.y = fill_word<T>(w[u].y, fill, ix);
+                o.z = fill_word<T>(w[u].z, fill, ix); o.w = fill_word<T>(w[u].w, fill, ix);
+                v[iu] = o;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 }  // namespace dlwpcs
@@ -99,4 +178,27 @@ extern "C" int dlwpcs_missing_count(const void *x, int dtype, int64_t n_planes, 
     else
         hipLaunchKernelGGL(missing_count_kernel<float>, grid, blk, 0, s, (const float *)x, n_planes, plane, count);
     return check_launch("missing_count");
+}
+
+extern "C" int dlwpcs_fill_missing(void *x, int dtype, size_t n, const float *fill, int fill_div, int fill_period,
+                                   dlwpcs_stream_t stream) {
+    if (!dtype_ok(dtype)) return fail(DLWPCS_E_INVALID, "fill_missing: dtype %d is neither DLWPCS_F32 nor DLWPCS_BF16", dtype);
+    if (n >= (1ull << 32) - MC_THREADS) return fail(DLWPCS_E_UNSUPPORTED, "fill_missing: %zu elements (< 2^32 - %d)", n, MC_THREADS);
+    if (fill_div < 1 || fill_period < 1) return fail(DLWPCS_E_INVALID, "fill_missing: the fill field needs div, period >= 1");
+    if (n == 0) return DLWPCS_OK;
+    if (!x || !fill) return fail(DLWPCS_E_INVALID, "fill_missing: null pointer");
+    const size_t esz = dtype_size(dtype);
+    if (((uintptr_t)x) & (esz - 1)) return fail(DLWPCS_E_INVALID, "fill_missing: x is not aligned to its %zu-byte elements", esz);
+    hipStream_t s = (hipStream_t)stream;
+    size_t g = (n * esz / 16 + MC_THREADS - 1) / MC_THREADS;
+    if (g > FM_MAX_GRID) g = FM_MAX_GRID;
+    if (g < 1) g = 1;
+    const dim3 grid((unsigned)g), blk(MC_THREADS);
+    if (dtype == DLWPCS_BF16)
+        hipLaunchKernelGGL(fill_missing_kernel<bf16_t>, grid, blk, 0, s, (bf16_t *)x, (uint32_t)n, fill, (uint32_t)fill_div,
+                           (uint32_t)fill_period);
+    else
+        hipLaunchKernelGGL(fill_missing_kernel<float>, grid, blk, 0, s, (float *)x, (uint32_t)n, fill, (uint32_t)fill_div,
+                           (uint32_t)fill_period);
+    return check_launch("fill_missing");
 }

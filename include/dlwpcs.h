@@ -493,6 +493,37 @@ typedef struct dlwpcs_loss_desc {
 size_t dlwpcs_loss_scratch_bytes(void);
 int dlwpcs_loss_fwd_bwd(const dlwpcs_loss_desc *L, const void *y, const void *t, void *dy, float *loss_out, size_t n,
                         int dtype, void *scratch, dlwpcs_stream_t stream);
+/* Masked losses: dlwpcs_loss_fwd_bwd for targets with holes (DLWPCS_LOSS_MSE / DLWPCS_LOSS_MAE, with or without a weight field).
+ *   hole     element e is a hole iff t[e] != t[e] after widening to fp32: any NaN payload, either sign; +-inf is data (the
+ *            convention of dlwpcs_missing_count).  y is never inspected.
+ *   sums     at a hole d = y - t is replaced by 0 by a SELECT (not a multiplication) before the element's arithmetic, so a NaN
+ *            or inf y[e] at a hole reaches neither sum; everywhere else the arithmetic is dlwpcs_loss_fwd_bwd's.
+ *   dy       at a hole +0.0 is stored (a select again); elsewhere gscale * (the plain gradient term).
+ *   count    the number of non-holes, an exact integer (uint32 per lane, added over the workgroup in a fixed order, one uint32 per
+ *            workgroup in the scratch, added by the second stage).  valid_out[0] = count whenever valid_out is given.
+ *   result   loss_out[0] (+)= loss_weight * S0 / D, loss_out[1] (+)= S1 / D with S0 / S1 the sums of the loss terms / of |d| and
+ *            D = n (DLWPCS_NORM_ALL: a hole contributes 0, as if y == t there) or D = count (DLWPCS_NORM_VALID: a nan-mean).  The
+ *            weighted forms divide by the same D, not by sum w (the reference's weight field has mean 1).
+ *            count == 0: both results are 0 (not NaN) and dy is +0.0 everywhere.
+ * L, dtype (DLWPCS_MSE_TARGET_F32 included), loss_out and L->overwrite bit 0 as for dlwpcs_loss_fwd_bwd; scratch >=
+ * dlwpcs_loss_scratch_bytes(); dy and valid_out may be NULL.  Refused with nothing written: DLWPCS_LOSS_ACC, a climatology, an
+ * unknown `normalize`, n >= 2^32.
+ * Launches (none synchronises with the host, no atomics): the first stage has dlwpcs_loss_fwd_bwd's geometry -- the 8-wide kernel
+ * when n % 8 == 0 and y, t, dy sit on 32-byte boundaries, min(ceil(items / 256), 1024) workgroups, the same lane -> element map,
+ * fp32 lane sums and workgroup tree -- and the second is one workgroup in fp64.
+ *   NORM_ALL    two launches; gscale = loss_weight * 2 / (float)n (MSE; loss_weight / (float)n for MAE) is formed on the host and
+ *               the first stage writes dy; inv_n = 1.f / (float)n.  Bit for bit dlwpcs_loss_fwd_bwd on copies of y and t with
+ *               zeros written at the holes.
+ *   NORM_VALID  three launches; the first stage writes no dy, the second forms inv = (float)(1.0 / (double)(float)count) and
+ *               gscale = (float)((double)(loss_weight * 2.f) / (double)(float)count) (loss_weight for MAE) in device memory (an
+ *               fp64 quotient of two fp32 values rounded once to fp32 is the correctly rounded fp32 quotient: without holes these
+ *               are the bits the plain call forms on the host, and so are loss_out and dy), and a third launch of at most 2048
+ *               workgroups writes dy. */
+#define DLWPCS_NORM_ALL   0   /* divide by n: a hole contributes 0, as if y == t there */
+#define DLWPCS_NORM_VALID 1   /* divide by the number of valid elements (a nan-mean) */
+int dlwpcs_loss_masked_fwd_bwd(const dlwpcs_loss_desc *L, const void *y, const void *t, int normalize,
+                               void *dy, float *loss_out, uint32_t *valid_out, size_t n, int dtype,
+                               void *scratch, dlwpcs_stream_t stream);
 /* dlwpcs_head_mse_step(_masked) for DLWPCS_LOSS_MSE / DLWPCS_LOSS_MAE with an optional per-cell weight field (weight_div = C_out,
  * weight_period = 6*N*N); mask_dx != 0: the masked form.  The deferred tail is described by dlwpcs_head_mse_tail as before. */
 int dlwpcs_head_loss_step(const dlwpcs_conv_desc *d, const dlwpcs_loss_desc *L, const void *x, const void *wpk_fwd,
@@ -642,6 +673,12 @@ int dlwpcs_sparse_map_apply_masked(const dlwpcs_sparse_map_desc *d, const int32_
  * one workgroup (no atomics: count need not be zeroed).  One launch, no host synchronisation, no allocation. */
 #define DLWPCS_I16 2                  /* dlwpcs_missing_count only: int16 codes */
 int dlwpcs_missing_count(const void *x, int dtype, int64_t n_planes, int64_t plane, int32_t *count, dlwpcs_stream_t stream);
+/* Fill the missing values of x in place (dtype DLWPCS_F32 or DLWPCS_BF16, n < 2^32 elements): x[e] = fill[(e / fill_div) %
+ * fill_period] where x[e] is NaN (any payload, either sign); every other element, -0.0 and +-inf included, keeps its bits.  fill:
+ * fp32 device table of fill_period values; a bf16 element receives the value rounded to nearest even.  x needs the alignment of
+ * its element only.  One streaming launch, no host synchronisation, no allocation. */
+int dlwpcs_fill_missing(void *x, int dtype, size_t n, const float *fill, int fill_div, int fill_period,
+                        dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
  * Zonal power spectra and cross-spectra (DLWP/verify.py zonal_spectrum, zonal_cross_spectrum, zonal_coherence): a score that
