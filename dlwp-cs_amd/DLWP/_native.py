@@ -29,6 +29,7 @@ HEAD_DEFER_STAGE2 = 2
 LOSS_MSE, LOSS_MAE, LOSS_ACC = 0, 1, 2
 REG_NONE, REG_MSE, REG_MAE, REG_GLOBAL = 0, 1, 2, 3
 NORM_ALL, NORM_VALID = 0, 1             # dlwpcs_loss_masked_fwd_bwd: divide by n / by the number of valid elements
+E_UNSUPPORTED = -2
 ACT_NONE = 0
 ACT_LEAKY_CLIP = 1
 CONV_ACCUMULATE_WGRAD = 1
@@ -180,6 +181,10 @@ PROTOTYPES = {
                                                                                       c_void_p, c_size_t, c_void_p]),
     'dlwpcs_conv_bwd_data_masked': (c_int, [ctypes.POINTER(ConvDesc)] + [c_void_p] * 4 + [c_void_p] * 4 + [c_float, c_float] +
                                     [c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_conv_small_fwd': (c_int, [ctypes.POINTER(ConvDesc)] + [c_void_p] * 8 + [c_void_p, c_void_p, c_void_p, c_size_t,
+                                                                                       c_void_p]),
+    'dlwpcs_conv_small_bwd_data': (c_int, [ctypes.POINTER(ConvDesc)] + [c_void_p] * 4 + [c_void_p] * 4 + [c_float, c_float] +
+                                   [c_void_p, c_void_p, c_size_t, c_void_p]),
     'dlwpcs_conv_bwd_weights': (c_int, [ctypes.POINTER(ConvDesc)] + [c_void_p] * 4 + [c_void_p] * 6 +
                                 [c_void_p, c_void_p, c_size_t, c_void_p]),
     'dlwpcs_conv_wgrad_reduce_item': (c_int, [ctypes.POINTER(ConvDesc)] + [c_void_p] * 6 +

@@ -96,6 +96,7 @@ class Model(object):
         self.fuse_head_loss = option('fuse_head')
         # inference: the pointwise output layer inside the epilogue of the convolution in front of it (ops.cs_conv_head)
         self.fold_head = option('fold_head')
+        self.small_conv = option('small_conv')
         # True: the caller feeds every step through the SAME device tensors (e.g. a generator that assembles each batch in
         # place): the captured graphs read them directly instead of copying each batch into private static buffers
         self.static_batch_buffers = False
@@ -463,7 +464,8 @@ class Model(object):
                                                  premask0=pm.get(s0) if m0 else None, premask1=pm.get(s1) if m1 else None,
                                                  dy_premasked=out_uid in pm,
                                                  defer_ring0=bool(pm) and self.fold_ring and i in self._defer_ring,
-                                                 want_pool=self.fuse_pool and i in self._pool_producers)
+                                                 want_pool=self.fuse_pool and i in self._pool_producers,
+                                                 small=self.small_conv)
             elif st[0] == 'pool_skip':
                 _, out_uid, lay, in_uid = st
                 values[out_uid], values[in_uid] = ops.avgpool2_skip(values[in_uid],

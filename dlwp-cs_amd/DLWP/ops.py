@@ -525,8 +525,10 @@ class _CSConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, src0, src1, w_eq, w_pol, w_np, b_eq, b_pol, b_np, ksize, halo, up0, flip, act, alpha, vmax,
                 c0_valid=0, premask0=None, premask1=None, dy_premasked=False, defer_ring0=False, want_pool=False,
-                out_padded=False):
-        """out_padded (inference only, the pointwise bf16 output layer): y gets ceil8(C_out) channels per pixel, the padding
+                out_padded=False, small=False):
+        """small (engine option small_conv): layers the small-face kernel serves (_small_conv_ok) try dlwpcs_conv_small_fwd /
+        dlwpcs_conv_small_bwd_data first -- the same bits -- and take the general entry point when it answers E_UNSUPPORTED.
+        out_padded (inference only, the pointwise bf16 output layer): y gets ceil8(C_out) channels per pixel, the padding
         zero (DLWPCS_CONV_OUT_PADDED) -- what the first layer takes back as a padded source in a rollout.
         want_pool: the 2x2 average pooling of y is produced as a by-product (dlwpcs_conv_fwd_pool) and parked in _POOLED for
         the pooling node that follows (avgpool2_skip), which then launches nothing in its forward pass.
@@ -580,13 +582,21 @@ class _CSConv(torch.autograd.Function):
                  (ptr(w_eq), ptr(w_pol), ptr(w_np), ptr(b_eq), ptr(b_pol), ptr(b_np)))
         if packed is not None:
             d.flags |= nat.CONV_PREPACKED
+        small = bool(small) and _small_conv_ok(d)
         if yp is not None:
             check(lib().dlwpcs_conv_fwd_pool(ctypes.byref(d), ptr(src0), ptr(src1), *wargs, ptr(y), ptr(yp), ptr(table), ptr(ws),
                                              ws.numel(), stream_ptr()), 'dlwpcs_conv_fwd_pool')
             _POOLED[y.data_ptr()] = yp
         else:
-            check(lib().dlwpcs_conv_fwd(ctypes.byref(d), ptr(src0), ptr(src1), *wargs, ptr(y), ptr(table), ptr(ws),
-                                        ws.numel(), stream_ptr()), 'dlwpcs_conv_fwd')
+            rc = nat.E_UNSUPPORTED
+            if small:
+                rc = lib().dlwpcs_conv_small_fwd(ctypes.byref(d), ptr(src0), ptr(src1), *wargs, ptr(y), ptr(table), ptr(ws),
+                                                 ws.numel(), stream_ptr())
+            if rc == nat.E_UNSUPPORTED:
+                rc = lib().dlwpcs_conv_fwd(ctypes.byref(d), ptr(src0), ptr(src1), *wargs, ptr(y), ptr(table), ptr(ws),
+                                           ws.numel(), stream_ptr())
+            check(rc, 'dlwpcs_conv_fwd')
+        ctx.small = small
         if premask0 is not None and premask1 is not None and tuple(premask0) != tuple(premask1):
             raise ValueError('cs_conv: both sources must share the activation parameters of their masks')
         ctx.premask = (premask0, premask1)
@@ -651,16 +661,21 @@ class _CSConv(torch.autograd.Function):
                 wq = ctx.packed[3] if ctx.packed is not None else w_eq
                 pm = pm0 if pm0 is not None else pm1
                 ma, mv = (float(pm[0]), float(pm[1])) if pm is not None else (0.0, 0.0)
-                check(lib().dlwpcs_conv_bwd_data_masked(ctypes.byref(dn), ptr(dz), ptr(wq), ptr(w_pol), ptr(w_np), ptr(dsrc0),
-                                                        ptr(dsrc1), ptr(src0 if pm0 is not None else None),
-                                                        ptr(src1 if pm1 is not None else None), ma, mv, ptr(inv), ptr(ws),
-                                                        ws.numel(), stream_ptr()), 'dlwpcs_conv_bwd_data_masked')
+                bargs = (ctypes.byref(dn), ptr(dz), ptr(wq), ptr(w_pol), ptr(w_np), ptr(dsrc0), ptr(dsrc1),
+                         ptr(src0 if pm0 is not None else None), ptr(src1 if pm1 is not None else None), ma, mv, ptr(inv), ptr(ws),
+                         ws.numel(), stream_ptr())
+                rc = nat.E_UNSUPPORTED
+                if ctx.small and dsrc0 is not None and dsrc1 is None:
+                    rc = lib().dlwpcs_conv_small_bwd_data(*bargs)
+                if rc == nat.E_UNSUPPORTED:
+                    rc = lib().dlwpcs_conv_bwd_data_masked(*bargs)
+                check(rc, 'dlwpcs_conv_bwd_data_masked')
                 if ring is not None:
                     _pending_ring[dsrc0.data_ptr()] = (ws, ring[0], ring[1], nat.halo_tables(d.N, 1, dev)[1])
                     dn.flags &= ~nat.CONV_DEFER_RING0
             dw_eq, dw_pol, dw_np, db_eq, db_pol, db_np = _weight_gradients(
                 dn, src0, src1, dz, None, ctx.params, table, ws, nbytes, direct, defer, need[2:8], has_np, has_bias, has_bnp)
-            return (dsrc0, dsrc1, dw_eq, dw_pol, dw_np, db_eq, db_pol, db_np) + (None,) * 14
+            return (dsrc0, dsrc1, dw_eq, dw_pol, dw_np, db_eq, db_pol, db_np) + (None,) * 15
         no_dgrad = dsrc0 is None and dsrc1 is None        # (first layer: the batched kernel applies act' itself)
         # (exact-fp32 mode: the batched kernel forms dz = dy * act'(y) on load in every 3x3 layer -- exact in fp32, so the
         #  data-gradient kernel forming its own copy changes no bits -- and no dz hand-over is written at all)
@@ -693,7 +708,13 @@ class _CSConv(torch.autograd.Function):
             batch_mask_ok=mask_on_load)
         if reuse_dz:
             run_bwd_data()
-        return (dsrc0, dsrc1, dw_eq, dw_pol, dw_np, db_eq, db_pol, db_np) + (None,) * 14
+        return (dsrc0, dsrc1, dw_eq, dw_pol, dw_np, db_eq, db_pol, db_np) + (None,) * 15
+
+
+def _small_conv_ok(d):
+    """Layers worth offering to the small-face kernel (the library decides: it answers E_UNSUPPORTED for what it does not serve)."""
+    return (d.dtype == nat.BF16 and d.ksize == 3 and d.halo and d.C1 == 0 and not d.up0 and d.c0_valid == 0
+            and d.N * d.N <= 320 and d.C0 % 32 == 0 and d.Cout % 32 == 0 and d.B > 0)
 
 
 _ring_info_cache = {}
@@ -761,7 +782,9 @@ def pack_batch(items_dev, n_items):
 
 def cs_conv(src0, w_eq, w_pol, w_np=None, b_eq=None, b_pol=None, b_np=None, src1=None, ksize=3, halo=True, up0=False,
             flip_north_pole=True, act=nat.ACT_NONE, alpha=0.0, vmax=0.0, premask0=None, premask1=None, dy_premasked=False,
-            defer_ring0=False, want_pool=False, out_padded=False):
+            defer_ring0=False, want_pool=False, out_padded=False, small=False):
+    """small: offer the layer to the small-face kernel first (the engine passes its option small_conv; direct callers keep the
+    general kernel unless they ask)."""
     if (w_np is None) != (b_np is None) and b_eq is not None:
         raise ValueError('cs_conv: north-pole kernel and bias must be given together')
     # Network inputs with a channel count that is not a multiple of the 16-B vector (7 variables; optionally 14 = 7 x 2):
@@ -781,7 +804,7 @@ def cs_conv(src0, w_eq, w_pol, w_np=None, b_eq=None, b_pol=None, b_np=None, src1
             c0_valid = cin_w
     return _CSConv.apply(src0, src1, w_eq, w_pol, w_np, b_eq, b_pol, b_np, int(ksize), bool(halo), bool(up0),
                          bool(flip_north_pole), int(act), float(alpha), float(vmax), int(c0_valid), premask0, premask1,
-                         bool(dy_premasked), bool(defer_ring0), bool(want_pool), bool(out_padded))
+                         bool(dy_premasked), bool(defer_ring0), bool(want_pool), bool(out_padded), bool(small))
 
 
 def cs_conv_head_applicable(src0, src1, w_eq, head_w_eq, out_padded):

@@ -18,6 +18,7 @@ is asked for, so a test can set it around the construction of a model).  Everyth
   resident_data   fit() over several epochs keeps the arrays it uploaded during the first one in HBM            (Model)
   fold_head       inference: the pointwise output layer inside the epilogue of the convolution in front of it  (Model)
   dgrad_gather    bf16 data gradients in gather form (no halo ring, no fix-up launches); 0: padded grid        (ops)
+  small_conv      bf16 3x3 layers on faces of <= 320 cells (the coarsest U-Net level) run the small-face kernel    (Model)
   check_finite    fit() raises on a non-finite loss                                                            (Model.check_finite)
 """
 import os
@@ -25,7 +26,7 @@ import os
 DEFAULTS = {
     'graphs': True, 'premask': True, 'wgrad_batch': True, 'fuse_adam': True, 'fuse_pack': True, 'fuse_head': True,
     'fold_loss_tail': True, 'fuse_pool': True, 'fold_ring': True, 'cf_model': True, 'padded_io': True, 'host_staging': True, 'resident_data': True,
-    'dgrad_gather': True, 'fold_head': True, 'check_finite': False,
+    'dgrad_gather': True, 'fold_head': True, 'small_conv': True, 'check_finite': False,
 }
 
 

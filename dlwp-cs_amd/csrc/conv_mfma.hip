@@ -1429,6 +1429,14 @@ static inline int out_size(const dlwpcs_conv_desc *d) { return d->halo ? d->N : 
 // fills k >= K) and the weight-gradient reduction emits the real rows only.
 static inline int cin_logical(const dlwpcs_conv_desc *d) { return (d->c0_valid > 0 ? d->c0_valid : d->C0) + d->C1; }
 
+// conv_small.hip: the non-persistent kernel for small faces (dlwpcs_conv_small_fwd / dlwpcs_conv_small_bwd_data)
+bool conv_small_serves(int B, int N, int Cin, int Cout);
+int launch_conv_small(const ConvKParams &K, hipStream_t s);
+static bool conv_small_layer_ok(const dlwpcs_conv_desc *d) {
+    return d->dtype == DLWPCS_BF16 && d->ksize == 3 && d->halo && d->C1 == 0 && !d->up0 && d->c0_valid == 0 &&
+           !(d->flags & DLWPCS_CONV_OUT_PADDED) && conv_small_serves(d->B, d->N, d->C0, d->Cout);
+}
+
 // workspace layout (bytes, 256-aligned regions)
 struct WsLayout {
     size_t wpk_f, bias, wpk_b, dxv, dz, partial, bpartial, total;
@@ -1708,7 +1716,7 @@ static int conv_fwd_impl(const dlwpcs_conv_desc *d, const void *src0, const void
                          const void *b_eq, const void *b_pol, const void *b_np,
                          void *y, const int32_t *table_dev,
                          void *workspace, size_t workspace_bytes, dlwpcs_stream_t stream, void *y_pooled, int *pool_done,
-                         const ConvHeadArgs *head = nullptr);
+                         const ConvHeadArgs *head = nullptr, bool small = false);
 
 extern "C" int dlwpcs_conv_fwd(const dlwpcs_conv_desc *d, const void *src0, const void *src1,
                                const void *w_eq, const void *w_pol, const void *w_np,
@@ -1776,9 +1784,12 @@ static int conv_fwd_impl(const dlwpcs_conv_desc *d, const void *src0, const void
                          const void *b_eq, const void *b_pol, const void *b_np,
                          void *y, const int32_t *table_dev,
                          void *workspace, size_t workspace_bytes, dlwpcs_stream_t stream, void *y_pooled, int *pool_done,
-                         const ConvHeadArgs *head) {
+                         const ConvHeadArgs *head, bool small) {
     int rc = validate(d, "conv_fwd");
     if (rc) return rc;
+    // the small-face kernel (conv_small.hip) or nothing: decided before anything is launched (weight packing included)
+    if (small && !conv_small_layer_ok(d))
+        return fail(DLWPCS_E_UNSUPPORTED, "conv_small_fwd: serves bf16 3x3 halo layers with one source on faces of <= 320 cells, channel counts multiples of 32");
     if (!src0 || !w_eq || (!w_pol && !(d->flags & DLWPCS_CONV_PREPACKED)) || !y || !workspace)
         return fail(DLWPCS_E_INVALID, "conv_fwd: null pointer");
     if (d->C1 > 0 && !src1) return fail(DLWPCS_E_INVALID, "conv_fwd: C1 > 0 but src1 is null");
@@ -1812,6 +1823,7 @@ static int conv_fwd_impl(const dlwpcs_conv_desc *d, const void *src0, const void
     if (head) { P.head_w = head->wpk; P.head_b = head->bias; P.head_out = head->out; P.head_done = head->done; }
     if ((d->flags & DLWPCS_CONV_OUT_PADDED) && !pw_applies(d))
         return fail(DLWPCS_E_UNSUPPORTED, "conv_fwd: DLWPCS_CONV_OUT_PADDED serves the bf16 pointwise output layer only");
+    if (small) return launch_conv_small(P, s);
     if (pw_applies(d)) {
         PwParams Q{};
         Q.in = (const bf16_t *)src0; Q.wpk = (const bf16_t *)wpk; Q.bias = b_eq ? bpk : nullptr; Q.out = (bf16_t *)y;
@@ -1856,9 +1868,13 @@ static int conv_bwd_data_impl(const dlwpcs_conv_desc *d, const void *dy, const v
                               const void *w_eq, const void *w_pol, const void *w_np,
                               void *dsrc0, void *dsrc1, const void *m0, const void *m1, float m_alpha, float m_vmax,
                               const int32_t *inv_table_dev, void *workspace, size_t workspace_bytes, dlwpcs_stream_t stream,
-                              const char *who, int *ring_query = nullptr) {
+                              const char *who, int *ring_query = nullptr, bool small = false) {
     int rc = validate(d, who);
     if (rc) return rc;
+    // the small-face kernel (conv_small.hip) or nothing: decided before anything is launched.  It takes the gradient as dz (no
+    // mask on load) and writes what the padded-grid kernel writes; everything behind the launch is this function's as it is.
+    if (small && (!conv_small_layer_ok(d) || (d->act != DLWPCS_ACT_NONE && !dz_given) || dsrc1 || !dsrc0))
+        return fail(DLWPCS_E_UNSUPPORTED, "%s: serves bf16 3x3 halo layers with one source on faces of <= 320 cells, channel counts multiples of 32, gradient given as dz", who);
     const bool prepacked = (d->flags & DLWPCS_CONV_PREPACKED) != 0;
     if (!dy || !w_eq || (!w_pol && !prepacked) || !workspace) return fail(DLWPCS_E_INVALID, "%s: null pointer", who);
     const bool has_act = d->act != DLWPCS_ACT_NONE && !dz_given;
@@ -1957,6 +1973,8 @@ static int conv_bwd_data_impl(const dlwpcs_conv_desc *d, const void *dy, const v
         const bool need_direct = G.d0 || G.d1;
         if (!grc) grc = dispatch_conv(d->dtype, d->ksize, 8, G, conv_work(d), s);
         if (!grc && (g_direct || !need_direct)) {
+            // (the gather form would serve this shape: its result is rounded once, the padded grid's twice -- not the same bits)
+            if (small) return fail(DLWPCS_E_UNSUPPORTED, "%s: this shape is served in gather form", who);
             if (ring_query) { *ring_query = 0; return DLWPCS_OK; }      // nothing is deferred: there is no ring
             G.dry_run = 0;
             grc = dispatch_conv(d->dtype, d->ksize, 8, G, conv_work(d), s);
@@ -1982,7 +2000,7 @@ static int conv_bwd_data_impl(const dlwpcs_conv_desc *d, const void *dy, const v
     const bool whole = !d->halo && !d->up0 && d->C1 == 0 && dsrc0;
     if (whole) P.out = dsrc0;
     P.dry_run = ring_query ? 1 : 0;
-    rc = dispatch_conv(d->dtype, d->ksize, vec_width(d->Cout, 0, d->dtype), P, conv_work(d), s);
+    rc = small ? launch_conv_small(P, s) : dispatch_conv(d->dtype, d->ksize, vec_width(d->Cout, 0, d->dtype), P, conv_work(d), s);
     if (ring_query) { *ring_query = (!rc && direct_done && P.d0 && !m0) ? 1 : 0; return rc; }
     if (rc) return rc;
     if (whole) return finish_masks(true, false);
@@ -2041,6 +2059,25 @@ extern "C" int dlwpcs_conv_bwd_data_masked(const dlwpcs_conv_desc *d, const void
                                            void *workspace, size_t workspace_bytes, dlwpcs_stream_t stream) {
     return conv_bwd_data_impl(d, dz, nullptr, true, w_eq, w_pol, w_np, dsrc0, dsrc1, m0, m1, m_alpha, m_vmax, inv_table_dev, workspace,
                               workspace_bytes, stream, "conv_bwd_data_masked");
+}
+
+// The small-face kernel behind the same parameter records: DLWPCS_E_UNSUPPORTED (nothing launched) for every call it does not serve.
+extern "C" int dlwpcs_conv_small_fwd(const dlwpcs_conv_desc *d, const void *src0, const void *src1,
+                                     const void *w_eq, const void *w_pol, const void *w_np,
+                                     const void *b_eq, const void *b_pol, const void *b_np,
+                                     void *y, const int32_t *table_dev,
+                                     void *workspace, size_t workspace_bytes, dlwpcs_stream_t stream) {
+    return conv_fwd_impl(d, src0, src1, w_eq, w_pol, w_np, b_eq, b_pol, b_np, y, table_dev, workspace, workspace_bytes, stream,
+                         nullptr, nullptr, nullptr, true);
+}
+
+extern "C" int dlwpcs_conv_small_bwd_data(const dlwpcs_conv_desc *d, const void *dz,
+                                          const void *w_eq, const void *w_pol, const void *w_np,
+                                          void *dsrc0, void *dsrc1, const void *m0, const void *m1, float m_alpha, float m_vmax,
+                                          const int32_t *inv_table_dev,
+                                          void *workspace, size_t workspace_bytes, dlwpcs_stream_t stream) {
+    return conv_bwd_data_impl(d, dz, nullptr, true, w_eq, w_pol, w_np, dsrc0, dsrc1, m0, m1, m_alpha, m_vmax, inv_table_dev, workspace,
+                              workspace_bytes, stream, "conv_small_bwd_data", nullptr, true);
 }
 
 extern "C" int dlwpcs_conv_ring_info(const dlwpcs_conv_desc *d, size_t *dxv_offset, int *channels) {

@@ -238,6 +238,26 @@ int dlwpcs_conv_bwd_data_masked(const dlwpcs_conv_desc *d, const void *dz,
                                 const int32_t *inv_table_dev,
                                 void *workspace, size_t workspace_bytes, dlwpcs_stream_t stream);
 
+/* The SMALL-FACE kernel behind the same parameter records: bf16, k = 3, halo, one source (C1 = 0, no up0, no c0_valid), faces of
+ * N * N <= 320 cells (the coarsest U-Net level, N = 12), C0 and C_out multiples of 32.  One workgroup per (sample, face, 32 output
+ * channels) holds the whole haloed face in LDS, several workgroups per CU -- where the persistent kernel of dlwpcs_conv_fwd /
+ * dlwpcs_conv_bwd_data_masked runs a single under-filled tile per workgroup.  The same arithmetic in the same order: y, dsrc0 and
+ * the halo ring in the workspace are bitwise what those calls produce (DLWPCS_CONV_DEFER_RING0 / dlwpcs_conv_ring_info apply
+ * unchanged).  dlwpcs_conv_small_bwd_data takes the gradient as dz like dlwpcs_conv_bwd_data_masked (dsrc1 / m1 must be NULL).
+ * Every other request returns DLWPCS_E_UNSUPPORTED and has launched nothing: the caller falls back to the general entry point.
+ * Not bracketed by the opt-in launch profiler. */
+int dlwpcs_conv_small_fwd(const dlwpcs_conv_desc *d,
+                          const void *src0, const void *src1,
+                          const void *w_eq, const void *w_pol, const void *w_np,
+                          const void *b_eq, const void *b_pol, const void *b_np,
+                          void *y, const int32_t *table_dev,
+                          void *workspace, size_t workspace_bytes, dlwpcs_stream_t stream);
+int dlwpcs_conv_small_bwd_data(const dlwpcs_conv_desc *d, const void *dz,
+                               const void *w_eq, const void *w_pol, const void *w_np,
+                               void *dsrc0, void *dsrc1, const void *m0, const void *m1, float m_alpha, float m_vmax,
+                               const int32_t *inv_table_dev,
+                               void *workspace, size_t workspace_bytes, dlwpcs_stream_t stream);
+
 /* 1 if a data-gradient call on d with DLWPCS_CONV_DEFER_RING0 defers the fix-up of source 0; then *dxv_offset = byte offset of
  * the padded gradient (B,6,N+2,N+2,channels) inside that call's workspace and *channels = C0 + C1 (source 0 = the first C0). */
 int dlwpcs_conv_ring_info(const dlwpcs_conv_desc *d, size_t *dxv_offset, int *channels);
