@@ -148,6 +148,16 @@ class ZonalSpectrumDesc(ctypes.Structure):
                 ('stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 3)]
 
 
+ENSEMBLE_MAX_M = 128
+
+
+class EnsembleDesc(ctypes.Structure):
+    """struct dlwpcs_ensemble_desc (include/dlwpcs.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ('M', 'n_dims', 'fair', 'ddof', 'variance', 'reserved')] + \
+               [('member_stride', ctypes.c_int64), ('ext', ctypes.c_int64 * SCORE_MAX_DIMS),
+                ('stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 2)]
+
+
 AFFINE_MUL_ADD, AFFINE_SUB_DIV = 0, 1
 AFFINE_MAX_CHANNELS = 1024
 
@@ -247,6 +257,8 @@ PROTOTYPES = {
     'dlwpcs_fill_missing': (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_int, c_int, c_void_p]),
     'dlwpcs_zonal_spectrum_scratch_bytes': (c_size_t, [c_void_p]),
     'dlwpcs_zonal_spectrum': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_ensemble_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_ensemble_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_count': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_fill': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p]),
     'dlwpcs_cube_bilinear': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -2033,6 +2033,129 @@ def zonal_spectrum(a, b=None, lon_axis=-1, reduced=(), weights=None, n_wave=None
 
 
 # ------------------------------------------------------------------------------------------------------------------ #
+# Ensemble scores (DLWP/verify.py ensemble_* / rank_histogram), include/dlwpcs.h dlwpcs_ensemble_stats
+# ------------------------------------------------------------------------------------------------------------------ #
+
+ENSEMBLE_MAX_M = nat.ENSEMBLE_MAX_M
+ENSEMBLE_OUTPUTS = ('mean', 'spread', 'crps', 'rank')
+
+
+def ensemble_layout(shape, strides, member_axis=0, valid_shape=None, valid_strides=None):
+    """
+    How dlwpcs_ensemble_stats walks an ensemble of logical `shape` and element `strides` whose members lie along `member_axis`,
+    and a verification of `valid_shape` / `valid_strides` (the ensemble's dims without the member axis, extents of 1 broadcast):
+    (M, member stride, element shape, order, merged dims).  `order` lists the element dims of extent > 1 from the largest stride
+    of the ensemble to the smallest, so that the lanes run along the dim that is contiguous in memory whatever view the caller
+    holds; the outputs are laid out in that order and handed back as views of the element shape.  Merged dims as _coalesce makes
+    them: [(extent, (ensemble stride, verification stride))].
+    """
+    shape = tuple(int(s) for s in shape)
+    strides = tuple(int(s) for s in strides)
+    nd = len(shape)
+    if nd < 1 or not -nd <= int(member_axis) < nd:
+        raise ValueError('ensemble_stats: member axis %s out of range of %d axes' % (member_axis, nd))
+    ax = int(member_axis) % nd
+    M = shape[ax]
+    if M < 2:
+        raise ValueError('ensemble_stats: %d members (at least 2)' % M)
+    eshape = shape[:ax] + shape[ax + 1:]
+    es = strides[:ax] + strides[ax + 1:]
+    if valid_shape is None:
+        vs = (0,) * len(eshape)
+    else:
+        vshape = tuple(int(s) for s in valid_shape)
+        if len(vshape) != len(eshape) or any(v not in (1, e) for v, e in zip(vshape, eshape)):
+            raise ValueError('ensemble_stats: the verification %s must carry the dims of the ensemble without the member axis %s '
+                             '(extents of 1 broadcast)' % (vshape, eshape))
+        vs = tuple(0 if v == 1 else int(s) for v, s in zip(vshape, valid_strides))
+    order = sorted((i for i in range(len(eshape)) if eshape[i] != 1), key=lambda i: -abs(es[i]))
+    merged = _coalesce(order, eshape, [es, vs])
+    if len(merged) > nat.SCORE_MAX_DIMS:
+        raise NotImplementedError('ensemble_stats: more than %d element dims after merging' % nat.SCORE_MAX_DIMS)
+    return M, strides[ax], eshape, order, merged
+
+
+def ensemble_desc(M, member_stride, merged, fair=False, ddof=1, variance=False):
+    """nat.EnsembleDesc of M members `member_stride` elements apart over the merged dims of ensemble_layout"""
+    if int(ddof) not in (0, 1):
+        raise ValueError('ensemble_stats: ddof = %s (0 or 1)' % (ddof,))
+    d = nat.EnsembleDesc()
+    d.M, d.n_dims, d.fair, d.ddof, d.variance = int(M), len(merged), int(bool(fair)), int(ddof), int(bool(variance))
+    d.member_stride = int(member_stride)
+    for i, (e, s) in enumerate(merged):
+        d.ext[i] = e
+        d.stride[0][i], d.stride[1][i] = s
+    return d
+
+
+def ensemble_plan(shape, strides, member_axis=0, valid_shape=None, valid_strides=None, ens_ptr=1 << 20, valid_ptr=None,
+                  fair=False, ddof=1, variance=False):
+    """
+    Which code ensemble_stats would run for an ensemble of this shape, these element strides and this address (host only: no
+    device is touched, the addresses are looked at for alignment): dict(m_class = member slots of the instantiation, vec = 16-byte
+    loads of the ensemble, valid = -1 absent / 0 element by element / 1 16-byte loads, lds = members in LDS, grid, threads).
+    valid_ptr defaults to an aligned address when a verification shape is given.  Raises what ensemble_stats would raise.
+    """
+    M, ms, _, _, merged = ensemble_layout(shape, strides, member_axis, valid_shape, valid_strides)
+    d = ensemble_desc(M, ms, merged, fair, ddof, variance)
+    if valid_ptr is None and valid_shape is not None:
+        valid_ptr = 1 << 21
+    info = (ctypes.c_int32 * 8)()
+    check(lib().dlwpcs_ensemble_plan_info(ctypes.byref(d), int(ens_ptr), valid_ptr or None, info), 'dlwpcs_ensemble_plan_info')
+    return dict(m_class=info[0], vec=bool(info[1]), valid=info[2], lds=bool(info[3]), grid=(info[4], info[5]), threads=info[6])
+
+
+def ensemble_stats(ens, valid=None, member_axis=0, want=ENSEMBLE_OUTPUTS, fair=False, ddof=1, variance=False):
+    """
+    Collapse the member axis of the float32 device tensor `ens` element by element: dict of device tensors shaped like `ens`
+    without that axis, 'mean', 'spread' (standard deviation with `ddof`; variance=True: the variance), 'crps' (against `valid`;
+    fair=True: the pair term over M (M - 1)) -- float32 -- and 'rank' (int32: members strictly below `valid`, 0..M), those named
+    in `want`.  `valid`: a float32 device tensor with the dims of `ens` without the member axis, extents of 1 broadcast; 'crps'
+    and 'rank' need it.  An element with a NaN or infinite member is NaN / -1 everywhere, a NaN or infinite verification in
+    'crps' / 'rank'.  Views are read through their strides (no copy); the results may come back as permuted views.  One launch
+    on the current stream, no host synchronisation, no allocation besides the outputs.
+    """
+    want = tuple(want)
+    if not want or any(w not in ENSEMBLE_OUTPUTS for w in want):
+        raise ValueError('ensemble_stats: want %s, a non-empty choice of %s' % (want, ENSEMBLE_OUTPUTS))
+    require_device(ens, 'ensemble_stats')
+    if ens.dtype != torch.float32:
+        raise TypeError('ensemble_stats: operands must be float32, got %s' % ens.dtype)
+    if valid is not None:
+        require_device(valid, 'ensemble_stats')
+        if valid.dtype != torch.float32 or valid.device != ens.device:
+            raise TypeError('ensemble_stats: the verification must be a float32 tensor on the device of the ensemble')
+    elif 'crps' in want or 'rank' in want:
+        raise ValueError("ensemble_stats: 'crps' and 'rank' need a verification")
+    M, ms, eshape, order, merged = ensemble_layout(ens.shape, ens.stride(), member_axis,
+                                                   None if valid is None else valid.shape,
+                                                   None if valid is None else valid.stride())
+    if M > ENSEMBLE_MAX_M:
+        raise NotImplementedError('ensemble_stats: %d members, the kernel serves 2 .. %d' % (M, ENSEMBLE_MAX_M))
+    d = ensemble_desc(M, ms, merged, fair, ddof, variance)
+    n = 1
+    for e in eshape:
+        n *= e
+    dims = sorted(order)
+    perm = [order.index(i) for i in dims]
+    flat, res = {}, {}
+    for name in ENSEMBLE_OUTPUTS:
+        if name in want:
+            flat[name] = torch.empty(n, dtype=torch.int32 if name == 'rank' else torch.float32, device=ens.device)
+            t = flat[name].view([eshape[i] for i in order]).permute(perm) if order else flat[name].view(())
+            for i, e in enumerate(eshape):
+                if e == 1:
+                    t = t.unsqueeze(i)
+            res[name] = t if n else flat[name].view(eshape)
+    if n:
+        with torch.cuda.device(ens.device):
+            check(lib().dlwpcs_ensemble_stats(ctypes.byref(d), ptr(ens), ptr(valid) or None, ptr(flat.get('mean')) or None,
+                                              ptr(flat.get('spread')) or None, ptr(flat.get('crps')) or None,
+                                              ptr(flat.get('rank')) or None, stream_ptr()), 'dlwpcs_ensemble_stats')
+    return res
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
 # Climatologies (DLWP/verify.py): grouped mean over rows and indexed row gather, include/dlwpcs.h dlwpcs_rows_desc
 # ------------------------------------------------------------------------------------------------------------------ #
 

@@ -739,6 +739,49 @@ int dlwpcs_zonal_spectrum(const dlwpcs_zonal_spectrum_desc *d, const float *a, c
                           int32_t *skipped /* may be NULL */, dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Ensemble scores (DLWP/verify.py ensemble_mean, ensemble_spread, ensemble_crps, ensemble_error, rank_histogram): the member
+ * axis of an fp32 ensemble collapsed element by element.  The element dims arrive as n_dims merged dims with an extent and an
+ * element stride per operand (0: ens, 1: valid; 0 = broadcast), the members lie member_stride elements apart: a permuted view
+ * or a member axis in the middle needs no copy.  With the members x_1..x_M of an element and its verification y, in fp32:
+ *   mean    x_1 + (sum_i (x_i - x_1)) / M
+ *   spread  sqrt(sum_i ((x_i - x_1) - tbar)^2 / (M - ddof)), tbar the mean of the x_i - x_1; `variance`: its square instead
+ *   crps    A - B / 2,  A = (1 / M) sum_i |x_i - y|,  B = sum_ij |x_i - x_j| / M^2  (`fair`: / (M (M - 1))), evaluated as the
+ *           integral of (F(t) - 1{t >= y})^2 over the gaps of the SORTED differences d_i = x_i - y: a sum of non-negative terms
+ *           k^2 (part of gap k below y) + (M - k)^2 (part above y), over M^2, plus the tail |d| beyond the ensemble; the fair
+ *           form subtracts sum_k k (M - k) gap_k / (M^2 (M - 1)).  No offset of the data reaches the error, M identical members
+ *           give spread 0 and crps = the fp32 |x - y| exactly.
+ *   rank    the number of members with x_i < y (the inputs compared as they are), 0..M
+ * An element with a NaN or infinite member gets NaN in mean, spread and crps and -1 in rank; a NaN or infinite y gets NaN in
+ * crps and -1 in rank only.  Outputs (each may be NULL: not computed) are contiguous in the row-major order of the element
+ * dims; crps and rank need valid.  2 <= M <= 128 (DLWPCS_E_UNSUPPORTED beyond): M <= 32 is sorted by a compare-exchange network
+ * in registers (classes of 4, 8, 16, 32 slots, the unused ones never enter a sum), 33..128 in lane-private columns of LDS
+ * (classes of 64 and 128).  Lanes run along the LAST element dim: list the dim that is contiguous in ens last.  16-byte loads
+ * (four elements per lane) in the classes up to 16 when that dim has stride 1 and an extent that is a multiple of 4, every other
+ * stride of ens and member_stride are multiples of 4 and ens is 16-byte aligned; one element per lane otherwise -- the same bits.
+ * One launch, no scratch, no atomics, no allocation, no host synchronisation (capturable).  A zero extent launches nothing.
+ *
+ * dlwpcs_ensemble_plan_info (host only; the pointers are looked at for NULL and alignment, never dereferenced): info[0] = the
+ * class (slots: 4, 8, 16, 32, 64, 128), info[1] = 1: 16-byte loads of ens, 0: one element per load, info[2] = how valid is read
+ * (-1: absent, 0: element by element, 1: 16-byte loads), info[3] = 1: members in LDS, 0: in registers, info[4] / info[5] = the
+ * grid, info[6] = threads of a workgroup, info[7] = 0.  Returns what the entry point would return for the descriptor.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_ENSEMBLE_MAX_M 128
+typedef struct dlwpcs_ensemble_desc {
+    int32_t M;                   /* members, 2 .. DLWPCS_ENSEMBLE_MAX_M */
+    int32_t n_dims;              /* element dims, at most DLWPCS_SCORE_MAX_DIMS */
+    int32_t fair;                /* crps: pair term over M (M - 1) */
+    int32_t ddof;                /* spread: 0 or 1 */
+    int32_t variance;            /* out_spread holds the variance */
+    int32_t reserved;
+    int64_t member_stride;       /* elements */
+    int64_t ext[DLWPCS_SCORE_MAX_DIMS];
+    int64_t stride[2][DLWPCS_SCORE_MAX_DIMS];     /* elements: ens, valid */
+} dlwpcs_ensemble_desc;
+int dlwpcs_ensemble_stats(const dlwpcs_ensemble_desc *d, const float *ens, const float *valid /* may be NULL */,
+                          float *out_mean, float *out_spread, float *out_crps, int32_t *out_rank, dlwpcs_stream_t stream);
+int dlwpcs_ensemble_plan_info(const dlwpcs_ensemble_desc *d, const void *ens, const void *valid, int32_t info[8]);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Conservative offline maps made on the device (DLWP/remap/overlap.py is the host twin and states the maths): A[r, c], the
  * area in steradians of (lat-lon cell r) intersected with (equiangular cubed-sphere cell c), in closed form and fp64, in CSR
  * form over the lat-lon cells (lat-major).  The cube is given by its face frames {e0, eu, ev} (centre, width and height
