@@ -871,6 +871,11 @@ def _same_pads(n, k, s, dil):
     return total // 2, out
 
 
+def _valid_len(n, k, s, dil):
+    """output length of a 'valid' axis; < 1 when the dilated window does not fit (cs_gconv then raises)"""
+    return (n - (k - 1) * dil - 1) // s + 1
+
+
 class _GConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_eq, w_pol, w_np, b_eq, b_pol, b_np, strides, padding, dilation, flip):
@@ -890,8 +895,8 @@ class _GConv(torch.autograd.Function):
             pad_l, Wo = _same_pads(W, kw, sw, dw)
         elif padding == 'valid':
             pad_t = pad_l = 0
-            Ho = (H - (kh - 1) * dh - 1) // sh + 1
-            Wo = (W - (kw - 1) * dw - 1) // sw + 1
+            Ho = _valid_len(H, kh, sh, dh)
+            Wo = _valid_len(W, kw, sw, dw)
         else:
             raise ValueError('padding must be "valid" or "same"')
         if Ho < 1 or Wo < 1:

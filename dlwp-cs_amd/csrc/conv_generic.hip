@@ -98,7 +98,10 @@ __global__ void __launch_bounds__(256) gconv_bwd_data_kernel(GP g, const T *__re
     }
 }
 
-// one workgroup per weight element (group, ky, kx, ci, co) or bias element; fixed-order tree reduction
+// one workgroup per weight element (group, ky, kx, ci, co), then one per element of every bias gradient asked for (the host
+// launches bias workgroups for db_eq and db_pol, and for db_np when it is given, or none); fixed-order tree reduction.
+// The face ranges are the adjoint of group_ptr in the forward pass, for the kernels and for the biases SEPARATELY: face 5
+// goes to dw_np if given, else to dw_pol, and its bias sum to db_np if given, else to db_pol -- whichever kernel served it.
 template <typename T>
 __global__ void __launch_bounds__(256) gconv_bwd_weights_kernel(GP g, const T *__restrict__ x, const T *__restrict__ dy,
                                                                 float *__restrict__ dw_eq, float *__restrict__ dw_pol,
@@ -106,16 +109,17 @@ __global__ void __launch_bounds__(256) gconv_bwd_weights_kernel(GP g, const T *_
                                                                 float *__restrict__ db_pol, float *__restrict__ db_np,
                                                                 int ngroups) {
     const int nW = g.kh * g.kw * g.Cin * g.Cout;
-    const int per_group = nW + g.Cout;
-    const int grp = blockIdx.x / per_group;          // 0 eq, 1 pol, 2 np
-    const int e = blockIdx.x % per_group;
-    const bool is_bias = e >= nW;
+    const bool is_bias = (int)blockIdx.x >= ngroups * nW;
+    const int rb = is_bias ? (int)blockIdx.x - ngroups * nW : (int)blockIdx.x;
+    const int grp = rb / (is_bias ? g.Cout : nW);    // 0 eq, 1 pol, 2 np
+    const int e = rb % (is_bias ? g.Cout : nW);
+    const bool own_np = is_bias ? db_np != nullptr : ngroups == 3;
     int f_begin, f_end;
     if (grp == 0) { f_begin = 0; f_end = 4; }
-    else if (grp == 1) { f_begin = 4; f_end = (ngroups == 3) ? 5 : 6; }
+    else if (grp == 1) { f_begin = 4; f_end = own_np ? 5 : 6; }
     else { f_begin = 5; f_end = 6; }
     int co, ci = 0, ky = 0, kx = 0;
-    if (is_bias) co = e - nW;
+    if (is_bias) co = e;
     else { co = e % g.Cout; ci = (e / g.Cout) % g.Cin; kx = (e / (g.Cout * g.Cin)) % g.kw; ky = e / (g.Cout * g.Cin * g.kw); }
     const size_t npos = (size_t)g.B * (f_end - f_begin) * g.Ho * g.Wo;
     float acc = 0.f;
@@ -145,7 +149,7 @@ __global__ void __launch_bounds__(256) gconv_bwd_weights_kernel(GP g, const T *_
     if (threadIdx.x == 0) {
         float *dw = grp == 0 ? dw_eq : (grp == 1 ? dw_pol : dw_np);
         float *db = grp == 0 ? db_eq : (grp == 1 ? db_pol : db_np);
-        if (is_bias) { if (db) db[co] = red[0]; }
+        if (is_bias) db[co] = red[0];
         else dw[e] = red[0];
     }
 }
@@ -217,14 +221,18 @@ extern "C" int dlwpcs_gconv_bwd_weights(const dlwpcs_gconv_desc *d, const void *
     int rc = check_desc(d, "gconv_bwd_weights", g);
     if (rc) return rc;
     if (!x || !dy || !dw_eq || !dw_pol) return fail(DLWPCS_E_INVALID, "gconv_bwd_weights: null pointer");
+    if ((db_eq == nullptr) != (db_pol == nullptr) || (db_np && !db_eq))
+        return fail(DLWPCS_E_INVALID, "gconv_bwd_weights: db_eq and db_pol must be both given or both null, db_np only with them");
     const int ngroups = dw_np ? 3 : 2;
-    const int per_group = g.kh * g.kw * g.Cin * g.Cout + g.Cout;
+    const int nbias = db_eq ? (db_np ? 3 : 2) : 0;
+    const long long nblocks = (long long)ngroups * g.kh * g.kw * g.Cin * g.Cout + (long long)nbias * g.Cout;
+    if (nblocks > 0x7fffffffLL) return fail(DLWPCS_E_INVALID, "gconv_bwd_weights: too many weight elements");
     if (d->dtype == DLWPCS_BF16)
-        hipLaunchKernelGGL(gconv_bwd_weights_kernel<bf16_t>, dim3((unsigned)(ngroups * per_group)), dim3(256), 0,
+        hipLaunchKernelGGL(gconv_bwd_weights_kernel<bf16_t>, dim3((unsigned)nblocks), dim3(256), 0,
                            (hipStream_t)stream, g, (const bf16_t *)x, (const bf16_t *)dy, (float *)dw_eq, (float *)dw_pol,
                            (float *)dw_np, (float *)db_eq, (float *)db_pol, (float *)db_np, ngroups);
     else
-        hipLaunchKernelGGL(gconv_bwd_weights_kernel<float>, dim3((unsigned)(ngroups * per_group)), dim3(256), 0,
+        hipLaunchKernelGGL(gconv_bwd_weights_kernel<float>, dim3((unsigned)nblocks), dim3(256), 0,
                            (hipStream_t)stream, g, (const float *)x, (const float *)dy, (float *)dw_eq, (float *)dw_pol,
                            (float *)dw_np, (float *)db_eq, (float *)db_pol, (float *)db_np, ngroups);
     return check_launch("gconv_bwd_weights");

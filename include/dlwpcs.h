@@ -369,6 +369,12 @@ int dlwpcs_wgrad_batch_apply(const dlwpcs_wgrad_item *items, int n_items, const 
  * Generic (any kernel size / stride / dilation / 'same') per-face convolution on an ALREADY PADDED channels_last
  * tensor: the off-hot-path options of CubeSphereConv2D (DLWP/custom.py:824-842).  Direct VALU kernels.
  * x: (B,6,H,W,Cin) -> y: (B,6,Ho,Wo,Cout);  pad_{t,l}: zero padding already resolved by the caller ('same').
+ * Weight groups: faces 0-3 use w_eq / b_eq, face 4 w_pol / b_pol; face 5 uses w_np if given, else w_pol, and -- chosen
+ * separately -- b_np if given, else b_pol.  b_eq and b_pol are both given or both null (no bias; b_np is then ignored).
+ * dlwpcs_gconv_bwd_weights is the adjoint of exactly that rule: face 5's kernel gradient goes to dw_np if given, else it is
+ * summed into dw_pol; face 5's bias gradient goes to db_np if given, else it is summed into db_pol, whether or not dw_np is
+ * given.  db_eq and db_pol are both given or both null (no bias gradient is computed), db_np only together with them;
+ * anything else is DLWPCS_E_INVALID.  Every tensor that is given is written completely, a null one is not touched.
  * ------------------------------------------------------------------------------------------------------------- */
 typedef struct dlwpcs_gconv_desc {
     int32_t B, H, W, Cin, Cout;
