@@ -148,6 +148,14 @@ class ZonalSpectrumDesc(ctypes.Structure):
                 ('stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 3)]
 
 
+class ShtSpectrumDesc(ctypes.Structure):
+    """struct dlwpcs_sht_spectrum_desc (include/dlwpcs.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ('nlat', 'L', 'T', 'n_dims')] + \
+               [('lat_stride', ctypes.c_int64 * 2), ('ext', ctypes.c_int64 * SCORE_MAX_DIMS),
+                ('stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 2)]
+
+
+SHT_MAX_NLAT = 8192
 ENSEMBLE_MAX_M = 128
 
 
@@ -257,6 +265,8 @@ PROTOTYPES = {
     'dlwpcs_fill_missing': (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_int, c_int, c_void_p]),
     'dlwpcs_zonal_spectrum_scratch_bytes': (c_size_t, [c_void_p]),
     'dlwpcs_zonal_spectrum': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_sht_spectrum_scratch_bytes': (c_size_t, [c_void_p]),
+    'dlwpcs_sht_spectrum': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_ensemble_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_ensemble_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_count': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

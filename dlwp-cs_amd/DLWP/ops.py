@@ -2038,6 +2038,155 @@ def zonal_spectrum(a, b=None, lon_axis=-1, reduced=(), weights=None, n_wave=None
 
 
 # ------------------------------------------------------------------------------------------------------------------ #
+# Spherical-harmonic spectra (DLWP/verify.py spherical_spectrum / spherical_cross_spectrum / spherical_correlation),
+# include/dlwpcs.h dlwpcs_sht_spectrum; the tables come from DLWP/remap/spharm.py SphericalTransform
+# ------------------------------------------------------------------------------------------------------------------ #
+
+_sht_groups = {}            # (leading shape, reduced axes, device) -> (group_start, row_index) int32 device tensors
+
+
+def sht_desc(nlat, L, T, dims, lat_strides):
+    """nat.ShtSpectrumDesc of fields of nlat x L points analysed up to degree T: `dims` the leading dims of spectrum_dims (all
+    kept: they index the fields), lat_strides the element stride of the latitude axis in a and in b"""
+    if len(dims) > nat.SCORE_MAX_DIMS:
+        raise NotImplementedError('spherical_spectrum: more than %d leading dims after merging' % nat.SCORE_MAX_DIMS)
+    d = nat.ShtSpectrumDesc()
+    d.nlat, d.L, d.T, d.n_dims = int(nlat), int(L), int(T), len(dims)
+    d.lat_stride[0], d.lat_stride[1] = int(lat_strides[0]), int(lat_strides[1])
+    for i, (e, st, _) in enumerate(dims):
+        d.ext[i] = e
+        for k in range(2):
+            d.stride[k][i] = st[k]
+    return d
+
+
+def sht_launch(d, a, b, twiddle, table, out, skipped=None):
+    """dlwpcs_sht_spectrum on the current stream: device tensors a, b (None: single form) addressed by the descriptor, into the
+    float32 tensor `out` ((3,) fields, T + 1) and the int32 tensor `skipped` (fields; None: not wanted)"""
+    dev = a.device
+    nbytes = int(lib().dlwpcs_sht_spectrum_scratch_bytes(ctypes.byref(d)))
+    scratch = _workspace(nbytes, dev, 'sht') if nbytes else None
+    with torch.cuda.device(dev):
+        check(lib().dlwpcs_sht_spectrum(ctypes.byref(d), ptr(a), ptr(b) or None, ptr(twiddle), ptr(table), ptr(scratch) or None,
+                                        ptr(out), ptr(skipped) or None, stream_ptr()), 'dlwpcs_sht_spectrum')
+    return out
+
+
+def sht_groups_host(lead, red):
+    """(group_start, row_index) of dlwpcs_group_mean for fields numbered row-major over the leading shape `lead`: a group per
+    index of the kept axes (row-major), its members the fields over the averaged axes `red` in row-major order.  numpy only."""
+    lead = tuple(int(e) for e in lead)
+    kept = [i for i in range(len(lead)) if i not in red]
+    idx = np.arange(int(np.prod(lead, dtype=np.int64)), dtype=np.int64).reshape(lead)
+    n_groups = int(np.prod([lead[i] for i in kept], dtype=np.int64))
+    idx = idx.transpose(kept + sorted(red)).reshape(n_groups, -1)
+    return np.arange(n_groups + 1, dtype=np.int64) * idx.shape[1], idx.reshape(-1)
+
+
+def _sht_group_tables(lead, red, dev):
+    key = (tuple(lead), tuple(sorted(red)), str(dev))
+    hit = _sht_groups.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise nat.NativeError('spherical_spectrum: first use of this averaging inside a graph capture (run it once eagerly first)')
+        gs, ri = sht_groups_host(lead, red)
+        if ri.size >= 1 << 31:
+            raise NotImplementedError('spherical_spectrum: too many fields')
+        hit = (torch.from_numpy(gs.astype(np.int32)).to(dev), torch.from_numpy(ri.astype(np.int32)).to(dev))
+        _sht_groups[key] = hit
+    return hit
+
+
+def spherical_spectrum(a, b=None, transform=None, lat_axis=-2, lon_axis=-1, reduced=(), counts=False):
+    """
+    Spherical-harmonic power spectrum S_n = sum_{m<=n} c_m |a_n^m|^2 (n = 0 .. T) of the float32 device tensor `a`, whose
+    `lat_axis` and `lon_axis` hold the grid of `transform` (a DLWP.remap.spharm.SphericalTransform: it states the definitions,
+    fixes T and holds the tables), as the mean over the axes `reduced` (axes of `a`, neither of the two grid axes) of the fields
+    whose values are all finite.  The area weighting is part of the transform.
+    Returns a float32 device tensor (kept axes..., T + 1); with b (same shape as a), the pair form: (3, kept axes..., T + 1) = S_aa,
+    S_bb and the co-spectrum sum_m c_m Re(a_n^m conj b_n^m); a field counts only when it is finite in both.  A result without a
+    counted field is NaN.  counts=True: also the int32 tensor (kept axes...) of fields that did not count.
+    Two launches of dlwpcs_sht_spectrum and, when something is averaged, dlwpcs_group_mean (fp64, fixed order) on the current
+    stream, no host synchronisation (the tables of a transform and of an averaging are uploaded at their first use).
+    """
+    if transform is None:
+        raise TypeError('spherical_spectrum: a SphericalTransform is required')
+    require_device(a, 'spherical_spectrum')
+    ops = [a] if b is None else [a, b]
+    for t in ops:
+        require_device(t, 'spherical_spectrum')
+        if t.dtype != torch.float32:
+            raise TypeError('spherical_spectrum: operands must be float32, got %s' % t.dtype)
+        if t.device != a.device or t.shape != a.shape:
+            raise ValueError('spherical_spectrum: the two operands must have one shape and one device')
+    nd = a.dim()
+    if nd < 2:
+        raise ValueError('spherical_spectrum: the input needs a latitude and a longitude axis')
+    lat, lon = int(lat_axis), int(lon_axis)
+    if not (-nd <= lat < nd and -nd <= lon < nd) or lat % nd == lon % nd:
+        raise ValueError('spherical_spectrum: lat_axis %d and lon_axis %d must be two axes of the %d' % (lat, lon, nd))
+    lat, lon = lat % nd, lon % nd
+    nlat, L, T = int(a.shape[lat]), int(a.shape[lon]), int(transform.truncation)
+    if (nlat, L) != (transform.nlat, transform.n_lon):
+        raise ValueError('spherical_spectrum: the grid axes hold %d x %d points, the transform is for %d x %d'
+                         % (nlat, L, transform.nlat, transform.n_lon))
+    if L > SPECTRUM_MAX_L:
+        raise NotImplementedError('spherical_spectrum: %d longitudes, the kernel serves 2 .. %d' % (L, SPECTRUM_MAX_L))
+    if nlat > nat.SHT_MAX_NLAT:
+        raise NotImplementedError('spherical_spectrum: %d latitudes, the kernel serves 2 .. %d' % (nlat, nat.SHT_MAX_NLAT))
+    lead_axes = [i for i in range(nd) if i not in (lat, lon)]
+    red = set()
+    for r in reduced:
+        r = int(r)
+        if r < -nd or r >= nd or r % nd in (lat, lon):
+            raise ValueError('spherical_spectrum: reduced axis %d is out of range or a grid axis' % r)
+        red.add(lead_axes.index(r % nd))                # its place among the leading axes
+    # longitude last and unit-stride: a view where that is possible, else one copy (the latitude axis keeps its own stride)
+    ops = [t.permute(lead_axes + [lat, lon]) for t in ops]
+    ops = [t.contiguous() if t.stride(-1) != 1 else t for t in ops]
+    lead = tuple(int(e) for e in ops[0].shape[:-2])
+    strides = [tuple(int(s) for s in t.stride()[:-2]) for t in ops]
+    lat_strides = [int(t.stride(-2)) for t in ops]
+    if b is None:
+        strides.append((0,) * len(lead))
+        lat_strides.append(0)
+    kept_shape = [lead[i] for i in range(len(lead)) if i not in red]
+    nq = [] if b is None else [3]
+    K = T + 1
+    dev = a.device
+    fields = int(np.prod(lead, dtype=np.int64))
+    out = torch.empty(nq + kept_shape + [K], dtype=torch.float32, device=dev)
+    cnt = torch.empty(kept_shape, dtype=torch.int32, device=dev) if counts else None
+    if fields == 0 or out.numel() == 0:
+        if out.numel():
+            out.fill_(float('nan'))
+        if cnt is not None:
+            cnt.zero_()
+        return (out, cnt) if counts else out
+    twiddle, table = transform.device_tables(dev)
+    averaged = any(lead[i] != 1 for i in red)
+    rows = out.view(nq + [fields, K]) if not averaged else torch.empty(nq + [fields, K], dtype=torch.float32, device=dev)
+    flags = torch.empty((fields,), dtype=torch.int32, device=dev) if counts else None
+    d = sht_desc(nlat, L, T, spectrum_dims(lead, strides, ()), lat_strides)
+    sht_launch(d, ops[0], ops[1] if b is not None else None, twiddle, table, rows, flags)
+    if averaged:
+        gs_d, ri_d = _sht_group_tables(lead, red, dev)
+        n_groups, longest = int(gs_d.numel()) - 1, fields // max(int(gs_d.numel()) - 1, 1)
+        row_axis = len(nq)
+        rd, mean = _rows_desc(rows, row_axis, None, n_groups)
+        with torch.cuda.device(dev):
+            nbytes = int(lib().dlwpcs_group_mean_scratch_bytes(ctypes.byref(rd), n_groups, longest, -1))
+            scratch = _workspace(nbytes, dev, 'sht_mean') if nbytes else None
+            check(lib().dlwpcs_group_mean(ctypes.byref(rd), rows.data_ptr(), gs_d.data_ptr(), ri_d.data_ptr(), n_groups, longest, -1,
+                                          mean.data_ptr(), None, ptr(scratch), nbytes, stream_ptr()), 'dlwpcs_group_mean')
+        out = mean.view(nq + kept_shape + [K])
+    if counts:
+        full = flags.view(lead)
+        cnt = full.sum(dim=tuple(sorted(red)), dtype=torch.int32) if red else full
+    return (out, cnt) if counts else out
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
 # Ensemble scores (DLWP/verify.py ensemble_* / rank_histogram), include/dlwpcs.h dlwpcs_ensemble_stats
 # ------------------------------------------------------------------------------------------------------------------ #
 

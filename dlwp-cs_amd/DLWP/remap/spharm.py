@@ -1,0 +1,204 @@
+"""
+Spherical-harmonic analysis on lat-lon grids: the quadratures, the Legendre table and the host transform behind
+DLWP.verify.spherical_spectrum (device: ops.spherical_spectrum / dlwpcs_sht_spectrum, include/dlwpcs.h).  numpy only; torch is
+touched by SphericalTransform.device_tables alone.
+
+A field x[i, j] lies on nlat latitudes (mu_i = sin(lat_i), weights w_i >= 0 with sum w_i = 2) and L equally spaced longitudes.
+Pbar_n^m are the associated Legendre functions with (1/2) int Pbar_n^m Pbar_n'^m dmu = delta_nn' (no Condon-Shortley phase):
+    X_m(i) = sum_j x[i,j] exp(-2 pi i j m / L),   a_n^m = sum_i (w_i / 2) Pbar_n^m(mu_i) X_m(i) / L      (0 <= m <= n <= T)
+    S_n    = sum_{m=0..n} c_m |a_n^m|^2,   c_0 = 1, c_m = 2 otherwise.
+For a field band-limited to T, sum_n S_n is its area-weighted mean square; S_0 is the squared global mean.
+
+Three latitude layouts are recognised (either direction):
+    'gauss'            the nodes of numpy.polynomial.legendre.leggauss(nlat); exact for T <= nlat - 1
+    'clenshaw-curtis'  equally spaced with both poles; exact while 2 T <= nlat - 1
+    'fejer'            equally spaced cell centres (LatLonGrid.cells); exact while 2 T <= nlat - 1
+and every layout needs L >= 2 T + 1.
+"""
+import numpy as np
+
+KINDS = ('gauss', 'clenshaw-curtis', 'fejer')
+LAT_TOL = 1e-4              # degrees: latitude coordinates are often stored as float32
+
+
+def _nodes(kind, nlat):
+    """(colatitude in radians north to south or None, mu = sin(latitude) north to south) of a layout"""
+    if kind == 'gauss':
+        mu = -np.polynomial.legendre.leggauss(nlat)[0]
+        return None, mu
+    i = np.arange(nlat, dtype=np.float64)
+    theta = i * np.pi / (nlat - 1) if kind == 'clenshaw-curtis' else (2.0 * i + 1.0) * np.pi / (2.0 * nlat)
+    mu = np.cos(theta)
+    if kind == 'clenshaw-curtis':
+        mu[0], mu[-1] = 1.0, -1.0
+    return theta, mu
+
+
+def _weights(kind, nlat):
+    """the quadrature weights north to south, float64, summing to 2"""
+    if kind == 'gauss':
+        return np.polynomial.legendre.leggauss(nlat)[1][::-1].copy()
+    theta, _ = _nodes(kind, nlat)
+    if kind == 'clenshaw-curtis':
+        N = nlat - 1
+        c = np.full(nlat, 2.0)
+        c[0] = c[-1] = 1.0
+        s = np.zeros(nlat)
+        for k in range(1, N // 2 + 1):
+            s += (1.0 if 2 * k == N else 2.0) * np.cos(2 * k * theta) / (4.0 * k * k - 1.0)
+        return c / N * (1.0 - s)
+    s = np.zeros(nlat)
+    for k in range(1, nlat // 2 + 1):
+        s += np.cos(2 * k * theta) / (4.0 * k * k - 1.0)
+    return 2.0 / nlat * (1.0 - 2.0 * s)
+
+
+def _classify(lat):
+    """(kind, flipped): the layout of a latitude vector in degrees; flipped when it runs south to north"""
+    lat = np.asarray(getattr(lat, 'values', lat), dtype=np.float64).reshape(-1)
+    nlat = lat.size
+    if nlat < 2 or not np.all(np.isfinite(lat)):
+        raise ValueError('latitude_quadrature: at least 2 finite latitudes are needed')
+    flipped = bool(lat[0] < lat[-1])
+    d = lat[::-1] if flipped else lat
+    for kind in ('clenshaw-curtis', 'fejer', 'gauss'):
+        if kind == 'clenshaw-curtis':
+            want = 90.0 - 180.0 * np.arange(nlat) / (nlat - 1)
+        elif kind == 'fejer':
+            want = 90.0 - 180.0 * (2.0 * np.arange(nlat) + 1.0) / (2.0 * nlat)
+        else:
+            want = np.degrees(np.arcsin(_nodes(kind, nlat)[1]))
+        if np.abs(d - want).max() <= LAT_TOL:
+            return kind, flipped
+    raise ValueError('latitude_quadrature: %d latitudes from %g to %g are neither Gaussian nor equally spaced with both poles '
+                     'nor equally spaced cell centres' % (nlat, lat[0], lat[-1]))
+
+
+def latitude_quadrature(lat):
+    """(kind, weights): the layout of the latitude vector `lat` (degrees, either direction) -- 'gauss', 'clenshaw-curtis' or
+    'fejer' -- and its float64 quadrature weights in the order of `lat`, w_i >= 0, sum w_i = 2.  Any other vector is refused."""
+    kind, flipped = _classify(lat)
+    w = _weights(kind, np.asarray(getattr(lat, 'values', lat)).size)
+    return kind, (w[::-1].copy() if flipped else w)
+
+
+def max_truncation(kind, nlat, n_lon):
+    """the largest truncation the quadrature and the longitudes allow"""
+    t_lat = nlat - 1 if kind == 'gauss' else (nlat - 1) // 2
+    return max(min(t_lat, (int(n_lon) - 1) // 2), 0)
+
+
+def packed_rows(T):
+    return (T + 1) * (T + 2) // 2
+
+
+def packed_row(m, n, T):
+    """row of (m, n) in the packed table: orders outermost, within an order the degrees n = m .. T"""
+    return m * (T + 1) - m * (m - 1) // 2 + (n - m)
+
+
+def legendre_functions(mu, T):
+    """Pbar_n^m(mu_i) for 0 <= m <= n <= T, packed rows x len(mu), float64, by the three-term recurrence in n"""
+    mu = np.asarray(mu, dtype=np.float64)
+    cos_lat = np.sqrt(np.maximum(1.0 - mu * mu, 0.0))
+    P = np.zeros((packed_rows(T), mu.size))
+    pmm = np.ones(mu.size)
+    for m in range(T + 1):
+        if m > 0:
+            pmm = np.sqrt((2.0 * m + 1.0) / (2.0 * m)) * cos_lat * pmm
+        r = packed_row(m, m, T)
+        P[r] = pmm
+        if m < T:
+            P[r + 1] = np.sqrt(2.0 * m + 3.0) * mu * pmm
+        for n in range(m + 2, T + 1):
+            A = np.sqrt((4.0 * n * n - 1.0) / (n * n - m * m))
+            B = np.sqrt(((n - 1.0) ** 2 - m * m) / (4.0 * (n - 1.0) ** 2 - 1.0))
+            P[r + n - m] = A * (mu * P[r + n - m - 1] - B * P[r + n - m - 2])
+    return P
+
+
+def legendre_table(lat, truncation):
+    """(float32 packed table (rows, nlat padded with zeros to a multiple of 4), its float64 parent (rows, nlat)):
+    (w_i / 2) Pbar_n^m(mu_i) in the order of `lat`, row packed_row(m, n, T); every entry evaluated in float64 and rounded once"""
+    kind, flipped = _classify(lat)
+    nlat = np.asarray(getattr(lat, 'values', lat)).size
+    T = int(truncation)
+    if T < 0 or T > (nlat - 1 if kind == 'gauss' else (nlat - 1) // 2):
+        raise ValueError("legendre_table: truncation %d is outside what %d '%s' latitudes integrate exactly (0 .. %d)"
+                         % (T, nlat, kind, nlat - 1 if kind == 'gauss' else (nlat - 1) // 2))
+    mu, w = _nodes(kind, nlat)[1], _weights(kind, nlat)
+    t64 = legendre_functions(mu, T) * (0.5 * w)[None, :]
+    if flipped:
+        t64 = np.ascontiguousarray(t64[:, ::-1])
+    t32 = np.zeros((t64.shape[0], (nlat + 3) // 4 * 4), dtype=np.float32)
+    t32[:, :nlat] = t64
+    return t32, t64
+
+
+class SphericalTransform(object):
+    """The analysis of fields on `lat` (degrees) x n_lon longitudes up to `truncation` (None: the largest the grid allows):
+    kind, weights, truncation, the packed tables, and one device copy of the float32 table and the twiddles per device."""
+
+    def __init__(self, lat, n_lon, truncation=None):
+        self.lat = np.asarray(getattr(lat, 'values', lat), dtype=np.float64).reshape(-1).copy()
+        self.kind, self.weights = latitude_quadrature(self.lat)
+        self.nlat, self.n_lon = self.lat.size, int(n_lon)
+        if self.n_lon < 2:
+            raise ValueError('SphericalTransform: %d longitudes (at least 2)' % self.n_lon)
+        most = max_truncation(self.kind, self.nlat, self.n_lon)
+        if truncation is None:
+            truncation = most
+        T = int(truncation)
+        if T < 0:
+            raise ValueError('SphericalTransform: truncation %d is negative' % T)
+        if 2 * T + 1 > self.n_lon:
+            raise ValueError('SphericalTransform: truncation %d needs at least %d longitudes, the grid has %d'
+                             % (T, 2 * T + 1, self.n_lon))
+        if T > most:
+            raise ValueError("SphericalTransform: truncation %d is above %d, the largest that %d '%s' latitudes integrate exactly"
+                             % (T, most, self.nlat, self.kind))
+        self.truncation = T
+        self.table32, self.table64 = legendre_table(self.lat, T)
+        self._device = {}
+
+    def device_tables(self, device):
+        """(twiddle table, Legendre table) on `device`, uploaded at the first use there (not inside a graph capture)"""
+        import torch
+        from .. import ops
+        key = str(torch.device(device))
+        hit = self._device.get(key)
+        if hit is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise ops.nat.NativeError('spherical_spectrum: first use of this transform inside a graph capture (run it once '
+                                          'eagerly first)')
+            hit = (ops.spectrum_twiddle(self.n_lon, device), torch.from_numpy(self.table32).to(device))
+            self._device[key] = hit
+        return hit
+
+    def coefficients(self, x):
+        """a_n^m of float64 fields x (..., nlat, n_lon): complex (..., packed rows)"""
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape[-2:] != (self.nlat, self.n_lon):
+            raise ValueError('SphericalTransform: fields of %s, the transform is for %s' % (x.shape[-2:], (self.nlat, self.n_lon)))
+        T = self.truncation
+        X = np.fft.rfft(x, axis=-1)[..., :T + 1] / self.n_lon
+        a = np.empty(x.shape[:-2] + (packed_rows(T),), dtype=np.complex128)
+        for m in range(T + 1):
+            r = packed_row(m, m, T)
+            a[..., r:r + T + 1 - m] = np.einsum('ni,...i->...n', self.table64[r:r + T + 1 - m], X[..., m])
+        return a
+
+    def power(self, f, v=None):
+        """(nq, ..., T + 1) float64: S_n of f; with v also S_n of v and the co-spectrum sum_m c_m Re(a_f conj a_v)"""
+        T = self.truncation
+        af = self.coefficients(f)
+        av = af if v is None else self.coefficients(v)
+        prods = [af.real ** 2 + af.imag ** 2]
+        if v is not None:
+            prods += [av.real ** 2 + av.imag ** 2, (af * np.conj(av)).real]
+        out = np.zeros((len(prods),) + af.shape[:-1] + (T + 1,))
+        for m in range(T + 1):
+            r = packed_row(m, m, T)
+            for q, p in enumerate(prods):
+                out[q][..., m:] += (1.0 if m == 0 else 2.0) * p[..., r:r + T + 1 - m]
+        return out

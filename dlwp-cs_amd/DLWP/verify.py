@@ -972,6 +972,163 @@ def zonal_coherence(forecast, valid, lon_axis=-1, axis=None, weighted=False, wei
 
 
 # --------------------------------------------------------------------------------------------------------------------- #
+# Spherical-harmonic spectra: power per total wavenumber
+# --------------------------------------------------------------------------------------------------------------------- #
+#
+# The zonal spectrum treats a row at 80 N like a row at the equator and names no scale in kilometres.  The spherical-harmonic
+# spectrum S_n = sum_{m<=n} c_m |a_n^m|^2 (DLWP/remap/spharm.py states the definitions) is the power per total wavenumber n that
+# the literature reports: sum_n S_n is the area-weighted mean square of a band-limited field, S_0 its squared global mean, and
+# degree n is a wavelength of 40 000 km / n.  The latitudes must be Gaussian, equally spaced with both poles, or equally spaced
+# cell centres; the area weighting is inside the transform.  numpy inputs are transformed on the host (np.fft.rfft and the float64
+# Legendre table), device tensors by dlwpcs_sht_spectrum; neither path falls back to the other.
+
+SphericalCrossSpectrum = namedtuple('SphericalCrossSpectrum', ['power_f', 'power_v', 'co'])
+_transforms = {}
+
+
+def _spherical_transform(lat, n_lon, truncation):
+    from .remap.spharm import SphericalTransform
+    lat = np.asarray(_host(lat), dtype=np.float64).reshape(-1)
+    key = (lat.tobytes(), int(n_lon), None if truncation is None else int(truncation))
+    hit = _transforms.get(key)
+    if hit is None:
+        hit = _transforms[key] = SphericalTransform(lat, n_lon, truncation)
+    return hit
+
+
+def _grid_axis(x, name, given):
+    nd = len(x.shape)
+    if hasattr(x, 'dims') and name in tuple(x.dims):
+        return tuple(x.dims).index(name)
+    a = int(given)
+    if a < -nd or a >= nd:
+        raise ValueError('%s_axis %d out of range of %d axes' % (name, a, nd))
+    return a % nd
+
+
+def _sht_host(f, v, la, lo, ax, tr):
+    """numpy twin of ops.spherical_spectrum: (quantities (nq, kept..., T + 1) float64, skipped fields (kept...) int32)"""
+    arrs = [np.moveaxis(np.asarray(x, dtype=np.float64), (la, lo), (-2, -1)) for x in ((f,) if v is None else (f, v))]
+    lead_axes = [i for i in range(arrs[0].ndim) if i not in (la, lo)]
+    red = tuple(lead_axes.index(a) for a in ax)
+    counted = np.ones(arrs[0].shape[:-2], dtype=bool)
+    for x in arrs:
+        counted &= np.isfinite(x).all(axis=(-2, -1))
+    arrs = [np.where(counted[..., None, None], x, 0.0) for x in arrs]
+    q = tr.power(arrs[0], None if v is None else arrs[1])
+    n = counted.sum(axis=red) if red else counted.astype(np.int64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        total = (q * counted[..., None]).sum(axis=tuple(r + 1 for r in red)) if red else q * counted[..., None]
+        out = np.where(n[..., None] == 0, np.nan, total / np.maximum(n, 1)[..., None])
+    skipped = (~counted).sum(axis=red) if red else (~counted).astype(np.int64)
+    return out, np.asarray(skipped, dtype=np.int32)
+
+
+def _sht(f, v, lat, lat_axis, lon_axis, axis, truncation):
+    """(quantities (nq, kept..., T + 1) float64, skipped, kept dim names or None)"""
+    if v is not None:
+        if len(v.shape) == len(f.shape) - 1:
+            raise NotImplementedError('the lagged form against a continuous verification series (valid[f + t]) is not served: '
+                                      'aligned arrays of one shape are')
+        _check_labels(f, v)
+        if tuple(f.shape) != tuple(v.shape):
+            raise ValueError('forecast %s and verification %s must have one shape' % (tuple(f.shape), tuple(v.shape)))
+    if len(f.shape) < 2:
+        raise ValueError('the input needs a latitude and a longitude axis')
+    la, lo = _grid_axis(f, 'lat', lat_axis), _grid_axis(f, 'lon', lon_axis)
+    if la == lo:
+        raise ValueError('the latitude and the longitude axis must differ')
+    if lat is None:
+        coords = getattr(f, 'coords', {})
+        lat = coords['lat'] if 'lat' in coords else getattr(f, 'lat', None)
+        if lat is None:
+            raise ValueError("the latitudes are needed: pass lat=, or a labelled input with a 'lat' coordinate")
+    lat = np.asarray(_host(lat), dtype=np.float64).reshape(-1)
+    if lat.size != int(f.shape[la]):
+        raise ValueError('%d latitudes for a latitude axis of %d' % (lat.size, int(f.shape[la])))
+    tr = _spherical_transform(lat, int(f.shape[lo]), truncation)
+    nd = len(f.shape)
+    if axis is None:
+        ax = tuple(i for i in range(nd) if i not in (la, lo))
+    else:
+        ax = (axis,) if isinstance(axis, (int, np.integer, str)) else tuple(axis)
+        ax = _axes(tuple(tuple(f.dims).index(a) if isinstance(a, str) else a for a in ax), nd)
+        if la in ax or lo in ax:
+            raise ValueError('the latitude and longitude axes are transformed, they cannot be averaged over')
+    if _on_device(f, v):
+        import torch
+        from . import ops as dops
+        dev = next(_raw(x).device for x in (f, v) if x is not None and _is_tensor(_raw(x)) and _raw(x).is_cuda)
+        with torch.cuda.device(dev):
+            ft = _dev_operand(f, dev)
+            vt = _dev_operand(v, dev) if v is not None else None
+            out, cnt = dops.spherical_spectrum(ft, vt, transform=tr, lat_axis=la, lon_axis=lo, reduced=ax, counts=True)
+            out = out.cpu().numpy().astype(np.float64)
+            out, skipped = (out[None] if v is None else out), cnt.cpu().numpy()
+    else:
+        out, skipped = _sht_host(_host(f), None if v is None else _host(v), la, lo, ax, tr)
+    dims = tuple(d for i, d in enumerate(f.dims) if i not in (la, lo) and i not in ax) if hasattr(f, 'dims') else None
+    return out, skipped, dims
+
+
+def _label_degree(values, dims, src, name):
+    """a Forecast over the kept dims of `src` plus 'degree' when the input was labelled, else the array"""
+    if dims is None:
+        return values
+    coords = {d: np.asarray(getattr(src.coords[d], 'values', src.coords[d])) for d in dims if d in getattr(src, 'coords', {})}
+    coords['degree'] = np.arange(values.shape[-1])
+    return Forecast(values, dims + ('degree',), coords, name=name)
+
+
+def spherical_spectrum(x, lat=None, lat_axis=-2, lon_axis=-1, axis=None, truncation=None, return_count=False):
+    """
+    Spherical-harmonic power spectrum S_n = sum_{m<=n} c_m |a_n^m|^2 of `x`, n = 0 .. truncation, averaged over `axis`.
+
+    There is no `weighted=` argument: the area weighting is inside the transform (the quadrature weights of the latitudes).
+
+    :param x: ndarray, device tensor or labelled array (its dims 'lat' and 'lon' are the grid axes, its coordinate 'lat' the
+        latitudes)
+    :param lat: the latitudes in degrees, either direction: Gaussian, equally spaced with both poles (181 latitudes), or equally
+        spaced cell centres; any other vector is refused.  Needed for unlabelled inputs.
+    :param lat_axis, lon_axis: the grid axes of an unlabelled input
+    :param axis: int, dim name, tuple or None: the axes averaged over (None: all but the grid axes).  A field counts only when
+        all of its values are finite.
+    :param truncation: the largest degree; None: the largest the grid allows -- nlat - 1 for Gaussian latitudes,
+        (nlat - 1) // 2 for the equally spaced ones, and (n_lon - 1) // 2.  A larger one is a ValueError.
+    :param return_count: also return the number of fields per result that did not count
+    :return: float64 array (kept axes..., degree), labelled like the input; NaN where no field counts
+    """
+    out, skipped, dims = _sht(x, None, lat, lat_axis, lon_axis, axis, truncation)
+    res = _label_degree(out[0], dims, x, 'spherical_spectrum')
+    return (res, skipped) if return_count else res
+
+
+def spherical_cross_spectrum(forecast, valid, lat=None, lat_axis=-2, lon_axis=-1, axis=None, truncation=None, return_count=False):
+    """
+    Spherical-harmonic spectra of a forecast and its verification (aligned arrays of one shape) and their co-spectrum, averaged
+    over `axis`: SphericalCrossSpectrum(power_f, power_v, co) with co_n = sum_m c_m Re(a_n^m(f) conj a_n^m(v)).  The imaginary
+    part is not invariant under rotations and is not returned.  A field counts only when it is finite in both arrays.  Arguments as
+    for `spherical_spectrum`; a continuous verification series (one axis fewer) raises NotImplementedError.
+    """
+    out, skipped, dims = _sht(forecast, valid, lat, lat_axis, lon_axis, axis, truncation)
+    res = SphericalCrossSpectrum(*[_label_degree(out[i], dims, forecast, n) for i, n in enumerate(SphericalCrossSpectrum._fields)])
+    return (res, skipped) if return_count else res
+
+
+def spherical_correlation(forecast, valid, lat=None, lat_axis=-2, lon_axis=-1, axis=None, truncation=None, return_count=False):
+    """
+    Correlation per degree co / sqrt(power_f power_v), formed from the AVERAGED quantities of `spherical_cross_spectrum`: the
+    anomaly correlation of the two fields restricted to total wavenumber n.  NaN where either power is 0.  Arguments as for
+    `spherical_spectrum`.
+    """
+    out, skipped, dims = _sht(forecast, valid, lat, lat_axis, lon_axis, axis, truncation)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        cor = out[2] / np.sqrt(out[0] * out[1])
+    res = _label_degree(cor, dims, forecast, 'spherical_correlation')
+    return (res, skipped) if return_count else res
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
 # Ensembles: probabilistic scores over a member axis
 # --------------------------------------------------------------------------------------------------------------------- #
 #

@@ -1,0 +1,446 @@
+// Spherical-harmonic power spectra (dlwpcs_sht_spectrum, include/dlwpcs.h states the definitions): power per total wavenumber n
+// of fields x[i, j] on nlat latitudes and L longitudes,
+//   X_m(i) = sum_j x[i,j] exp(-2 pi i j m / L),  a_n^m = sum_i t[(m,n)][i] X_m(i) / L,  S_n = sum_{m<=n} c_m |a_n^m|^2,
+// t = (w_i / 2) Pbar_n^m(mu_i) the caller's fp32 Legendre table.  Two launches, no atomics.
+//
+// Stage A (sht_fourier_kernel), the longitude transform.  All latitude rows of all fields form one list of fields * nlat rows; a
+// workgroup of four waves owns 32 of them and 128 orders m.  It is the matrix product of spectrum.hip with the operands swapped:
+// the twiddles are the A operand and the rows the B operand of v_mfma_f32_32x32x2_f32, so that a lane ends up with ONE row and 16
+// orders, and the 32 lanes of a half wave store 32 neighbouring latitudes of one (field, m, re | im) line of the scratch
+//   xs[operand][field][m][re | im][nlat_pad]            (nlat_pad = nlat rounded up to 4; stage B reads it with unit stride along i).
+// Rows come through LDS in chunks of 64 longitudes, the twiddles {cos, -sin}(2 pi k / L) from the length-L table in LDS at the
+// reduced index (j m) mod L carried along in integers, exactly as in spectrum.hip.  The workgroups of the first 128 orders also
+// write bad[field][i]: 1 when row i of the field holds a NaN or an infinity (pair form: in either operand).
+//
+// Stage B (sht_legendre_kernel), the latitude transform and the power.  A workgroup is ONE wave and owns 32 degrees x 32 fields.  It
+// walks m = 0 .. its last degree in order; per m the product (32 degrees x nlat) . (nlat x 32 fields) runs twice (pair form: four
+// times) with the same A operand -- the table tile, rows (m, n) -- and the same column mapping, so Re and Im of a coefficient sit
+// in the same lane and register.  A lane loads 64 bytes of a table row and of an xs line per step (latitudes 32 t + 16 h ..+15, all
+// loads issued before the first MFMA) and feeds sixteen MFMAs per accumulator; degrees n < m and n > T are zero operands, latitudes
+// >= nlat are masked.  Then the fp32 products
+// Re^2 + Im^2 (pair: also S_bb and the co-spectrum) are widened to fp64, multiplied by c_m / L^2 and added to the lane's sums
+// in order of m; after the last m the sums are rounded to fp32 once.  The single form has the bits of the pair form's S_aa.
+//
+// The grid of stage B is (field tiles) x (degree tiles): a call with a handful of fields leaves most of the device idle, and the
+// degree tiles cost unequally (the top tile walks every m).  No m-split is built.
+#include "mfma_common.h"
+
+namespace dlwpcs {
+
+constexpr int SH_THREADS = 256;
+constexpr int SH_ROWS = 32;                 // latitude rows of a stage-A tile (the N of the MFMA)
+constexpr int SH_JC = 64;                   // longitudes per staged chunk
+constexpr int SH_XS = SH_JC + 2;            // LDS row stride (floats), as in spectrum.hip
+constexpr int SH_MW = 32;                   // orders per wave
+constexpr int SH_MT = 4 * SH_MW;            // orders per workgroup
+constexpr int SH_MAX_L = 1728;              // the twiddle table of 2 L floats lives in static LDS
+constexpr int SH_TILE = 32;                 // stage B: degrees and fields of a workgroup
+constexpr int SH_KV = 4;                    // stage B: 16-byte loads of a lane per step and line (a step covers 2 * 4 * SH_KV latitudes)
+
+struct ShGeom {
+    int32_t nlat, nlp, L, T, n_dims, n_mt, n_nt;
+    int64_t fields, rows, n_rt, n_ft;
+    int64_t op_stride;                       // floats between the operands' halves of xs
+    int64_t lat_stride[2];
+    int64_t ext[DLWPCS_SCORE_MAX_DIMS];
+    int64_t stride[2][DLWPCS_SCORE_MAX_DIMS];
+};
+
+__device__ __forceinline__ bool sh_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// the three fp32 products of the pair form (q = 0 alone in the single form), spelled once so that both forms round alike
+__device__ __forceinline__ float sh_product(int q, float cf, float sf, float cv, float sv) {
+#pragma clang fp contract(off)
+    if (q == 0) return __builtin_fmaf(sf, sf, cf * cf);
+    if (q == 1) return __builtin_fmaf(sv, sv, cv * cv);
+    return __builtin_fmaf(sf, sv, cf * cv);                             // Re(a conj b)
+}
+__device__ __forceinline__ double sh_add(double sum, double v, double scale) {
+#pragma clang fp contract(off)
+    return sum + v * scale;
+}
+
+template <bool PAIR, bool VEC>
+__global__ void __launch_bounds__(SH_THREADS) sht_fourier_kernel(ShGeom G, const float *__restrict__ a, const float *__restrict__ b,
+                                                                 const float2 *__restrict__ twiddle, float *__restrict__ xs,
+                                                                 int32_t *__restrict__ bad) {
+    constexpr int NOP = PAIR ? 2 : 1;
+    constexpr int NLD = VEC ? 2 : 8;                    // loads of a thread per chunk and operand
+    __shared__ float2 s_tw[SH_MAX_L];
+    __shared__ __attribute__((aligned(16))) float s_x[NOP][SH_ROWS * SH_XS];
+    __shared__ int64_t s_off[NOP][SH_ROWS];
+    __shared__ int64_t s_line[SH_ROWS];                 // xs offset of (field, m = 0, re, latitude) of the slot's row
+    __shared__ int64_t s_flag[SH_ROWS];
+    __shared__ int s_valid[SH_ROWS], s_bad[SH_ROWS];
+
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= G.n_rt * G.n_mt) return;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int mt = (int)(bid % G.n_mt);
+    const int64_t rt = bid / G.n_mt;
+    const int L = G.L, K = G.T + 1;
+
+    for (int m = tid; m < L; m += SH_THREADS) s_tw[m] = twiddle[m];
+
+    const int r32 = lane & 31, h = lane >> 5;
+    const int kw = mt * SH_MT + wv * SH_MW + r32;       // this lane's order as the row of the A operand
+    const bool wave_on = mt * SH_MT + wv * SH_MW < K;
+    const int step4 = (int)((4ll * kw) % L);
+
+    if (tid < SH_ROWS) {
+        const int64_t r = rt * SH_ROWS + tid;
+        const bool valid = r < G.rows;
+        int64_t off[2] = {0, 0}, f = 0;
+        int i = 0;
+        if (valid) {
+            f = r / G.nlat;
+            i = (int)(r - f * G.nlat);
+            int64_t q = f;
+            for (int d = G.n_dims - 1; d >= 0; --d) {
+                const int64_t e = G.ext[d], c = q % e;
+                q /= e;
+                off[0] += c * G.stride[0][d];
+                off[1] += c * G.stride[1][d];
+            }
+            off[0] += (int64_t)i * G.lat_stride[0];
+            off[1] += (int64_t)i * G.lat_stride[1];
+        }
+        s_off[0][tid] = off[0];
+        if (PAIR) s_off[NOP - 1][tid] = off[1];
+        s_line[tid] = f * K * 2 * G.nlp + i;
+        s_flag[tid] = f * G.nlat + i;
+        s_valid[tid] = valid;
+        s_bad[tid] = 0;
+    }
+    __syncthreads();
+
+    // staging: the slot and column of this thread's loads are the same in every chunk
+    int ld_row[NLD], ld_col[NLD];
+    int64_t ld_off[NOP][NLD];
+    bool ld_ok[NLD];
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+        const int idx = tid + i * SH_THREADS;
+        ld_row[i] = VEC ? idx >> 4 : idx >> 6;
+        ld_col[i] = VEC ? (idx & 15) * 4 : idx & 63;
+        ld_ok[i] = s_valid[ld_row[i]] != 0;
+#pragma unroll
+        for (int op = 0; op < NOP; ++op) ld_off[op][i] = s_off[op][ld_row[i]];
+    }
+    const int n_chunks = (L + SH_JC - 1) / SH_JC;
+    unsigned bad_mask = 0;
+
+    float regs[NOP][NLD][VEC ? 4 : 1];
+    auto fetch = [&](int chunk) {
+        const int j0 = chunk * SH_JC;
+#pragma unroll
+        for (int op = 0; op < NOP; ++op) {
+            const float *src = op == 0 ? a : b;
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) {
+                const int j = j0 + ld_col[i];
+                if constexpr (VEC) {
+                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (ld_ok[i] && j < L) v = *reinterpret_cast<const float4 *>(src + ld_off[op][i] + j);   // (L % 4 == 0)
+                    regs[op][i][0] = v.x; regs[op][i][1] = v.y; regs[op][i][2] = v.z; regs[op][i][3] = v.w;
+                } else {
+                    regs[op][i][0] = (ld_ok[i] && j < L) ? src[ld_off[op][i] + j] : 0.f;
+                }
+            }
+        }
+    };
+    auto stash = [&]() {
+#pragma unroll
+        for (int op = 0; op < NOP; ++op)
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) {
+                float v[VEC ? 4 : 1];
+#pragma unroll
+                for (int e = 0; e < (VEC ? 4 : 1); ++e) {
+                    v[e] = regs[op][i][e];              // (zero outside the row: fetch has seen to it)
+                    if (sh_nonfinite(v[e])) bad_mask |= 1u << i;
+                }
+                float *dst = &s_x[op][ld_row[i] * SH_XS + ld_col[i]];
+                if constexpr (VEC) {
+                    *reinterpret_cast<float2 *>(dst) = make_float2(v[0], v[1]);
+                    *reinterpret_cast<float2 *>(dst + 2) = make_float2(v[VEC ? 2 : 0], v[VEC ? 3 : 0]);
+                } else {
+                    *dst = v[0];
+                }
+            }
+    };
+
+    f32x16 acc[NOP][2];
+#pragma unroll
+    for (int op = 0; op < NOP; ++op)
+#pragma unroll
+        for (int cs = 0; cs < 2; ++cs)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[op][cs][i] = 0.f;
+    // reduced twiddle indices of this lane's two longitudes per step: j = 4 t + 2 h + u, u = 0, 1
+    int m0 = (int)(((int64_t)(2 * h) * kw) % L), m1 = (int)(((int64_t)(2 * h + 1) * kw) % L);
+
+    fetch(0);
+    for (int chunk = 0; chunk < n_chunks; ++chunk) {
+        __syncthreads();                                // the previous chunk has been consumed
+        stash();
+        if (chunk + 1 == n_chunks) {
+#pragma unroll
+            for (int i = 0; i < NLD; ++i)
+                if (bad_mask & (1u << i)) s_bad[ld_row[i]] = 1;
+        }
+        __syncthreads();
+        if (chunk + 1 < n_chunks) fetch(chunk + 1);
+        if (wave_on) {
+            const int left = L - chunk * SH_JC;
+            const int nt = left >= SH_JC ? SH_JC / 4 : (left + 3) / 4;
+            for (int t = 0; t < nt; ++t) {
+                const float2 tw0 = s_tw[m0], tw1 = s_tw[m1];
+                float2 xv[NOP];
+#pragma unroll
+                for (int op = 0; op < NOP; ++op)
+                    xv[op] = *reinterpret_cast<const float2 *>(&s_x[op][r32 * SH_XS + 4 * t + 2 * h]);
+#pragma unroll
+                for (int op = 0; op < NOP; ++op) {
+                    acc[op][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(tw0.x, xv[op].x, acc[op][0], 0, 0, 0);
+                    acc[op][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(tw0.y, xv[op].x, acc[op][1], 0, 0, 0);
+                }
+#pragma unroll
+                for (int op = 0; op < NOP; ++op) {
+                    acc[op][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(tw1.x, xv[op].y, acc[op][0], 0, 0, 0);
+                    acc[op][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(tw1.y, xv[op].y, acc[op][1], 0, 0, 0);
+                }
+                m0 += step4; m0 -= m0 >= L ? L : 0;
+                m1 += step4; m1 -= m1 >= L ? L : 0;
+            }
+        }
+    }
+
+    // the lane holds row slot r32 (the column of the product) and the orders 8 (i >> 2) + 4 h + (i & 3) of its wave
+    if (wave_on && s_valid[r32]) {
+        const int64_t line = s_line[r32];
+#pragma unroll
+        for (int op = 0; op < NOP; ++op) {
+            float *dst = xs + op * G.op_stride + line;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int m = mt * SH_MT + wv * SH_MW + 8 * (i >> 2) + 4 * h + (i & 3);
+                if (m < K) {
+                    dst[((int64_t)m * 2) * G.nlp] = acc[op][0][i];
+                    dst[((int64_t)m * 2 + 1) * G.nlp] = acc[op][1][i];
+                }
+            }
+        }
+    }
+    if (mt == 0 && tid < SH_ROWS && s_valid[tid]) bad[s_flag[tid]] = s_bad[tid];
+}
+
+template <bool PAIR>
+__global__ void __launch_bounds__(64) sht_legendre_kernel(ShGeom G, const float *__restrict__ xs, const int32_t *__restrict__ bad,
+                                                          const float *__restrict__ table, float *__restrict__ out,
+                                                          int32_t *__restrict__ skipped) {
+    constexpr int NOP = PAIR ? 2 : 1;
+    constexpr int NQ = PAIR ? 3 : 1;
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= G.n_ft * G.n_nt) return;
+    const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
+    const int nt = (int)(bid % G.n_nt);
+    const int64_t ft = bid / G.n_nt;
+    const int T = G.T, K = T + 1, nlat = G.nlat, nlp = G.nlp;
+    const int n0 = nt * SH_TILE;
+    const int nA = n0 + r32;                             // this lane's degree as the row of the A operand
+    const int64_t fB = ft * SH_TILE + r32;               // this lane's field as the column of the B operand
+    const bool f_ok = fB < G.fields;
+
+    int isbad = 0;
+    if (f_ok)
+        for (int i = h; i < nlat; i += 2) isbad |= bad[fB * nlat + i];
+    isbad |= __shfl_xor(isbad, 32, 64);
+
+    double sum[NQ][16];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sum[q][i] = 0.0;
+
+    const int m_last = n0 + SH_TILE - 1 < T ? n0 + SH_TILE - 1 : T;
+    const int n_steps = (nlp + 2 * SH_KV * 4 - 1) / (2 * SH_KV * 4);
+    const double inv_l2 = 1.0 / ((double)G.L * (double)G.L);
+    for (int m = 0; m <= m_last; ++m) {
+        f32x16 acc[NOP][2];
+#pragma unroll
+        for (int op = 0; op < NOP; ++op)
+#pragma unroll
+            for (int cs = 0; cs < 2; ++cs)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[op][cs][i] = 0.f;
+        const bool a_on = nA >= m && nA <= T;
+        const int64_t row = (int64_t)m * K - (int64_t)m * (m - 1) / 2 + (nA - m);
+        const float *pa = table + (a_on ? row : 0) * nlp;
+        const float *pb = xs + (((f_ok ? fB : 0) * K + m) * 2) * nlp;
+        for (int t = 0; t < n_steps; ++t) {
+            // all loads of the step are issued before its first MFMA: one wait per 32 latitudes
+            const int i0 = 2 * SH_KV * 4 * t + SH_KV * 4 * h;
+            float4 av[SH_KV], xv[NOP][2][SH_KV];
+#pragma unroll
+            for (int u = 0; u < SH_KV; ++u) {
+                const int iu = i0 + 4 * u;
+                const bool in = iu < nlp;                // (nlp is a multiple of 4: the 16 bytes lie inside the line or outside)
+                av[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (a_on && in) av[u] = *reinterpret_cast<const float4 *>(pa + iu);
+#pragma unroll
+                for (int op = 0; op < NOP; ++op)
+#pragma unroll
+                    for (int cs = 0; cs < 2; ++cs) {
+                        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                        if (f_ok && in) v = *reinterpret_cast<const float4 *>(pb + op * G.op_stride + (int64_t)cs * nlp + iu);
+                        v.x = iu < nlat ? v.x : 0.f;    // the padding of xs is never written
+                        v.y = iu + 1 < nlat ? v.y : 0.f;
+                        v.z = iu + 2 < nlat ? v.z : 0.f;
+                        v.w = iu + 3 < nlat ? v.w : 0.f;
+                        xv[op][cs][u] = v;
+                    }
+            }
+#pragma unroll
+            for (int u = 0; u < SH_KV; ++u) {
+                if (2 * SH_KV * 4 * t + 4 * u >= nlp) break;        // (wave-uniform: both halves of these MFMAs lie beyond the lines)
+#pragma unroll
+                for (int op = 0; op < NOP; ++op)
+#pragma unroll
+                    for (int cs = 0; cs < 2; ++cs) {
+                        const float4 x = xv[op][cs][u];
+                        acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].x, x.x, acc[op][cs], 0, 0, 0);
+                        acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].y, x.y, acc[op][cs], 0, 0, 0);
+                        acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].z, x.z, acc[op][cs], 0, 0, 0);
+                        acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].w, x.w, acc[op][cs], 0, 0, 0);
+                    }
+            }
+        }
+        const double scale = (m == 0 ? 1.0 : 2.0) * inv_l2;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float cf = acc[0][0][i], sf = acc[0][1][i], cv = acc[NOP - 1][0][i], sv = acc[NOP - 1][1][i];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) sum[q][i] = sh_add(sum[q][i], (double)sh_product(q, cf, sf, cv, sv), scale);
+        }
+    }
+
+    // the lane holds field fB (the column) and the degrees n0 + 8 (i >> 2) + 4 h + (i & 3)
+    if (f_ok) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int n = n0 + 8 * (i >> 2) + 4 * h + (i & 3);
+            if (n > T) continue;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q)
+                out[((int64_t)q * G.fields + fB) * K + n] = isbad ? __uint_as_float(0x7fc00000u) : (float)sum[q][i];
+        }
+        if (skipped && nt == 0 && h == 0) skipped[fB] = isbad ? 1 : 0;
+    }
+}
+
+namespace {
+
+struct ShPlan {
+    ShGeom G;
+    bool vec_ok;                                        // extents and strides allow 16-byte loads (the pointers decide the rest)
+    size_t xs_bytes, bad_bytes;
+};
+
+int sh_plan(const dlwpcs_sht_spectrum_desc *d, bool pair, ShPlan &P) {
+    if (!d) return fail(DLWPCS_E_INVALID, "sht_spectrum: null descriptor");
+    if (d->L < 2) return fail(DLWPCS_E_INVALID, "sht_spectrum: L = %d (at least 2 longitudes)", d->L);
+    if (d->L > SH_MAX_L) return fail(DLWPCS_E_UNSUPPORTED, "sht_spectrum: L = %d, this build serves 2 <= L <= %d", d->L, SH_MAX_L);
+    if (d->nlat < 2) return fail(DLWPCS_E_INVALID, "sht_spectrum: nlat = %d (at least 2 latitudes)", d->nlat);
+    if (d->nlat > DLWPCS_SHT_MAX_NLAT)
+        return fail(DLWPCS_E_UNSUPPORTED, "sht_spectrum: nlat = %d, this build serves 2 <= nlat <= %d", d->nlat, DLWPCS_SHT_MAX_NLAT);
+    if (d->T < 0 || 2 * (int64_t)d->T + 1 > d->L)
+        return fail(DLWPCS_E_INVALID, "sht_spectrum: truncation T = %d needs 0 <= T and L >= 2 T + 1 = %lld longitudes, L = %d", d->T,
+                    2 * (long long)d->T + 1, d->L);
+    if (d->n_dims < 0 || d->n_dims > DLWPCS_SCORE_MAX_DIMS) return fail(DLWPCS_E_INVALID, "sht_spectrum: n_dims %d out of range", d->n_dims);
+    ShGeom &G = P.G;
+    memset(&G, 0, sizeof(G));
+    G.nlat = d->nlat;
+    G.nlp = (d->nlat + 3) / 4 * 4;
+    G.L = d->L;
+    G.T = d->T;
+    G.n_dims = d->n_dims;
+    G.fields = 1;
+    bool vec = d->L % 4 == 0;
+    for (int op = 0; op < 2; ++op) {
+        G.lat_stride[op] = d->lat_stride[op];
+        if (op == 0 || pair) vec = vec && d->lat_stride[op] % 4 == 0;
+    }
+    for (int i = 0; i < d->n_dims; ++i) {
+        const int64_t e = d->ext[i];
+        if (e < 0 || e >= (1ll << 31)) return fail(DLWPCS_E_INVALID, "sht_spectrum: extent %lld of dim %d", (long long)e, i);
+        G.ext[i] = e;
+        for (int op = 0; op < 2; ++op) {
+            G.stride[op][i] = d->stride[op][i];
+            if (op == 0 || pair) vec = vec && d->stride[op][i] % 4 == 0;
+        }
+        G.fields *= e;
+        if (G.fields >= (1ll << 31)) return fail(DLWPCS_E_UNSUPPORTED, "sht_spectrum: too many fields");
+    }
+    P.vec_ok = vec;
+    G.rows = G.fields * G.nlat;
+    G.n_rt = (G.rows + SH_ROWS - 1) / SH_ROWS;
+    G.n_mt = (G.T + 1 + SH_MT - 1) / SH_MT;
+    G.n_ft = (G.fields + SH_TILE - 1) / SH_TILE;
+    G.n_nt = (G.T + 1 + SH_TILE - 1) / SH_TILE;
+    G.op_stride = G.fields * (G.T + 1) * 2 * G.nlp;
+    if (G.n_rt * G.n_mt > 65536ll * 65535ll) return fail(DLWPCS_E_UNSUPPORTED, "sht_spectrum: too many workgroups");
+    P.xs_bytes = (size_t)G.op_stride * sizeof(float) * (pair ? 2 : 1);
+    P.bad_bytes = (size_t)G.rows * sizeof(int32_t);
+    return DLWPCS_OK;
+}
+
+dim3 sh_grid(int64_t n) {
+    const int64_t gx = n < 65536 ? n : 65536;
+    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
+}
+
+}  // namespace
+
+}  // namespace dlwpcs
+
+using namespace dlwpcs;
+
+// the pair form needs the larger scratch; the single form of the same descriptor never needs more
+extern "C" size_t dlwpcs_sht_spectrum_scratch_bytes(const dlwpcs_sht_spectrum_desc *d) {
+    ShPlan P;
+    if (sh_plan(d, true, P) != DLWPCS_OK) return 0;
+    return P.xs_bytes + P.bad_bytes;
+}
+
+extern "C" int dlwpcs_sht_spectrum(const dlwpcs_sht_spectrum_desc *d, const float *a, const float *b, const float *twiddle,
+                                   const float *legendre, void *scratch, float *out, int32_t *skipped, dlwpcs_stream_t stream) {
+    const bool pair = b != nullptr;
+    ShPlan P;
+    const int rc = sh_plan(d, pair, P);
+    if (rc != DLWPCS_OK) return rc;
+    const ShGeom &G = P.G;
+    if (!twiddle || !legendre) return fail(DLWPCS_E_INVALID, "sht_spectrum: null twiddle or Legendre table");
+    if (((uintptr_t)twiddle) & 7) return fail(DLWPCS_E_INVALID, "sht_spectrum: the twiddle table is not aligned to 8 bytes");
+    if (((uintptr_t)legendre) & 15) return fail(DLWPCS_E_INVALID, "sht_spectrum: the Legendre table is not aligned to 16 bytes");
+    if (G.fields == 0) return DLWPCS_OK;
+    if (!out || !a) return fail(DLWPCS_E_INVALID, "sht_spectrum: null source or output");
+    if ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)out) | ((uintptr_t)skipped)) & 3)
+        return fail(DLWPCS_E_INVALID, "sht_spectrum: an operand is not aligned to its 4-byte elements");
+    if (!scratch || (((uintptr_t)scratch) & 15))
+        return fail(DLWPCS_E_INVALID, "sht_spectrum: this descriptor needs a 16-byte aligned scratch of %zu bytes", P.xs_bytes + P.bad_bytes);
+    float *xs = (float *)scratch;
+    int32_t *bad = (int32_t *)((char *)scratch + P.xs_bytes);
+    const bool vec = P.vec_ok && !((((uintptr_t)a) | ((uintptr_t)b)) & 15);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid_a = sh_grid(G.n_rt * G.n_mt), grid_b = sh_grid(G.n_ft * G.n_nt);
+    const float2 *tw = (const float2 *)twiddle;
+#define SH_LAUNCH_A(PAIR, VEC) \
+    hipLaunchKernelGGL((sht_fourier_kernel<PAIR, VEC>), grid_a, dim3(SH_THREADS), 0, s, G, a, b, tw, xs, bad)
+    if (pair) { if (vec) SH_LAUNCH_A(true, true); else SH_LAUNCH_A(true, false); }
+    else { if (vec) SH_LAUNCH_A(false, true); else SH_LAUNCH_A(false, false); }
+#undef SH_LAUNCH_A
+    if (pair) hipLaunchKernelGGL((sht_legendre_kernel<true>), grid_b, dim3(64), 0, s, G, xs, bad, legendre, out, skipped);
+    else hipLaunchKernelGGL((sht_legendre_kernel<false>), grid_b, dim3(64), 0, s, G, xs, bad, legendre, out, skipped);
+    return check_launch("sht_spectrum");
+}

@@ -745,6 +745,49 @@ int dlwpcs_zonal_spectrum(const dlwpcs_zonal_spectrum_desc *d, const float *a, c
                           int32_t *skipped /* may be NULL */, dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Spherical-harmonic power spectra (DLWP/verify.py spherical_spectrum, spherical_cross_spectrum, spherical_correlation): power
+ * per total wavenumber n.  A field is x[i, j] on nlat latitudes (mu_i = sin(lat_i), quadrature weights w_i >= 0, sum w_i = 2)
+ * and L equally spaced longitudes (unit stride).  With Pbar_n^m the associated Legendre functions normalised to
+ * (1/2) int Pbar_n^m Pbar_n'^m dmu = delta_nn' (no Condon-Shortley phase), for 0 <= m <= n <= T:
+ *   X_m(i) = sum_j x[i,j] exp(-2 pi i j m / L),   a_n^m = sum_i (w_i / 2) Pbar_n^m(mu_i) X_m(i) / L,
+ *   S_n = sum_{m=0..n} c_m |a_n^m|^2,  c_0 = 1, c_m = 2 otherwise:  sum_n S_n is the area-weighted mean square of a field
+ *   band-limited to T, S_0 the squared global mean.
+ * The leading axes arrive as n_dims merged dims with an extent and an element stride per operand (0: a, 1: b); they index the
+ * FIELDS, row-major in the order given.  Latitude i of a field lies lat_stride elements from latitude 0 (either operand its own).
+ *   b == NULL: out (fields, T + 1) fp32.   b != NULL, the pair form: out (3, fields, T + 1) = S_aa, S_bb and the co-spectrum
+ *   sum_m c_m Re(a_n^m conj b_n^m); out[0] has the bits of the single form on a.
+ * A field that holds a NaN or an infinity (pair form: in a or in b) gets NaN rows; skipped (may be NULL) receives 1 for such a
+ * field and 0 for every other, one int32 per field.  Means over fields are dlwpcs_group_mean's business.
+ * Two launches.  Stage A, Fourier: (fields x nlat rows x L) . (L x 2 (T + 1)) on v_mfma_f32_32x32x2_f32 with dlwpcs_zonal_spectrum's
+ * twiddle table and reduced-index lookup, written to scratch as [operand][field][m][re | im][nlat_pad] fp32, then one int32 per
+ * (field, latitude) that says whether the row held a non-finite value; nlat_pad = nlat rounded up to a multiple of 4.  Stage B,
+ * Legendre: per order m the product (degrees x nlat) . (nlat x fields) on the same instruction; a workgroup (one wave) owns 32
+ * degrees x 32 fields and walks m = 0 .. its last degree in order.  Per m the fp32 products Re^2 + Im^2 (pair: also the two
+ * others) are widened to fp64, multiplied by c_m / L^2 and added in order of m; the sum is rounded to fp32 once.  No atomics,
+ * bitwise repeatable, no host synchronisation, no allocation: scratch >= dlwpcs_sht_spectrum_scratch_bytes(d), 16-byte aligned.
+ * legendre: the caller's table (w_i / 2) Pbar_n^m(mu_i) in fp32, each entry evaluated in fp64 and rounded once, 16-byte
+ * aligned: (T + 1)(T + 2) / 2 rows of nlat_pad floats, row (m, n) = m (T + 1) - m (m - 1) / 2 + (n - m), entries i >= nlat zero.
+ * twiddle: as for dlwpcs_zonal_spectrum, for this L.
+ * Limits: 2 <= L <= 1728 (DLWPCS_E_UNSUPPORTED beyond), 2 <= nlat <= 8192, 0 <= T, 2 T + 1 <= L; 721 x 1440 at T = 360 is served
+ * (its table holds 190 MB).  Whether T suits the latitudes' quadrature is the caller's check: the descriptor does not carry it.
+ * The grid is (field tiles of 32) x (degree tiles of 32): a handful of fields leaves most of the device idle.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_SHT_MAX_NLAT 8192
+typedef struct dlwpcs_sht_spectrum_desc {
+    int32_t nlat;                /* latitudes */
+    int32_t L;                   /* longitudes per row */
+    int32_t T;                   /* truncation: degrees 0 .. T */
+    int32_t n_dims;              /* leading dims, at most DLWPCS_SCORE_MAX_DIMS */
+    int64_t lat_stride[2];       /* elements: a, b */
+    int64_t ext[DLWPCS_SCORE_MAX_DIMS];
+    int64_t stride[2][DLWPCS_SCORE_MAX_DIMS];     /* elements: a, b */
+} dlwpcs_sht_spectrum_desc;
+size_t dlwpcs_sht_spectrum_scratch_bytes(const dlwpcs_sht_spectrum_desc *d);
+int dlwpcs_sht_spectrum(const dlwpcs_sht_spectrum_desc *d, const float *a, const float *b /* NULL: single form */,
+                        const float *twiddle, const float *legendre, void *scratch, float *out,
+                        int32_t *skipped /* may be NULL */, dlwpcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Ensemble scores (DLWP/verify.py ensemble_mean, ensemble_spread, ensemble_crps, ensemble_error, rank_histogram): the member
  * axis of an fp32 ensemble collapsed element by element.  The element dims arrive as n_dims merged dims with an extent and an
  * element stride per operand (0: ens, 1: valid; 0 = broadcast), the members lie member_stride elements apart: a permuted view
