@@ -155,6 +155,12 @@ class ShtSpectrumDesc(ctypes.Structure):
                 ('stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 2)]
 
 
+class ShtSynthesisDesc(ctypes.Structure):
+    """struct dlwpcs_sht_synthesis_desc (include/dlwpcs.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ('nlat', 'L', 'T', 'n_dims')] + \
+               [('lat_stride', ctypes.c_int64), ('ext', ctypes.c_int64 * SCORE_MAX_DIMS), ('stride', ctypes.c_int64 * SCORE_MAX_DIMS)]
+
+
 SHT_MAX_NLAT = 8192
 ENSEMBLE_MAX_M = 128
 
@@ -267,6 +273,10 @@ PROTOTYPES = {
     'dlwpcs_zonal_spectrum': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sht_spectrum_scratch_bytes': (c_size_t, [c_void_p]),
     'dlwpcs_sht_spectrum': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_sht_analysis_scratch_bytes': (c_size_t, [c_void_p]),
+    'dlwpcs_sht_analysis': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_sht_synthesis_scratch_bytes': (c_size_t, [c_void_p]),
+    'dlwpcs_sht_synthesis': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_ensemble_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_ensemble_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_count': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

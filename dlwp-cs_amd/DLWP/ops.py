@@ -2186,6 +2186,157 @@ def spherical_spectrum(a, b=None, transform=None, lat_axis=-2, lon_axis=-1, redu
     return (out, cnt) if counts else out
 
 
+def _sht_grid_axes(a, transform, lat_axis, lon_axis, who):
+    """(lat, lon) as non-negative axes of the device tensor `a` after the checks spherical_spectrum makes"""
+    nd = a.dim()
+    if nd < 2:
+        raise ValueError('%s: the input needs a latitude and a longitude axis' % who)
+    lat, lon = int(lat_axis), int(lon_axis)
+    if not (-nd <= lat < nd and -nd <= lon < nd) or lat % nd == lon % nd:
+        raise ValueError('%s: lat_axis %d and lon_axis %d must be two axes of the %d' % (who, lat, lon, nd))
+    lat, lon = lat % nd, lon % nd
+    nlat, L = int(a.shape[lat]), int(a.shape[lon])
+    if (nlat, L) != (transform.nlat, transform.n_lon):
+        raise ValueError('%s: the grid axes hold %d x %d points, the transform is for %d x %d'
+                         % (who, nlat, L, transform.nlat, transform.n_lon))
+    if L > SPECTRUM_MAX_L:
+        raise NotImplementedError('%s: %d longitudes, the kernel serves 2 .. %d' % (who, L, SPECTRUM_MAX_L))
+    if nlat > nat.SHT_MAX_NLAT:
+        raise NotImplementedError('%s: %d latitudes, the kernel serves 2 .. %d' % (who, nlat, nat.SHT_MAX_NLAT))
+    return lat, lon
+
+
+def sht_analysis_launch(d, a, twiddle, table, coef, skipped=None):
+    """dlwpcs_sht_analysis on the current stream: the device tensor a addressed by the descriptor (operand 0), into the float32
+    tensor `coef` (fields, rows, 2) and the int32 tensor `skipped` (fields; None: not wanted)"""
+    dev = a.device
+    nbytes = int(lib().dlwpcs_sht_analysis_scratch_bytes(ctypes.byref(d)))
+    scratch = _workspace(nbytes, dev, 'sht') if nbytes else None
+    with torch.cuda.device(dev):
+        check(lib().dlwpcs_sht_analysis(ctypes.byref(d), ptr(a), ptr(twiddle), ptr(table), ptr(scratch) or None, ptr(coef),
+                                        ptr(skipped) or None, stream_ptr()), 'dlwpcs_sht_analysis')
+    return coef
+
+
+def sht_synthesis_desc(nlat, L, T, dims, lat_stride):
+    """nat.ShtSynthesisDesc of output fields of nlat x L points: `dims` the leading dims of spectrum_dims over the output's
+    strides, lat_stride the element stride of its latitude axis"""
+    if len(dims) > nat.SCORE_MAX_DIMS:
+        raise NotImplementedError('spherical_synthesis: more than %d leading dims after merging' % nat.SCORE_MAX_DIMS)
+    d = nat.ShtSynthesisDesc()
+    d.nlat, d.L, d.T, d.n_dims, d.lat_stride = int(nlat), int(L), int(T), len(dims), int(lat_stride)
+    for i, (e, st, _) in enumerate(dims):
+        d.ext[i], d.stride[i] = e, st[0]
+    return d
+
+
+def sht_synthesis_launch(d, coef, response, twiddle, table, out):
+    """dlwpcs_sht_synthesis on the current stream: the float32 tensor `coef` (fields, rows, 2), `response` (T + 1 floats or None)
+    and the unweighted table, into the device tensor `out` addressed by the descriptor"""
+    dev = out.device
+    nbytes = int(lib().dlwpcs_sht_synthesis_scratch_bytes(ctypes.byref(d)))
+    scratch = _workspace(nbytes, dev, 'sht_synth') if nbytes else None
+    with torch.cuda.device(dev):
+        check(lib().dlwpcs_sht_synthesis(ctypes.byref(d), ptr(coef), ptr(response) or None, ptr(twiddle), ptr(table),
+                                         ptr(scratch) or None, ptr(out), stream_ptr()), 'dlwpcs_sht_synthesis')
+    return out
+
+
+def spherical_analysis(a, transform, lat_axis=-2, lon_axis=-1, counts=False):
+    """
+    The spherical-harmonic coefficients a_n^m (0 <= m <= n <= T) of the float32 device tensor `a`, whose `lat_axis` and `lon_axis`
+    hold the grid of `transform` (a DLWP.remap.spharm.SphericalTransform: it states the definitions and the packing): a complex64
+    device tensor (leading axes..., (T + 1)(T + 2) / 2), row spharm.packed_row(m, n, T).  The grid axes may sit anywhere; no copy
+    is made while longitude is unit-stride.  A field that holds a NaN or an infinity gets NaN coefficients; counts=True: also the
+    int32 tensor (leading axes...) that holds 1 for such a field.  Two launches of dlwpcs_sht_analysis on the current stream.
+    """
+    if transform is None:
+        raise TypeError('spherical_analysis: a SphericalTransform is required')
+    require_device(a, 'spherical_analysis')
+    if a.dtype != torch.float32:
+        raise TypeError('spherical_analysis: the operand must be float32, got %s' % a.dtype)
+    lat, lon = _sht_grid_axes(a, transform, lat_axis, lon_axis, 'spherical_analysis')
+    nlat, L, T = transform.nlat, transform.n_lon, int(transform.truncation)
+    lead_axes = [i for i in range(a.dim()) if i not in (lat, lon)]
+    t = a.permute(lead_axes + [lat, lon])
+    if t.stride(-1) != 1:
+        t = t.contiguous()
+    lead = tuple(int(e) for e in t.shape[:-2])
+    fields = int(np.prod(lead, dtype=np.int64))
+    rows = (T + 1) * (T + 2) // 2
+    dev = a.device
+    coef = torch.empty(lead + (rows, 2), dtype=torch.float32, device=dev)
+    flags = torch.empty(lead, dtype=torch.int32, device=dev) if counts else None
+    if fields:
+        twiddle, table = transform.device_tables(dev)
+        strides = [tuple(int(s) for s in t.stride()[:-2]), (0,) * len(lead)]
+        d = sht_desc(nlat, L, T, spectrum_dims(lead, strides, ()), (int(t.stride(-2)), 0))
+        sht_analysis_launch(d, t, twiddle, table, coef, flags)
+    out = torch.view_as_complex(coef)
+    return (out, flags) if counts else out
+
+
+def _sht_response(response, T, dev, who):
+    """the response as a float32 device tensor of T + 1 factors (None stays None); a host array is uploaded, so pass a device
+    tensor where the call must be captured"""
+    if response is None:
+        return None
+    if not torch.is_tensor(response):
+        if torch.cuda.is_current_stream_capturing():
+            raise nat.NativeError('%s: a host response inside a graph capture (pass a device tensor)' % who)
+        response = torch.from_numpy(np.ascontiguousarray(np.asarray(response, dtype=np.float64).reshape(-1).astype(np.float32))).to(dev)
+    require_device(response, who)
+    if response.dtype != torch.float32 or response.device != dev or response.dim() != 1 or not response.is_contiguous():
+        raise TypeError('%s: the response must be a contiguous float32 vector on the device of the coefficients' % who)
+    if int(response.numel()) != T + 1:
+        raise ValueError('%s: a response of %d factors, truncation %d needs %d' % (who, int(response.numel()), T, T + 1))
+    return response
+
+
+def spherical_synthesis(coef, transform, response=None, out=None):
+    """
+    The fields x[i, j] = sum_m c_m Re(e^{2 pi i j m / L} sum_n r_n a_n^m Pbar_n^m(mu_i)) of the complex64 device tensor `coef`
+    (leading axes..., (T + 1)(T + 2) / 2) on the grid of `transform`: a float32 device tensor (leading axes..., nlat, L).
+    response: T + 1 real factors r_n per degree (float32 device vector or host array; None: ones, with the same bits).
+    out: a float32 device tensor of that shape to write into; any strides with longitude at unit stride.
+    Two launches of dlwpcs_sht_synthesis on the current stream, no host synchronisation (the unweighted table of a transform is
+    uploaded at its first use).
+    """
+    if transform is None:
+        raise TypeError('spherical_synthesis: a SphericalTransform is required')
+    if not isinstance(coef, torch.Tensor) or coef.dtype != torch.complex64:
+        raise TypeError('spherical_synthesis: the coefficients must be a complex64 tensor, got %s'
+                        % (coef.dtype if isinstance(coef, torch.Tensor) else type(coef)))
+    require_device(torch.view_as_real(coef), 'spherical_synthesis')
+    nlat, L, T = transform.nlat, transform.n_lon, int(transform.truncation)
+    rows = (T + 1) * (T + 2) // 2
+    if coef.dim() < 1 or int(coef.shape[-1]) != rows:
+        raise ValueError('spherical_synthesis: %s coefficients, truncation %d has %d per field' % (tuple(coef.shape), T, rows))
+    if L > SPECTRUM_MAX_L:
+        raise NotImplementedError('spherical_synthesis: %d longitudes, the kernel serves 2 .. %d' % (L, SPECTRUM_MAX_L))
+    if nlat > nat.SHT_MAX_NLAT:
+        raise NotImplementedError('spherical_synthesis: %d latitudes, the kernel serves 2 .. %d' % (nlat, nat.SHT_MAX_NLAT))
+    dev = coef.device
+    lead = tuple(int(e) for e in coef.shape[:-1])
+    if out is None:
+        out = torch.empty(lead + (nlat, L), dtype=torch.float32, device=dev)
+    else:
+        require_device(out, 'spherical_synthesis')
+        if out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != lead + (nlat, L):
+            raise ValueError('spherical_synthesis: out must be a float32 tensor of shape %s on the device of the coefficients'
+                             % (lead + (nlat, L),))
+        if out.stride(-1) != 1:
+            raise ValueError('spherical_synthesis: out needs unit stride along longitude')
+    resp = _sht_response(response, T, dev, 'spherical_synthesis')
+    if int(np.prod(lead, dtype=np.int64)):
+        flat = torch.view_as_real(coef.contiguous())
+        twiddle, table = transform.device_synthesis_tables(dev)
+        strides = [tuple(int(s) for s in out.stride()[:-2])]
+        d = sht_synthesis_desc(nlat, L, T, spectrum_dims(lead, strides, ()), int(out.stride(-2)))
+        sht_synthesis_launch(d, flat, resp, twiddle, table, out)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------ #
 # Ensemble scores (DLWP/verify.py ensemble_* / rank_histogram), include/dlwpcs.h dlwpcs_ensemble_stats
 # ------------------------------------------------------------------------------------------------------------------ #

@@ -8,6 +8,9 @@ Pbar_n^m are the associated Legendre functions with (1/2) int Pbar_n^m Pbar_n'^m
     X_m(i) = sum_j x[i,j] exp(-2 pi i j m / L),   a_n^m = sum_i (w_i / 2) Pbar_n^m(mu_i) X_m(i) / L      (0 <= m <= n <= T)
     S_n    = sum_{m=0..n} c_m |a_n^m|^2,   c_0 = 1, c_m = 2 otherwise.
 For a field band-limited to T, sum_n S_n is its area-weighted mean square; S_0 is the squared global mean.
+Synthesis with a real response r_n (device: ops.spherical_synthesis / dlwpcs_sht_synthesis):
+    x[i, j] = sum_{m=0..T} c_m Re( exp(+2 pi i j m / L) sum_{n=m..T} r_n a_n^m Pbar_n^m(mu_i) );   Im a_n^0 is ignored,
+and synthesis(analysis(x)) = x for a field band-limited to T.  Coefficients are packed in the order of packed_row(m, n, T).
 
 Three latitude layouts are recognised (either direction):
     'gauss'            the nodes of numpy.polynomial.legendre.leggauss(nlat); exact for T <= nlat - 1
@@ -135,6 +138,38 @@ def legendre_table(lat, truncation):
     return t32, t64
 
 
+def unweighted_table(lat, truncation):
+    """(float32 packed table (rows, nlat padded with zeros to a multiple of 4), its float64 parent (rows, nlat)): Pbar_n^m(mu_i)
+    in the order of `lat`, the packing of legendre_table; every entry evaluated in float64 and rounded once (it is not the
+    weighted table divided by the weights: that would round twice)"""
+    kind, flipped = _classify(lat)
+    nlat = np.asarray(getattr(lat, 'values', lat)).size
+    p64 = legendre_functions(_nodes(kind, nlat)[1], int(truncation))
+    if flipped:
+        p64 = np.ascontiguousarray(p64[:, ::-1])
+    p32 = np.zeros((p64.shape[0], (nlat + 3) // 4 * 4), dtype=np.float32)
+    p32[:, :nlat] = p64
+    return p32, p64
+
+
+def truncation_response(T, cutoff):
+    """(T + 1,) float64: 1 for the degrees n <= cutoff, 0 above"""
+    T, cutoff = int(T), int(cutoff)
+    if T < 0 or cutoff < 0:
+        raise ValueError('truncation_response: T = %d, cutoff = %d (both at least 0)' % (T, cutoff))
+    return (np.arange(T + 1) <= cutoff).astype(np.float64)
+
+
+def laplacian_response(T, radius=6371200., inverse=False):
+    """(T + 1,) float64: -n (n + 1) / radius^2, the Laplacian on a sphere of `radius` metres in spectral space; inverse: its
+    reciprocal, with 0 at n = 0 (the mean is lost)"""
+    n = np.arange(int(T) + 1, dtype=np.float64)
+    r = -n * (n + 1.0) / float(radius) ** 2
+    if inverse:
+        r[1:] = 1.0 / r[1:]
+    return r
+
+
 class SphericalTransform(object):
     """The analysis of fields on `lat` (degrees) x n_lon longitudes up to `truncation` (None: the largest the grid allows):
     kind, weights, truncation, the packed tables, and one device copy of the float32 table and the twiddles per device."""
@@ -160,6 +195,7 @@ class SphericalTransform(object):
         self.truncation = T
         self.table32, self.table64 = legendre_table(self.lat, T)
         self._device = {}
+        self._unweighted, self._device_unweighted = None, {}
 
     def device_tables(self, device):
         """(twiddle table, Legendre table) on `device`, uploaded at the first use there (not inside a graph capture)"""
@@ -174,6 +210,48 @@ class SphericalTransform(object):
             hit = (ops.spectrum_twiddle(self.n_lon, device), torch.from_numpy(self.table32).to(device))
             self._device[key] = hit
         return hit
+
+    def synthesis_tables(self):
+        """(float32, float64) unweighted tables Pbar_n^m(mu_i) of the synthesis, made at the first use"""
+        if self._unweighted is None:
+            self._unweighted = unweighted_table(self.lat, self.truncation)
+        return self._unweighted
+
+    def device_synthesis_tables(self, device):
+        """(twiddle table, unweighted Legendre table) on `device`, uploaded at the first use there (not inside a graph capture)"""
+        import torch
+        from .. import ops
+        key = str(torch.device(device))
+        hit = self._device_unweighted.get(key)
+        if hit is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise ops.nat.NativeError('spherical_synthesis: first use of this transform inside a graph capture (run it once '
+                                          'eagerly first)')
+            hit = (ops.spectrum_twiddle(self.n_lon, device), torch.from_numpy(self.synthesis_tables()[0]).to(device))
+            self._device_unweighted[key] = hit
+        return hit
+
+    def synthesis(self, coef, response=None):
+        """x[i, j] = sum_m c_m Re(e^{2 pi i j m / L} sum_n r_n a_n^m Pbar_n^m(mu_i)) of complex coefficients (..., packed rows):
+        float64 (..., nlat, n_lon).  response: T + 1 real factors per degree (None: ones).  Im a_n^0 is ignored."""
+        coef = np.asarray(coef, dtype=np.complex128)
+        T, L = self.truncation, self.n_lon
+        if coef.shape[-1:] != (packed_rows(T),):
+            raise ValueError('SphericalTransform: %s coefficients per field, truncation %d has %d'
+                             % (coef.shape[-1:], T, packed_rows(T)))
+        r = np.ones(T + 1) if response is None else np.asarray(response, dtype=np.float64).reshape(-1)
+        if r.shape != (T + 1,):
+            raise ValueError('SphericalTransform: a response of %d factors, truncation %d needs %d' % (r.size, T, T + 1))
+        p64 = self.synthesis_tables()[1]
+        G = np.zeros(coef.shape[:-1] + (self.nlat, L // 2 + 1), dtype=np.complex128)
+        for m in range(T + 1):
+            s = packed_row(m, m, T)
+            a = coef[..., s:s + T + 1 - m] * r[m:]
+            if m == 0:
+                a = a.real
+            G[..., m] = np.einsum('ni,...n->...i', p64[s:s + T + 1 - m], a)
+        # irfft sums c_m Re(G_m e^{i m lon}) / L for 0 < m < L / 2 (T < L / 2 always: L >= 2 T + 1)
+        return np.fft.irfft(G * L, n=L, axis=-1)
 
     def coefficients(self, x):
         """a_n^m of float64 fields x (..., nlat, n_lon): complex (..., packed rows)"""

@@ -1024,15 +1024,8 @@ def _sht_host(f, v, la, lo, ax, tr):
     return out, np.asarray(skipped, dtype=np.int32)
 
 
-def _sht(f, v, lat, lat_axis, lon_axis, axis, truncation):
-    """(quantities (nq, kept..., T + 1) float64, skipped, kept dim names or None)"""
-    if v is not None:
-        if len(v.shape) == len(f.shape) - 1:
-            raise NotImplementedError('the lagged form against a continuous verification series (valid[f + t]) is not served: '
-                                      'aligned arrays of one shape are')
-        _check_labels(f, v)
-        if tuple(f.shape) != tuple(v.shape):
-            raise ValueError('forecast %s and verification %s must have one shape' % (tuple(f.shape), tuple(v.shape)))
+def _sht_grid(f, lat, lat_axis, lon_axis, truncation):
+    """(latitude axis, longitude axis, SphericalTransform) of the input f"""
     if len(f.shape) < 2:
         raise ValueError('the input needs a latitude and a longitude axis')
     la, lo = _grid_axis(f, 'lat', lat_axis), _grid_axis(f, 'lon', lon_axis)
@@ -1046,7 +1039,19 @@ def _sht(f, v, lat, lat_axis, lon_axis, axis, truncation):
     lat = np.asarray(_host(lat), dtype=np.float64).reshape(-1)
     if lat.size != int(f.shape[la]):
         raise ValueError('%d latitudes for a latitude axis of %d' % (lat.size, int(f.shape[la])))
-    tr = _spherical_transform(lat, int(f.shape[lo]), truncation)
+    return la, lo, _spherical_transform(lat, int(f.shape[lo]), truncation)
+
+
+def _sht(f, v, lat, lat_axis, lon_axis, axis, truncation):
+    """(quantities (nq, kept..., T + 1) float64, skipped, kept dim names or None)"""
+    if v is not None:
+        if len(v.shape) == len(f.shape) - 1:
+            raise NotImplementedError('the lagged form against a continuous verification series (valid[f + t]) is not served: '
+                                      'aligned arrays of one shape are')
+        _check_labels(f, v)
+        if tuple(f.shape) != tuple(v.shape):
+            raise ValueError('forecast %s and verification %s must have one shape' % (tuple(f.shape), tuple(v.shape)))
+    la, lo, tr = _sht_grid(f, lat, lat_axis, lon_axis, truncation)
     nd = len(f.shape)
     if axis is None:
         ax = tuple(i for i in range(nd) if i not in (la, lo))
@@ -1126,6 +1131,185 @@ def spherical_correlation(forecast, valid, lat=None, lat_axis=-2, lon_axis=-1, a
         cor = out[2] / np.sqrt(out[0] * out[1])
     res = _label_degree(cor, dims, forecast, 'spherical_correlation')
     return (res, skipped) if return_count else res
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# Spherical-harmonic analysis, synthesis and filtering
+# --------------------------------------------------------------------------------------------------------------------- #
+#
+# The coefficients themselves, the inverse transform, and the chain analysis -> factor per degree -> synthesis: truncation to a
+# coarser resolution (scale-separated verification: forecast_error(spherical_filter(f, cutoff=21), spherical_filter(v, cutoff=21))),
+# the Laplacian and its inverse (height <-> vorticity), smoothing before a remap.  numpy inputs run on the host in float64 and
+# return numpy; device tensors run through dlwpcs_sht_analysis / dlwpcs_sht_synthesis and return device tensors (float32 /
+# complex64); neither path falls back to the other.  A field that holds a NaN or an infinity has NaN coefficients and comes back
+# as a field of NaN.
+
+_responses = {}             # (response bytes, device) -> float32 device vector
+
+
+def _device_of(x):
+    return _raw(x).device
+
+
+def _response_on(response, dev):
+    """the float32 device copy of a host response, uploaded once per device (so that a later call can be captured)"""
+    import torch
+    if response is None or _is_tensor(response):
+        return response
+    r32 = np.ascontiguousarray(np.asarray(response, dtype=np.float64).reshape(-1).astype(np.float32))
+    key = (r32.tobytes(), str(dev))
+    hit = _responses.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():
+            from . import _native as nat
+            raise nat.NativeError('spherical_filter: first use of this response inside a graph capture (run it once eagerly first)')
+        hit = _responses[key] = torch.from_numpy(r32).to(dev)
+    return hit
+
+
+def _coef_dims(x, la, lo):
+    return tuple(d for i, d in enumerate(x.dims) if i not in (la, lo)) if hasattr(x, 'dims') else None
+
+
+def _sht_label(values, dims, src, name):
+    """a Forecast over `dims` with the coordinates `src` has for them when the input was labelled, else the array"""
+    if dims is None:
+        return values
+    coords = {d: np.asarray(getattr(src.coords[d], 'values', src.coords[d])) for d in dims if d in getattr(src, 'coords', {})}
+    return Forecast(values, dims, coords, name=name)
+
+
+def _analysis_host(x, la, lo, tr):
+    """(complex128 coefficients (lead..., rows), int32 flags (lead...)) of the host array x"""
+    arr = np.moveaxis(np.asarray(x, dtype=np.float64), (la, lo), (-2, -1))
+    counted = np.isfinite(arr).all(axis=(-2, -1))
+    coef = tr.coefficients(np.where(counted[..., None, None], arr, 0.0))
+    coef[~counted] = complex(np.nan, np.nan)
+    return coef, (~counted).astype(np.int32)
+
+
+def spherical_analysis(x, lat=None, lat_axis=-2, lon_axis=-1, truncation=None, return_count=False):
+    """
+    The spherical-harmonic coefficients a_n^m of `x`, 0 <= m <= n <= truncation (DLWP/remap/spharm.py states the definitions).
+
+    :param x: ndarray, device tensor or labelled array; grid axes, `lat` and `truncation` as for `spherical_spectrum`
+    :param return_count: also return an int32 array (leading axes...) that holds 1 for a field with a NaN or an infinity
+    :return: complex array (leading axes..., (T + 1)(T + 2) / 2) in the order of spharm.packed_row(m, n, T): complex128 numpy for
+        host inputs, a complex64 device tensor for device inputs; a labelled input gives a Forecast whose last dim is
+        'coefficient'.  A field that holds a NaN or an infinity has NaN coefficients.
+    """
+    la, lo, tr = _sht_grid(x, lat, lat_axis, lon_axis, truncation)
+    if _on_device(x):
+        import torch
+        from . import ops as dops
+        dev = _device_of(x)
+        with torch.cuda.device(dev):
+            coef, flags = dops.spherical_analysis(_dev_operand(x, dev), tr, lat_axis=la, lon_axis=lo, counts=True)
+    else:
+        coef, flags = _analysis_host(_host(x), la, lo, tr)
+    dims = _coef_dims(x, la, lo)
+    res = _sht_label(coef, None if dims is None else dims + ('coefficient',), x, 'spherical_analysis')
+    return (res, flags) if return_count else res
+
+
+def _truncation_of_rows(rows):
+    T = int(round((np.sqrt(8.0 * rows + 1.0) - 3.0) / 2.0))
+    if T < 0 or (T + 1) * (T + 2) // 2 != rows:
+        raise ValueError('%d coefficients per field are not (T + 1)(T + 2) / 2 for any truncation T' % rows)
+    return T
+
+
+def spherical_synthesis(coef, lat, n_lon, response=None):
+    """
+    The fields x[i, j] = sum_m c_m Re(e^{i m lon_j} sum_n r_n a_n^m Pbar_n^m(mu_i)) of the coefficients `coef`
+    (leading axes..., (T + 1)(T + 2) / 2), as `spherical_analysis` returns them, on the latitudes `lat` (degrees) and n_lon longitudes.
+
+    :param coef: complex ndarray, complex64 device tensor or labelled array (its last dim holds the coefficients)
+    :param response: T + 1 real factors per degree (None: ones); see spharm.truncation_response, spharm.laplacian_response
+    :return: (leading axes..., nlat, n_lon): float64 numpy for host inputs, a float32 device tensor for device inputs; a labelled
+        input gives a Forecast with the dims 'lat' and 'lon' in place of the coefficient dim
+    """
+    if len(coef.shape) < 1:
+        raise ValueError('the coefficients need an axis')
+    T = _truncation_of_rows(int(coef.shape[-1]))
+    tr = _spherical_transform(lat, n_lon, T)
+    if response is not None and not _is_tensor(response) and np.asarray(response).size != T + 1:
+        raise ValueError('a response of %d factors, truncation %d needs %d' % (np.asarray(response).size, T, T + 1))
+    if _on_device(coef):
+        import torch
+        from . import ops as dops
+        dev = _device_of(coef)
+        with torch.cuda.device(dev):
+            c = _raw(coef)
+            out = dops.spherical_synthesis(c if c.dtype == torch.complex64 else c.to(torch.complex64), tr, _response_on(response, dev))
+    else:
+        out = tr.synthesis(_host(coef), None if response is None else _host(response))
+    if not hasattr(coef, 'dims'):
+        return out
+    dims = tuple(coef.dims)[:-1] + ('lat', 'lon')
+    coords = {d: np.asarray(getattr(coef.coords[d], 'values', coef.coords[d])) for d in dims if d in getattr(coef, 'coords', {})}
+    coords['lat'] = tr.lat.copy()
+    coords['lon'] = np.arange(tr.n_lon) * 360.0 / tr.n_lon
+    return Forecast(out, dims, coords, name='spherical_synthesis')
+
+
+def _filter(x, lat, lat_axis, lon_axis, truncation, response, name):
+    """analysis, `response` (a function of the transform's truncation, or None) and synthesis back into x's shape and axis order"""
+    la, lo, tr = _sht_grid(x, lat, lat_axis, lon_axis, truncation)
+    T = tr.truncation
+    r = response(T) if callable(response) else response
+    if r is not None and not _is_tensor(r) and np.asarray(r).size != T + 1:
+        raise ValueError('a response of %d factors, truncation %d needs %d' % (np.asarray(r).size, T, T + 1))
+    nd = len(x.shape)
+    lead_axes = [i for i in range(nd) if i not in (la, lo)]
+    if _on_device(x):
+        import torch
+        from . import ops as dops
+        dev = _device_of(x)
+        with torch.cuda.device(dev):
+            xt = _dev_operand(x, dev)
+            coef = dops.spherical_analysis(xt, tr, lat_axis=la, lon_axis=lo)
+            # the result has x's shape and axis order, and longitude at unit stride whatever x's own layout
+            order = [i for i in range(nd) if i != lo] + [lo]
+            buf = torch.empty([int(xt.shape[i]) for i in order], dtype=torch.float32, device=dev)
+            out = buf.permute([order.index(i) for i in range(nd)])
+            dops.spherical_synthesis(coef, tr, _response_on(r, dev), out=out.permute(lead_axes + [la, lo]))
+    else:
+        coef, _ = _analysis_host(_host(x), la, lo, tr)
+        out = np.moveaxis(tr.synthesis(coef, None if r is None else _host(r)), (-2, -1), (la, lo))
+    return _sht_label(out, tuple(x.dims) if hasattr(x, 'dims') else None, x, name)
+
+
+def spherical_filter(x, lat=None, lat_axis=-2, lon_axis=-1, truncation=None, cutoff=None, response=None):
+    """
+    `x` with every spherical-harmonic degree n multiplied by a real factor: analysis up to `truncation`, the factor, synthesis.
+
+    :param x: ndarray, device tensor or labelled array; grid axes, `lat` and `truncation` as for `spherical_spectrum`
+    :param cutoff: keep the degrees n <= cutoff and drop the others (the field truncated to T`cutoff`)
+    :param response: truncation + 1 real factors per degree (host array, or a float32 device vector for device inputs);
+        `cutoff` and `response` are mutually exclusive, neither: the field band-limited to `truncation`
+    :return: the filtered field with the shape, axis order and labels of `x`: float64 numpy for host inputs, a float32 device tensor
+        for device inputs (four launches; after one eager call the call can be captured in a graph)
+    """
+    if cutoff is not None and response is not None:
+        raise ValueError('cutoff and response are mutually exclusive')
+    if cutoff is not None:
+        from .remap.spharm import truncation_response
+        cut = int(cutoff)
+        if cut < 0:
+            raise ValueError('cutoff %d is negative' % cut)
+        response = lambda T: truncation_response(T, cut)        # noqa: E731
+    return _filter(x, lat, lat_axis, lon_axis, truncation, response, 'spherical_filter')
+
+
+def spherical_laplacian(x, lat=None, lat_axis=-2, lon_axis=-1, truncation=None, radius=6371200., inverse=False):
+    """
+    The Laplacian of `x` on a sphere of `radius` metres, degree n multiplied by -n (n + 1) / radius^2 (height -> vorticity up to
+    g / f); inverse=True: the inverse Laplacian, degree n >= 1 divided by that factor and the mean set to 0.  Arguments and
+    result as for `spherical_filter`.
+    """
+    from .remap.spharm import laplacian_response
+    return _filter(x, lat, lat_axis, lon_axis, truncation, lambda T: laplacian_response(T, radius, inverse), 'spherical_laplacian')
 
 
 # --------------------------------------------------------------------------------------------------------------------- #

@@ -23,6 +23,10 @@
 //
 // The grid of stage B is (field tiles) x (degree tiles): a call with a handful of fields leaves most of the device idle, and the
 // degree tiles cost unequally (the top tile walks every m).  No m-split is built.
+//
+// Analysis and synthesis (dlwpcs_sht_analysis, dlwpcs_sht_synthesis) share this geometry: the coefficient kernel is stage B's
+// product with the coefficients as its output, the inverse pair (sht_ilegendre_kernel, sht_ifourier_kernel) is described where it
+// stands below.
 #include "mfma_common.h"
 
 namespace dlwpcs {
@@ -36,9 +40,14 @@ constexpr int SH_MT = 4 * SH_MW;            // orders per workgroup
 constexpr int SH_MAX_L = 1728;              // the twiddle table of 2 L floats lives in static LDS
 constexpr int SH_TILE = 32;                 // stage B: degrees and fields of a workgroup
 constexpr int SH_KV = 4;                    // stage B: 16-byte loads of a lane per step and line (a step covers 2 * 4 * SH_KV latitudes)
+constexpr int SH_MC = 8;                    // coefficient kernel: orders per workgroup
+constexpr int SH_JT = 4 * SH_TILE;          // inverse Fourier: longitudes per workgroup (32 per wave)
+constexpr int SH_KU = 4;                    // inverse stages: MFMAs per accumulator whose operands are loaded together
+constexpr int64_t SH_MAX_GRID = 65536ll * 65535ll;
 
 struct ShGeom {
     int32_t nlat, nlp, L, T, n_dims, n_mt, n_nt;
+    int32_t n_mc, n_lt, n_jt;                // order chunks of the coefficient kernel; latitude tiles, longitude tiles of the synthesis
     int64_t fields, rows, n_rt, n_ft;
     int64_t op_stride;                       // floats between the operands' halves of xs
     int64_t lat_stride[2];
@@ -235,6 +244,63 @@ __global__ void __launch_bounds__(SH_THREADS) sht_fourier_kernel(ShGeom G, const
     if (mt == 0 && tid < SH_ROWS && s_valid[tid]) bad[s_flag[tid]] = s_bad[tid];
 }
 
+// One order m of stage B: acc[op][re | im] = (32 degrees x nlat) . (nlat x 32 fields), the table tile rows (m, nA) as the A operand,
+// the lines of xs as the B operand.  Shared by the power kernel and the coefficient kernel: same tiles, operand mapping and masks.
+template <int NOP>
+__device__ __forceinline__ void sh_legendre_order(const ShGeom &G, const float *__restrict__ xs, const float *__restrict__ table,
+                                                  int m, int nA, int64_t fB, bool f_ok, int h, f32x16 (&acc)[NOP][2]) {
+    const int T = G.T, K = T + 1, nlat = G.nlat, nlp = G.nlp;
+    const int n_steps = (nlp + 2 * SH_KV * 4 - 1) / (2 * SH_KV * 4);
+#pragma unroll
+    for (int op = 0; op < NOP; ++op)
+#pragma unroll
+        for (int cs = 0; cs < 2; ++cs)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[op][cs][i] = 0.f;
+    const bool a_on = nA >= m && nA <= T;
+    const int64_t row = (int64_t)m * K - (int64_t)m * (m - 1) / 2 + (nA - m);
+    const float *pa = table + (a_on ? row : 0) * nlp;
+    const float *pb = xs + (((f_ok ? fB : 0) * K + m) * 2) * nlp;
+    for (int t = 0; t < n_steps; ++t) {
+        // all loads of the step are issued before its first MFMA: one wait per 32 latitudes
+        const int i0 = 2 * SH_KV * 4 * t + SH_KV * 4 * h;
+        float4 av[SH_KV], xv[NOP][2][SH_KV];
+#pragma unroll
+        for (int u = 0; u < SH_KV; ++u) {
+            const int iu = i0 + 4 * u;
+            const bool in = iu < nlp;                // (nlp is a multiple of 4: the 16 bytes lie inside the line or outside)
+            av[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (a_on && in) av[u] = *reinterpret_cast<const float4 *>(pa + iu);
+#pragma unroll
+            for (int op = 0; op < NOP; ++op)
+#pragma unroll
+                for (int cs = 0; cs < 2; ++cs) {
+                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (f_ok && in) v = *reinterpret_cast<const float4 *>(pb + op * G.op_stride + (int64_t)cs * nlp + iu);
+                    v.x = iu < nlat ? v.x : 0.f;    // the padding of xs is never written
+                    v.y = iu + 1 < nlat ? v.y : 0.f;
+                    v.z = iu + 2 < nlat ? v.z : 0.f;
+                    v.w = iu + 3 < nlat ? v.w : 0.f;
+                    xv[op][cs][u] = v;
+                }
+        }
+#pragma unroll
+        for (int u = 0; u < SH_KV; ++u) {
+            if (2 * SH_KV * 4 * t + 4 * u >= nlp) break;        // (wave-uniform: both halves of these MFMAs lie beyond the lines)
+#pragma unroll
+            for (int op = 0; op < NOP; ++op)
+#pragma unroll
+                for (int cs = 0; cs < 2; ++cs) {
+                    const float4 x = xv[op][cs][u];
+                    acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].x, x.x, acc[op][cs], 0, 0, 0);
+                    acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].y, x.y, acc[op][cs], 0, 0, 0);
+                    acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].z, x.z, acc[op][cs], 0, 0, 0);
+                    acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].w, x.w, acc[op][cs], 0, 0, 0);
+                }
+        }
+    }
+}
+
 template <bool PAIR>
 __global__ void __launch_bounds__(64) sht_legendre_kernel(ShGeom G, const float *__restrict__ xs, const int32_t *__restrict__ bad,
                                                           const float *__restrict__ table, float *__restrict__ out,
@@ -246,7 +312,7 @@ __global__ void __launch_bounds__(64) sht_legendre_kernel(ShGeom G, const float 
     const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
     const int nt = (int)(bid % G.n_nt);
     const int64_t ft = bid / G.n_nt;
-    const int T = G.T, K = T + 1, nlat = G.nlat, nlp = G.nlp;
+    const int T = G.T, K = T + 1, nlat = G.nlat;
     const int n0 = nt * SH_TILE;
     const int nA = n0 + r32;                             // this lane's degree as the row of the A operand
     const int64_t fB = ft * SH_TILE + r32;               // this lane's field as the column of the B operand
@@ -264,58 +330,10 @@ __global__ void __launch_bounds__(64) sht_legendre_kernel(ShGeom G, const float 
         for (int i = 0; i < 16; ++i) sum[q][i] = 0.0;
 
     const int m_last = n0 + SH_TILE - 1 < T ? n0 + SH_TILE - 1 : T;
-    const int n_steps = (nlp + 2 * SH_KV * 4 - 1) / (2 * SH_KV * 4);
     const double inv_l2 = 1.0 / ((double)G.L * (double)G.L);
     for (int m = 0; m <= m_last; ++m) {
         f32x16 acc[NOP][2];
-#pragma unroll
-        for (int op = 0; op < NOP; ++op)
-#pragma unroll
-            for (int cs = 0; cs < 2; ++cs)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[op][cs][i] = 0.f;
-        const bool a_on = nA >= m && nA <= T;
-        const int64_t row = (int64_t)m * K - (int64_t)m * (m - 1) / 2 + (nA - m);
-        const float *pa = table + (a_on ? row : 0) * nlp;
-        const float *pb = xs + (((f_ok ? fB : 0) * K + m) * 2) * nlp;
-        for (int t = 0; t < n_steps; ++t) {
-            // all loads of the step are issued before its first MFMA: one wait per 32 latitudes
-            const int i0 = 2 * SH_KV * 4 * t + SH_KV * 4 * h;
-            float4 av[SH_KV], xv[NOP][2][SH_KV];
-#pragma unroll
-            for (int u = 0; u < SH_KV; ++u) {
-                const int iu = i0 + 4 * u;
-                const bool in = iu < nlp;                // (nlp is a multiple of 4: the 16 bytes lie inside the line or outside)
-                av[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (a_on && in) av[u] = *reinterpret_cast<const float4 *>(pa + iu);
-#pragma unroll
-                for (int op = 0; op < NOP; ++op)
-#pragma unroll
-                    for (int cs = 0; cs < 2; ++cs) {
-                        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (f_ok && in) v = *reinterpret_cast<const float4 *>(pb + op * G.op_stride + (int64_t)cs * nlp + iu);
-                        v.x = iu < nlat ? v.x : 0.f;    // the padding of xs is never written
-                        v.y = iu + 1 < nlat ? v.y : 0.f;
-                        v.z = iu + 2 < nlat ? v.z : 0.f;
-                        v.w = iu + 3 < nlat ? v.w : 0.f;
-                        xv[op][cs][u] = v;
-                    }
-            }
-#pragma unroll
-            for (int u = 0; u < SH_KV; ++u) {
-                if (2 * SH_KV * 4 * t + 4 * u >= nlp) break;        // (wave-uniform: both halves of these MFMAs lie beyond the lines)
-#pragma unroll
-                for (int op = 0; op < NOP; ++op)
-#pragma unroll
-                    for (int cs = 0; cs < 2; ++cs) {
-                        const float4 x = xv[op][cs][u];
-                        acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].x, x.x, acc[op][cs], 0, 0, 0);
-                        acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].y, x.y, acc[op][cs], 0, 0, 0);
-                        acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].z, x.z, acc[op][cs], 0, 0, 0);
-                        acc[op][cs] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u].w, x.w, acc[op][cs], 0, 0, 0);
-                    }
-            }
-        }
+        sh_legendre_order<NOP>(G, xs, table, m, nA, fB, f_ok, h, acc);
         const double scale = (m == 0 ? 1.0 : 2.0) * inv_l2;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -339,6 +357,232 @@ __global__ void __launch_bounds__(64) sht_legendre_kernel(ShGeom G, const float 
     }
 }
 
+// ---- coefficients (dlwpcs_sht_analysis) ----------------------------------------------------------------------------------------
+// Stage B with the coefficients as its output: the product of sh_legendre_order in the single form, then
+//   coef[field][row (m, n)] = { fl(Re / L), fl(Im / L) }:  the fp32 sum is divided by L in fp64 and rounded to fp32, which is ONE
+// rounding of the exact quotient (53 >= 2 * 24 + 2 bits: the double rounding of a quotient of two fp32 numbers is innocuous).
+// The orders are independent here, so a workgroup (one wave) owns 32 degrees x 32 fields x SH_MC orders: the grid is (field tiles)
+// x (degree tiles) x (order chunks), and a chunk above its tile's last degree leaves at once.  The scan of the fields' row flags
+// is paid once per chunk.
+__device__ __forceinline__ float sh_div_l(float v, double L) { return (float)((double)v / L); }
+
+__global__ void __launch_bounds__(64) sht_coef_kernel(ShGeom G, const float *__restrict__ xs, const int32_t *__restrict__ bad,
+                                                      const float *__restrict__ table, float2 *__restrict__ coef,
+                                                      int32_t *__restrict__ skipped) {
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= G.n_ft * G.n_nt * G.n_mc) return;
+    const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
+    const int mc = (int)(bid % G.n_mc);
+    const int nt = (int)((bid / G.n_mc) % G.n_nt);
+    const int64_t ft = bid / G.n_mc / G.n_nt;
+    const int T = G.T, K = T + 1, nlat = G.nlat;
+    const int n0 = nt * SH_TILE;
+    const int m_last = n0 + SH_TILE - 1 < T ? n0 + SH_TILE - 1 : T;
+    const int m_begin = mc * SH_MC;
+    if (m_begin > m_last) return;
+    const int m_end = m_begin + SH_MC - 1 < m_last ? m_begin + SH_MC - 1 : m_last;
+    const int nA = n0 + r32;
+    const int64_t fB = ft * SH_TILE + r32;
+    const bool f_ok = fB < G.fields;
+    const int64_t R = (int64_t)K * (K + 1) / 2;
+
+    int isbad = 0;
+    if (f_ok)
+        for (int i = h; i < nlat; i += 2) isbad |= bad[fB * nlat + i];
+    isbad |= __shfl_xor(isbad, 32, 64);
+
+    const double Ld = (double)G.L;
+    const float nan = __uint_as_float(0x7fc00000u);
+    for (int m = m_begin; m <= m_end; ++m) {
+        f32x16 acc[1][2];
+        sh_legendre_order<1>(G, xs, table, m, nA, fB, f_ok, h, acc);
+        if (!f_ok) continue;
+        const int64_t row0 = (int64_t)m * K - (int64_t)m * (m - 1) / 2 - m;       // row (m, n) = row0 + n
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int n = n0 + 8 * (i >> 2) + 4 * h + (i & 3);
+            if (n < m || n > T) continue;
+            coef[fB * R + row0 + n] = isbad ? make_float2(nan, nan) : make_float2(sh_div_l(acc[0][0][i], Ld), sh_div_l(acc[0][1][i], Ld));
+        }
+    }
+    if (skipped && f_ok && nt == 0 && mc == 0 && h == 0) skipped[fB] = isbad ? 1 : 0;
+}
+
+// ---- synthesis (dlwpcs_sht_synthesis) ------------------------------------------------------------------------------------------
+//   x[i, j] = sum_{m=0..T} c_m Re( e^{+2 pi i j m / L} G_m(i) ),   G_m(i) = sum_{n=m..T} P[(m, n)][i] fl(r_n a_n^m),
+// P the UNWEIGHTED fp32 table Pbar_n^m(mu_i) (the packing of the analysis table), r the response (NULL: ones).  Two launches.
+//
+// Inverse Legendre (sht_ilegendre_kernel).  A workgroup is one wave and owns ONE order m, 32 latitudes and 32 fields: the product
+// (32 latitudes x degrees) . (degrees x 32 fields) with the degrees m .. T as the k of v_mfma_f32_32x32x2_f32, two per MFMA (lane
+// half h holds n = m + 2 t + h).  The A operand is one float of table row (m, n) per lane -- the 32 lanes of a half read 32
+// neighbouring latitudes of the row --, the B operand fl(r_n Re a) and fl(r_n Im a) of the lane's field (Im a_n^0 enters as zero).
+// Degrees > T, latitudes >= nlat and fields beyond the last are SELECTED to zero in both operands, never multiplied by zero.  The
+// operands of SH_KU MFMAs per accumulator are loaded before the first of them.  The lane ends with its field and four runs of four
+// latitudes: 16-byte stores into gs[field][m][re | im][nlat_pad] (stage A's layout of xs); the padding is not written.
+// The grid is (field tiles) x (latitude tiles) x (orders): no wave walks the orders, the longest chain is T + 1 degrees.
+__global__ void __launch_bounds__(64) sht_ilegendre_kernel(ShGeom G, const float2 *__restrict__ coef, const float *__restrict__ response,
+                                                           const float *__restrict__ ptable, float *__restrict__ gs) {
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int T = G.T, K = T + 1, nlat = G.nlat, nlp = G.nlp;
+    if (bid >= G.n_ft * G.n_lt * K) return;
+    const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
+    const int m = (int)(bid % K);
+    const int lt = (int)((bid / K) % G.n_lt);
+    const int64_t ft = bid / K / G.n_lt;
+    const int iA = lt * SH_TILE + r32;                   // this lane's latitude as the row of the A operand
+    const int64_t fB = ft * SH_TILE + r32;               // this lane's field as the column of the B operand
+    const bool a_ok = iA < nlat, f_ok = fB < G.fields;
+    const int64_t R = (int64_t)K * (K + 1) / 2;
+    const int64_t row0 = (int64_t)m * K - (int64_t)m * (m - 1) / 2;               // row (m, m)
+    const int count = K - m;                             // degrees m .. T
+    const float *pa = ptable + row0 * nlp + (a_ok ? iA : 0);
+    const float2 *pb = coef + (f_ok ? fB : 0) * R + row0;
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int cs = 0; cs < 2; ++cs)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[cs][i] = 0.f;
+    for (int k0 = 0; k0 < count; k0 += 2 * SH_KU) {
+        float av[SH_KU];
+        float2 bv[SH_KU];
+#pragma unroll
+        for (int u = 0; u < SH_KU; ++u) {
+            const int k = k0 + 2 * u + h;
+            const bool on = k < count;
+            av[u] = 0.f;
+            bv[u] = make_float2(0.f, 0.f);
+            if (on && a_ok) av[u] = pa[(int64_t)k * nlp];
+            if (on && f_ok) {
+                const float2 c = pb[k];
+                const float r = response ? response[m + k] : 1.f;
+                bv[u] = make_float2(r * c.x, m == 0 ? 0.f : r * c.y);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < SH_KU; ++u) {
+            if (k0 + 2 * u >= count) break;              // (wave-uniform)
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u].x, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u].y, acc[1], 0, 0, 0);
+        }
+    }
+
+    // the lane holds field fB (the column) and the latitudes 32 lt + 8 q + 4 h + (0 .. 3)
+    if (f_ok) {
+        float *dst = gs + ((fB * K + m) * 2) * nlp;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = lt * SH_TILE + 8 * q + 4 * h;
+            if (i >= nlat) continue;
+#pragma unroll
+            for (int cs = 0; cs < 2; ++cs) {
+                float *p = dst + (int64_t)cs * nlp + i;
+                if (i + 3 < nlat) {
+                    *reinterpret_cast<float4 *>(p) = make_float4(acc[cs][4 * q], acc[cs][4 * q + 1], acc[cs][4 * q + 2], acc[cs][4 * q + 3]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 3; ++e)
+                        if (i + e < nlat) p[e] = acc[cs][4 * q + e];
+                }
+            }
+        }
+    }
+}
+
+// Inverse Fourier (sht_ifourier_kernel).  The rows (field, latitude) form one list as in stage A; a workgroup of four waves owns 32
+// of them and SH_JT longitudes, 32 per wave.  Per order m ONE MFMA: the A operand is the twiddle of the lane's longitude -- lane
+// half 0 holds c_m cos, half 1 holds -c_m sin (c_m is 1 or 2: exact) from the {cos, -sin} table in LDS at the reduced index
+// (j m) mod L carried along in integers --, the B operand Re G_m (half 0) and Im G_m (half 1) of the lane's row, read from gs with
+// unit stride along the latitudes.  Orders 0 .. T only, in order; longitudes >= L and rows beyond the last are selected to zero.
+// The lane ends with ONE row and four runs of four longitudes: 16-byte stores (VEC) or element stores of the same registers.
+template <bool VEC>
+__global__ void __launch_bounds__(SH_THREADS) sht_ifourier_kernel(ShGeom G, const float *__restrict__ gs, const float2 *__restrict__ twiddle,
+                                                                  float *__restrict__ out) {
+    __shared__ float2 s_tw[SH_MAX_L];
+    __shared__ int64_t s_off[SH_ROWS];                  // offset of the row in the output
+    __shared__ int64_t s_line[SH_ROWS];                 // gs offset of (field, m = 0, re, latitude) of the slot's row
+    __shared__ int s_valid[SH_ROWS];
+
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= G.n_rt * G.n_jt) return;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int jt = (int)(bid % G.n_jt);
+    const int64_t rt = bid / G.n_jt;
+    const int L = G.L, K = G.T + 1, nlp = G.nlp;
+
+    for (int m = tid; m < L; m += SH_THREADS) s_tw[m] = twiddle[m];
+    if (tid < SH_ROWS) {
+        const int64_t r = rt * SH_ROWS + tid;
+        const bool valid = r < G.rows;
+        int64_t off = 0, f = 0;
+        int i = 0;
+        if (valid) {
+            f = r / G.nlat;
+            i = (int)(r - f * G.nlat);
+            int64_t q = f;
+            for (int d = G.n_dims - 1; d >= 0; --d) {
+                const int64_t e = G.ext[d], c = q % e;
+                q /= e;
+                off += c * G.stride[0][d];
+            }
+            off += (int64_t)i * G.lat_stride[0];
+        }
+        s_off[tid] = off;
+        s_line[tid] = f * K * 2 * nlp + i;
+        s_valid[tid] = valid;
+    }
+    __syncthreads();
+
+    const int r32 = lane & 31, h = lane >> 5;
+    const int j0 = jt * SH_JT + wv * SH_TILE;
+    if (j0 >= L) return;
+    const int jA = j0 + r32;                            // this lane's longitude as the row of the A operand
+    const bool a_ok = jA < L, b_ok = s_valid[r32] != 0;
+    const int step = a_ok ? jA : 0;                     // (j m) mod L grows by j per order
+    const float *tw = reinterpret_cast<const float *>(s_tw) + h;
+    const float *pb = gs + (b_ok ? s_line[r32] : 0) + (int64_t)h * nlp;
+
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    int idx = 0;
+    for (int m0 = 0; m0 < K; m0 += SH_KU) {
+        float av[SH_KU], bv[SH_KU];
+#pragma unroll
+        for (int u = 0; u < SH_KU; ++u) {
+            const int m = m0 + u;
+            const bool on = m < K;
+            const float t = tw[2 * idx];
+            av[u] = (on && a_ok) ? (m == 0 ? t : 2.f * t) : 0.f;
+            bv[u] = 0.f;
+            if (on && b_ok) bv[u] = pb[(int64_t)m * 2 * nlp];
+            idx += step; idx -= idx >= L ? L : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < SH_KU; ++u) {
+            if (m0 + u >= K) break;                     // (wave-uniform)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
+        }
+    }
+
+    // the lane holds row slot r32 (the column) and the longitudes j0 + 8 q + 4 h + (0 .. 3)
+    if (b_ok) {
+        float *dst = out + s_off[r32];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = j0 + 8 * q + 4 * h;
+            if (j >= L) continue;
+            if constexpr (VEC) {                        // (L % 4 == 0: the 16 bytes lie inside the row)
+                *reinterpret_cast<float4 *>(dst + j) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (j + e < L) dst[j + e] = acc[4 * q + e];
+            }
+        }
+    }
+}
+
 namespace {
 
 struct ShPlan {
@@ -347,17 +591,17 @@ struct ShPlan {
     size_t xs_bytes, bad_bytes;
 };
 
-int sh_plan(const dlwpcs_sht_spectrum_desc *d, bool pair, ShPlan &P) {
-    if (!d) return fail(DLWPCS_E_INVALID, "sht_spectrum: null descriptor");
-    if (d->L < 2) return fail(DLWPCS_E_INVALID, "sht_spectrum: L = %d (at least 2 longitudes)", d->L);
-    if (d->L > SH_MAX_L) return fail(DLWPCS_E_UNSUPPORTED, "sht_spectrum: L = %d, this build serves 2 <= L <= %d", d->L, SH_MAX_L);
-    if (d->nlat < 2) return fail(DLWPCS_E_INVALID, "sht_spectrum: nlat = %d (at least 2 latitudes)", d->nlat);
+int sh_plan(const dlwpcs_sht_spectrum_desc *d, bool pair, ShPlan &P, const char *who = "sht_spectrum") {
+    if (!d) return fail(DLWPCS_E_INVALID, "%s: null descriptor", who);
+    if (d->L < 2) return fail(DLWPCS_E_INVALID, "%s: L = %d (at least 2 longitudes)", who, d->L);
+    if (d->L > SH_MAX_L) return fail(DLWPCS_E_UNSUPPORTED, "%s: L = %d, this build serves 2 <= L <= %d", who, d->L, SH_MAX_L);
+    if (d->nlat < 2) return fail(DLWPCS_E_INVALID, "%s: nlat = %d (at least 2 latitudes)", who, d->nlat);
     if (d->nlat > DLWPCS_SHT_MAX_NLAT)
-        return fail(DLWPCS_E_UNSUPPORTED, "sht_spectrum: nlat = %d, this build serves 2 <= nlat <= %d", d->nlat, DLWPCS_SHT_MAX_NLAT);
+        return fail(DLWPCS_E_UNSUPPORTED, "%s: nlat = %d, this build serves 2 <= nlat <= %d", who, d->nlat, DLWPCS_SHT_MAX_NLAT);
     if (d->T < 0 || 2 * (int64_t)d->T + 1 > d->L)
-        return fail(DLWPCS_E_INVALID, "sht_spectrum: truncation T = %d needs 0 <= T and L >= 2 T + 1 = %lld longitudes, L = %d", d->T,
+        return fail(DLWPCS_E_INVALID, "%s: truncation T = %d needs 0 <= T and L >= 2 T + 1 = %lld longitudes, L = %d", who, d->T,
                     2 * (long long)d->T + 1, d->L);
-    if (d->n_dims < 0 || d->n_dims > DLWPCS_SCORE_MAX_DIMS) return fail(DLWPCS_E_INVALID, "sht_spectrum: n_dims %d out of range", d->n_dims);
+    if (d->n_dims < 0 || d->n_dims > DLWPCS_SCORE_MAX_DIMS) return fail(DLWPCS_E_INVALID, "%s: n_dims %d out of range", who, d->n_dims);
     ShGeom &G = P.G;
     memset(&G, 0, sizeof(G));
     G.nlat = d->nlat;
@@ -373,14 +617,14 @@ int sh_plan(const dlwpcs_sht_spectrum_desc *d, bool pair, ShPlan &P) {
     }
     for (int i = 0; i < d->n_dims; ++i) {
         const int64_t e = d->ext[i];
-        if (e < 0 || e >= (1ll << 31)) return fail(DLWPCS_E_INVALID, "sht_spectrum: extent %lld of dim %d", (long long)e, i);
+        if (e < 0 || e >= (1ll << 31)) return fail(DLWPCS_E_INVALID, "%s: extent %lld of dim %d", who, (long long)e, i);
         G.ext[i] = e;
         for (int op = 0; op < 2; ++op) {
             G.stride[op][i] = d->stride[op][i];
             if (op == 0 || pair) vec = vec && d->stride[op][i] % 4 == 0;
         }
         G.fields *= e;
-        if (G.fields >= (1ll << 31)) return fail(DLWPCS_E_UNSUPPORTED, "sht_spectrum: too many fields");
+        if (G.fields >= (1ll << 31)) return fail(DLWPCS_E_UNSUPPORTED, "%s: too many fields", who);
     }
     P.vec_ok = vec;
     G.rows = G.fields * G.nlat;
@@ -389,7 +633,10 @@ int sh_plan(const dlwpcs_sht_spectrum_desc *d, bool pair, ShPlan &P) {
     G.n_ft = (G.fields + SH_TILE - 1) / SH_TILE;
     G.n_nt = (G.T + 1 + SH_TILE - 1) / SH_TILE;
     G.op_stride = G.fields * (G.T + 1) * 2 * G.nlp;
-    if (G.n_rt * G.n_mt > 65536ll * 65535ll) return fail(DLWPCS_E_UNSUPPORTED, "sht_spectrum: too many workgroups");
+    G.n_mc = (G.T + 1 + SH_MC - 1) / SH_MC;
+    G.n_lt = (G.nlat + SH_TILE - 1) / SH_TILE;
+    G.n_jt = (G.L + SH_JT - 1) / SH_JT;
+    if (G.n_rt * G.n_mt > SH_MAX_GRID) return fail(DLWPCS_E_UNSUPPORTED, "%s: too many workgroups", who);
     P.xs_bytes = (size_t)G.op_stride * sizeof(float) * (pair ? 2 : 1);
     P.bad_bytes = (size_t)G.rows * sizeof(int32_t);
     return DLWPCS_OK;
@@ -443,4 +690,100 @@ extern "C" int dlwpcs_sht_spectrum(const dlwpcs_sht_spectrum_desc *d, const floa
     if (pair) hipLaunchKernelGGL((sht_legendre_kernel<true>), grid_b, dim3(64), 0, s, G, xs, bad, legendre, out, skipped);
     else hipLaunchKernelGGL((sht_legendre_kernel<false>), grid_b, dim3(64), 0, s, G, xs, bad, legendre, out, skipped);
     return check_launch("sht_spectrum");
+}
+
+extern "C" size_t dlwpcs_sht_analysis_scratch_bytes(const dlwpcs_sht_spectrum_desc *d) {
+    ShPlan P;
+    if (sh_plan(d, false, P, "sht_analysis") != DLWPCS_OK) return 0;
+    return P.xs_bytes + P.bad_bytes;
+}
+
+extern "C" int dlwpcs_sht_analysis(const dlwpcs_sht_spectrum_desc *d, const float *a, const float *twiddle, const float *legendre,
+                                   void *scratch, float *coef, int32_t *skipped, dlwpcs_stream_t stream) {
+    ShPlan P;
+    const int rc = sh_plan(d, false, P, "sht_analysis");
+    if (rc != DLWPCS_OK) return rc;
+    const ShGeom &G = P.G;
+    if (G.n_ft * G.n_nt * G.n_mc > SH_MAX_GRID) return fail(DLWPCS_E_UNSUPPORTED, "sht_analysis: too many workgroups");
+    if (!twiddle || !legendre) return fail(DLWPCS_E_INVALID, "sht_analysis: null twiddle or Legendre table");
+    if (((uintptr_t)twiddle) & 7) return fail(DLWPCS_E_INVALID, "sht_analysis: the twiddle table is not aligned to 8 bytes");
+    if (((uintptr_t)legendre) & 15) return fail(DLWPCS_E_INVALID, "sht_analysis: the Legendre table is not aligned to 16 bytes");
+    if (G.fields == 0) return DLWPCS_OK;
+    if (!coef || !a) return fail(DLWPCS_E_INVALID, "sht_analysis: null source or output");
+    if ((((uintptr_t)a) | ((uintptr_t)skipped)) & 3)
+        return fail(DLWPCS_E_INVALID, "sht_analysis: an operand is not aligned to its 4-byte elements");
+    if (((uintptr_t)coef) & 7) return fail(DLWPCS_E_INVALID, "sht_analysis: the coefficients are not aligned to their 8-byte pairs");
+    if (!scratch || (((uintptr_t)scratch) & 15))
+        return fail(DLWPCS_E_INVALID, "sht_analysis: this descriptor needs a 16-byte aligned scratch of %zu bytes", P.xs_bytes + P.bad_bytes);
+    float *xs = (float *)scratch;
+    int32_t *bad = (int32_t *)((char *)scratch + P.xs_bytes);
+    const bool vec = P.vec_ok && !(((uintptr_t)a) & 15);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid_a = sh_grid(G.n_rt * G.n_mt), grid_b = sh_grid(G.n_ft * G.n_nt * G.n_mc);
+    const float2 *tw = (const float2 *)twiddle;
+    const float *none = nullptr;
+    if (vec) hipLaunchKernelGGL((sht_fourier_kernel<false, true>), grid_a, dim3(SH_THREADS), 0, s, G, a, none, tw, xs, bad);
+    else hipLaunchKernelGGL((sht_fourier_kernel<false, false>), grid_a, dim3(SH_THREADS), 0, s, G, a, none, tw, xs, bad);
+    hipLaunchKernelGGL(sht_coef_kernel, grid_b, dim3(64), 0, s, G, xs, bad, legendre, (float2 *)coef, skipped);
+    return check_launch("sht_analysis");
+}
+
+namespace {
+
+int sh_synthesis_plan(const dlwpcs_sht_synthesis_desc *d, ShPlan &P) {
+    if (!d) return fail(DLWPCS_E_INVALID, "sht_synthesis: null descriptor");
+    if (d->n_dims < 0 || d->n_dims > DLWPCS_SCORE_MAX_DIMS) return fail(DLWPCS_E_INVALID, "sht_synthesis: n_dims %d out of range", d->n_dims);
+    dlwpcs_sht_spectrum_desc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.nlat = d->nlat;
+    sd.L = d->L;
+    sd.T = d->T;
+    sd.n_dims = d->n_dims;
+    sd.lat_stride[0] = d->lat_stride;
+    for (int i = 0; i < d->n_dims; ++i) {
+        sd.ext[i] = d->ext[i];
+        sd.stride[0][i] = d->stride[i];
+    }
+    const int rc = sh_plan(&sd, false, P, "sht_synthesis");
+    if (rc != DLWPCS_OK) return rc;
+    const ShGeom &G = P.G;
+    if (G.n_ft * G.n_lt * (G.T + 1) > SH_MAX_GRID || G.n_rt * G.n_jt > SH_MAX_GRID)
+        return fail(DLWPCS_E_UNSUPPORTED, "sht_synthesis: too many workgroups");
+    return DLWPCS_OK;
+}
+
+}  // namespace
+
+// gs alone: [field][m][re | im][nlat_pad] fp32
+extern "C" size_t dlwpcs_sht_synthesis_scratch_bytes(const dlwpcs_sht_synthesis_desc *d) {
+    ShPlan P;
+    if (sh_synthesis_plan(d, P) != DLWPCS_OK) return 0;
+    return P.xs_bytes;
+}
+
+extern "C" int dlwpcs_sht_synthesis(const dlwpcs_sht_synthesis_desc *d, const float *coef, const float *response, const float *twiddle,
+                                    const float *legendre, void *scratch, float *out, dlwpcs_stream_t stream) {
+    ShPlan P;
+    const int rc = sh_synthesis_plan(d, P);
+    if (rc != DLWPCS_OK) return rc;
+    const ShGeom &G = P.G;
+    if (!twiddle || !legendre) return fail(DLWPCS_E_INVALID, "sht_synthesis: null twiddle or Legendre table");
+    if (((uintptr_t)twiddle) & 7) return fail(DLWPCS_E_INVALID, "sht_synthesis: the twiddle table is not aligned to 8 bytes");
+    if (((uintptr_t)legendre) & 15) return fail(DLWPCS_E_INVALID, "sht_synthesis: the Legendre table is not aligned to 16 bytes");
+    if (G.fields == 0) return DLWPCS_OK;
+    if (!coef || !out) return fail(DLWPCS_E_INVALID, "sht_synthesis: null coefficients or output");
+    if ((((uintptr_t)out) | ((uintptr_t)response)) & 3)
+        return fail(DLWPCS_E_INVALID, "sht_synthesis: an operand is not aligned to its 4-byte elements");
+    if (((uintptr_t)coef) & 7) return fail(DLWPCS_E_INVALID, "sht_synthesis: the coefficients are not aligned to their 8-byte pairs");
+    if (!scratch || (((uintptr_t)scratch) & 15))
+        return fail(DLWPCS_E_INVALID, "sht_synthesis: this descriptor needs a 16-byte aligned scratch of %zu bytes", P.xs_bytes);
+    float *gs = (float *)scratch;
+    const bool vec = P.vec_ok && !(((uintptr_t)out) & 15);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid_l = sh_grid(G.n_ft * G.n_lt * (G.T + 1)), grid_f = sh_grid(G.n_rt * G.n_jt);
+    const float2 *tw = (const float2 *)twiddle;
+    hipLaunchKernelGGL(sht_ilegendre_kernel, grid_l, dim3(64), 0, s, G, (const float2 *)coef, response, legendre, gs);
+    if (vec) hipLaunchKernelGGL((sht_ifourier_kernel<true>), grid_f, dim3(SH_THREADS), 0, s, G, (const float *)gs, tw, out);
+    else hipLaunchKernelGGL((sht_ifourier_kernel<false>), grid_f, dim3(SH_THREADS), 0, s, G, (const float *)gs, tw, out);
+    return check_launch("sht_synthesis");
 }

@@ -788,6 +788,52 @@ int dlwpcs_sht_spectrum(const dlwpcs_sht_spectrum_desc *d, const float *a, const
                         int32_t *skipped /* may be NULL */, dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Spherical-harmonic analysis and synthesis (DLWP/verify.py spherical_analysis, spherical_synthesis, spherical_filter,
+ * spherical_laplacian), with the definitions, tables and limits of dlwpcs_sht_spectrum above.
+ *
+ * dlwpcs_sht_analysis: the coefficients a_n^m of the fields of operand a (operand 0 of the descriptor; operand 1 is not read),
+ *   coef[field][row (m, n)][re, im] fp32, dense, (T + 1)(T + 2) / 2 rows per field in the order of the Legendre table, 8-byte
+ *   aligned.  Two launches: stage A of dlwpcs_sht_spectrum in its single form, then its stage B storing coefficients: the same
+ *   tiles, operand mapping and masks, a workgroup owning 32 degrees x 32 fields x 8 orders.  Rounding: the fp32 sum over the
+ *   latitudes is divided by L in fp64 and rounded to fp32 -- ONE rounding of the exact quotient (the quotient of two fp32 numbers
+ *   rounded to 53 bits and then to 24 equals the quotient rounded to 24).  Im a_n^0 is what the sum gives (+-0).  A field that
+ *   holds a NaN or an infinity gets all-NaN coefficients and a 1 in skipped (may be NULL; 0 for every other field).
+ *   scratch >= dlwpcs_sht_analysis_scratch_bytes(d), 16-byte aligned.
+ *
+ * dlwpcs_sht_synthesis: x[i, j] = sum_{m=0..T} c_m Re( e^{+2 pi i j m / L} sum_{n=m..T} r_n a_n^m Pbar_n^m(mu_i) ), c_0 = 1 and
+ *   c_m = 2 otherwise, for every field of coef (layout above), written through the descriptor's leading strides and latitude
+ *   stride with longitude at unit stride.  response: T + 1 floats r_n, or NULL, which gives the bits of a response of ones.
+ *   Im a_n^0 is ignored.  For a field band-limited to T, synthesis(analysis(x)) = x up to rounding.
+ *   legendre here is the UNWEIGHTED table Pbar_n^m(mu_i) in fp32, each entry evaluated in fp64 and rounded once, with the
+ *   packing, padding and alignment of the analysis table (it is NOT the analysis table divided by the weights).
+ *   Two launches.  Inverse Legendre: per order m the product (latitudes x degrees) . (degrees x fields) on
+ *   v_mfma_f32_32x32x2_f32, G_m(i) = sum_n P[(m, n)][i] fl(r_n a_n^m) with the degrees in order, two per instruction; a workgroup
+ *   (one wave) owns one order, 32 latitudes and 32 fields; written to scratch as gs[field][m][re | im][nlat_pad].  Inverse
+ *   Fourier: per 32 rows (field, latitude) and 32 longitudes one instruction per order m = 0 .. T in order, the operands
+ *   {c_m cos, -c_m sin}(2 pi j m / L) from dlwpcs_zonal_spectrum's twiddle table at the reduced index (j m) mod L and {Re, Im} G_m;
+ *   16-byte stores where L, the strides and the pointer are multiples of 4 elements, element stores of the same values otherwise.
+ *   Masked degrees, latitudes, longitudes and fields are selected to zero in both operands.  A field with NaN coefficients comes
+ *   out NaN and touches no other field.  scratch >= dlwpcs_sht_synthesis_scratch_bytes(d), 16-byte aligned.
+ * Both: no atomics, a fixed summation order (bitwise repeatable), no host synchronisation, no allocation; a field's result
+ * depends on its own data only; zero fields is success without a launch.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct dlwpcs_sht_synthesis_desc {
+    int32_t nlat;                /* latitudes */
+    int32_t L;                   /* longitudes per row */
+    int32_t T;                   /* truncation: degrees 0 .. T */
+    int32_t n_dims;              /* leading dims of the output, at most DLWPCS_SCORE_MAX_DIMS */
+    int64_t lat_stride;          /* elements between the latitudes of a field of the output */
+    int64_t ext[DLWPCS_SCORE_MAX_DIMS];
+    int64_t stride[DLWPCS_SCORE_MAX_DIMS];        /* elements */
+} dlwpcs_sht_synthesis_desc;
+size_t dlwpcs_sht_analysis_scratch_bytes(const dlwpcs_sht_spectrum_desc *d);
+int dlwpcs_sht_analysis(const dlwpcs_sht_spectrum_desc *d, const float *a, const float *twiddle, const float *legendre,
+                        void *scratch, float *coef, int32_t *skipped /* may be NULL */, dlwpcs_stream_t stream);
+size_t dlwpcs_sht_synthesis_scratch_bytes(const dlwpcs_sht_synthesis_desc *d);
+int dlwpcs_sht_synthesis(const dlwpcs_sht_synthesis_desc *d, const float *coef, const float *response /* NULL: ones */,
+                         const float *twiddle, const float *legendre, void *scratch, float *out, dlwpcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Ensemble scores (DLWP/verify.py ensemble_mean, ensemble_spread, ensemble_crps, ensemble_error, rank_histogram): the member
  * axis of an fp32 ensemble collapsed element by element.  The element dims arrive as n_dims merged dims with an extent and an
  * element stride per operand (0: ens, 1: valid; 0 = broadcast), the members lie member_stride elements apart: a permuted view
