@@ -277,6 +277,12 @@ PROTOTYPES = {
     'dlwpcs_sht_analysis': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sht_synthesis_scratch_bytes': (c_size_t, [c_void_p]),
     'dlwpcs_sht_synthesis': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_sht_vector_synthesis_scratch_bytes': (c_size_t, [c_void_p]),
+    'dlwpcs_sht_vector_synthesis': (c_int, [c_void_p] * 12),
+    'dlwpcs_sht_vector_analysis_scratch_bytes': (c_size_t, [c_void_p]),
+    'dlwpcs_sht_vector_analysis': (c_int, [c_void_p] * 12),
+    'dlwpcs_barotropic_flux': (c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32] + [c_void_p] * 7),
+    'dlwpcs_barotropic_update': (c_int, [ctypes.c_int64, ctypes.c_int64, c_void_p, c_float, c_float, ctypes.c_int32] + [c_void_p] * 4),
     'dlwpcs_ensemble_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_ensemble_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_count': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -2338,6 +2338,240 @@ def spherical_synthesis(coef, transform, response=None, out=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------ #
+# Vector spherical harmonics (DLWP/verify.py spherical_uv / spherical_vrtdiv / spherical_gradient, DLWP/barotropic),
+# include/dlwpcs.h dlwpcs_sht_vector_synthesis / dlwpcs_sht_vector_analysis; the tables come from SphericalTransform
+# ------------------------------------------------------------------------------------------------------------------ #
+
+VECTOR_OUTPUTS = ('vrt', 'div')
+
+
+def sht_vector_synthesis_launch(d, coef_a, coef_b, rpsi, rchi, tables, out_u, out_v):
+    """dlwpcs_sht_vector_synthesis on the current stream: float32 tensors coef_a, coef_b (fields, rows, 2; either None), the
+    responses (T + 1 floats or None) and `tables` = SphericalTransform.device_vector_tables, into out_u (operand 0 of the
+    descriptor) and out_v (operand 1)"""
+    dev = out_u.device
+    nbytes = int(lib().dlwpcs_sht_vector_synthesis_scratch_bytes(ctypes.byref(d)))
+    scratch = _workspace(nbytes, dev, 'sht_synth') if nbytes else None
+    with torch.cuda.device(dev):
+        check(lib().dlwpcs_sht_vector_synthesis(ctypes.byref(d), ptr(coef_a) or None, ptr(coef_b) or None, ptr(rpsi) or None,
+                                                ptr(rchi) or None, ptr(tables[0]), ptr(tables[1]), ptr(tables[2]),
+                                                ptr(scratch) or None, ptr(out_u), ptr(out_v), stream_ptr()),
+              'dlwpcs_sht_vector_synthesis')
+
+
+def sht_vector_analysis_launch(d, u, v, response, tables, vrt, div, skipped=None):
+    """dlwpcs_sht_vector_analysis on the current stream: the device tensors u, v addressed by the descriptor, into the float32
+    tensors vrt, div (fields, rows, 2; either None) and the int32 tensor `skipped` (fields; None: not wanted)"""
+    dev = u.device
+    nbytes = int(lib().dlwpcs_sht_vector_analysis_scratch_bytes(ctypes.byref(d)))
+    scratch = _workspace(nbytes, dev, 'sht') if nbytes else None
+    with torch.cuda.device(dev):
+        check(lib().dlwpcs_sht_vector_analysis(ctypes.byref(d), ptr(u), ptr(v), ptr(response) or None, ptr(tables[0]), ptr(tables[3]),
+                                               ptr(tables[4]), ptr(scratch) or None, ptr(vrt) or None, ptr(div) or None,
+                                               ptr(skipped) or None, stream_ptr()), 'dlwpcs_sht_vector_analysis')
+
+
+def _view_span(t, period):
+    """(ok, span): span = the elements covered by one block of the dims of `t` with a stride below `period`; ok when every other
+    stride is a multiple of `period`, so that the view lies in the blocks [k period, k period + span)"""
+    span, ok = 1, True
+    for n, st in zip(t.shape, t.stride()):
+        if n <= 1:
+            continue
+        if st < period:
+            span += (int(n) - 1) * int(st)
+        elif st % period:
+            ok = False
+    return ok, span
+
+
+def _may_overlap(a, b):
+    """False when the float32 views a and b provably share no element: their address ranges are apart, or both lie in periodic
+    blocks of one period (a stride of either) that never meet, as two slices of one interleaved buffer do.  True otherwise."""
+    if not a.numel() or not b.numel():
+        return False
+    lo_a, lo_b = a.data_ptr() // 4, b.data_ptr() // 4
+    ext = lambda t: 1 + sum((int(n) - 1) * int(st) for n, st in zip(t.shape, t.stride()))      # noqa: E731
+    if any(st < 0 for t in (a, b) for st in t.stride()):
+        return True
+    if lo_a + ext(a) <= lo_b or lo_b + ext(b) <= lo_a:
+        return False
+    if lo_a > lo_b:
+        a, b, lo_a, lo_b = b, a, lo_b, lo_a
+    for period in sorted({int(st) for t in (a, b) for n, st in zip(t.shape, t.stride()) if n > 1 and st > 1}):
+        (ok_a, span_a), (ok_b, span_b) = _view_span(a, period), _view_span(b, period)
+        r = (lo_b - lo_a) % period
+        if ok_a and ok_b and span_a <= r and r + span_b <= period:
+            return False
+    return True
+
+
+def _sht_coef_operand(c, rows, who):
+    if not isinstance(c, torch.Tensor) or c.dtype != torch.complex64:
+        raise TypeError('%s: the coefficients must be a complex64 tensor, got %s' % (who, c.dtype if isinstance(c, torch.Tensor) else type(c)))
+    if c.dim() < 1 or int(c.shape[-1]) != rows:
+        raise ValueError('%s: %s coefficients, the truncation has %d per field' % (who, tuple(c.shape), rows))
+    require_device(torch.view_as_real(c), who)
+    return c
+
+
+def spherical_vector_synthesis(A, B, transform, rpsi=None, rchi=None, out_u=None, out_v=None):
+    """
+    The wind (u, v) of the potentials psi_n^m = rpsi_n A_n^m and chi_n^m = rchi_n B_n^m on the grid of `transform`:
+        u = -dpsi/dphi + (1/cos) dchi/dlambda,   v = (1/cos) dpsi/dlambda + dchi/dphi
+    (the factor 1 / radius belongs in the responses).  A, B: complex64 device tensors (leading axes..., (T + 1)(T + 2) / 2) of one
+    shape; either may be None (it then costs nothing), not both.  rpsi, rchi: T + 1 real factors per degree (float32 device vector
+    or host array; None: ones, with the same bits).  out_u, out_v: float32 device tensors (leading axes..., nlat, L) to write into,
+    any strides with longitude at unit stride, the two apart (two slices of one interleaved buffer are).  Returns (u, v).  Three launches of dlwpcs_sht_vector_synthesis on the current
+    stream, no host synchronisation (the tables of a transform are uploaded at their first use).
+    """
+    who = 'spherical_vector_synthesis'
+    if transform is None:
+        raise TypeError('%s: a SphericalTransform is required' % who)
+    if A is None and B is None:
+        raise ValueError('%s: both potentials are absent' % who)
+    nlat, L, T = transform.nlat, transform.n_lon, int(transform.truncation)
+    rows = (T + 1) * (T + 2) // 2
+    pots = [None if c is None else _sht_coef_operand(c, rows, who) for c in (A, B)]
+    first = pots[0] if pots[0] is not None else pots[1]
+    if pots[0] is not None and pots[1] is not None and (pots[0].shape != pots[1].shape or pots[0].device != pots[1].device):
+        raise ValueError('%s: the two potentials must have one shape and one device' % who)
+    if L > SPECTRUM_MAX_L:
+        raise NotImplementedError('%s: %d longitudes, the kernel serves 2 .. %d' % (who, L, SPECTRUM_MAX_L))
+    if nlat > nat.SHT_MAX_NLAT:
+        raise NotImplementedError('%s: %d latitudes, the kernel serves 2 .. %d' % (who, nlat, nat.SHT_MAX_NLAT))
+    dev = first.device
+    lead = tuple(int(e) for e in first.shape[:-1])
+    outs = []
+    for o in (out_u, out_v):
+        if o is None:
+            o = torch.empty(lead + (nlat, L), dtype=torch.float32, device=dev)
+        else:
+            require_device(o, who)
+            if o.dtype != torch.float32 or o.device != dev or tuple(o.shape) != lead + (nlat, L):
+                raise ValueError('%s: an output must be a float32 tensor of shape %s on the device of the coefficients'
+                                 % (who, lead + (nlat, L)))
+            if o.stride(-1) != 1:
+                raise ValueError('%s: an output needs unit stride along longitude' % who)
+        outs.append(o)
+    if _may_overlap(outs[0], outs[1]):
+        raise ValueError('%s: out_u and out_v overlap (or cannot be shown to be apart)' % who)
+    rp = _sht_response(rpsi, T, dev, who) if pots[0] is not None else None
+    rc = _sht_response(rchi, T, dev, who) if pots[1] is not None else None
+    if int(np.prod(lead, dtype=np.int64)):
+        flat = [None if c is None else torch.view_as_real(c.contiguous()) for c in pots]
+        tables = transform.device_vector_tables(dev)
+        strides = [tuple(int(s) for s in o.stride()[:-2]) for o in outs]
+        d = sht_desc(nlat, L, T, spectrum_dims(lead, strides, ()), [int(o.stride(-2)) for o in outs])
+        sht_vector_synthesis_launch(d, flat[0], flat[1], rp, rc, tables, outs[0], outs[1])
+    return outs[0], outs[1]
+
+
+def spherical_vector_analysis(u, v, transform, response=None, want=VECTOR_OUTPUTS, lat_axis=-2, lon_axis=-1, counts=False):
+    """
+    The vorticity-like and divergence-like coefficients of the float32 device tensors u, v (one shape, the grid of `transform` on
+    `lat_axis` and `lon_axis`):  vrt_n^m = r_n sum_i (w_i / 2) [i Q V_m + D U_m] / L,  div_n^m = r_n sum_i (w_i / 2) [i Q U_m - D V_m] / L.
+    response: T + 1 real factors r_n (1 / radius for vorticity and divergence; None: ones).  want: which of 'vrt', 'div', a tuple;
+    the result is a tuple of complex64 device tensors (leading axes..., (T + 1)(T + 2) / 2) in that order, and an output that is
+    not wanted costs nothing.  A field with a NaN or an infinity in u or in v has NaN coefficients in every output; counts=True:
+    also the int32 tensor (leading axes...) that holds 1 for such a field.  Two launches of dlwpcs_sht_vector_analysis.
+    """
+    who = 'spherical_vector_analysis'
+    if transform is None:
+        raise TypeError('%s: a SphericalTransform is required' % who)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in VECTOR_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError('%s: want %s, a non-empty choice of %s' % (who, want, VECTOR_OUTPUTS))
+    for t in (u, v):
+        require_device(t, who)
+        if t.dtype != torch.float32:
+            raise TypeError('%s: operands must be float32, got %s' % (who, t.dtype))
+    if u.shape != v.shape or u.device != v.device:
+        raise ValueError('%s: u and v must have one shape and one device' % who)
+    lat, lon = _sht_grid_axes(u, transform, lat_axis, lon_axis, who)
+    nlat, L, T = transform.nlat, transform.n_lon, int(transform.truncation)
+    lead_axes = [i for i in range(u.dim()) if i not in (lat, lon)]
+    ts = [t.permute(lead_axes + [lat, lon]) for t in (u, v)]
+    ts = [t.contiguous() if t.stride(-1) != 1 else t for t in ts]
+    lead = tuple(int(e) for e in ts[0].shape[:-2])
+    rows = (T + 1) * (T + 2) // 2
+    dev = u.device
+    out = {w: torch.empty(lead + (rows, 2), dtype=torch.float32, device=dev) for w in want}
+    flags = torch.empty(lead, dtype=torch.int32, device=dev) if counts else None
+    resp = _sht_response(response, T, dev, who)
+    if int(np.prod(lead, dtype=np.int64)):
+        tables = transform.device_vector_tables(dev)
+        strides = [tuple(int(s) for s in t.stride()[:-2]) for t in ts]
+        d = sht_desc(nlat, L, T, spectrum_dims(lead, strides, ()), [int(t.stride(-2)) for t in ts])
+        sht_vector_analysis_launch(d, ts[0], ts[1], resp, tables, out.get('vrt'), out.get('div'), flags)
+    res = tuple(torch.view_as_complex(out[w]) for w in want)
+    return res + (flags,) if counts else res
+
+
+def barotropic_flux(zeta, u, v, coriolis, out_f=None, out_g=None):
+    """((f_i + zeta) u, (f_i + zeta) v) of the contiguous float32 device tensors zeta, u, v (..., nlat, L) and the float32 device
+    vector `coriolis` of nlat values; out_f, out_g: contiguous tensors of that shape to write into.  One launch."""
+    who = 'barotropic_flux'
+    for t in (zeta, u, v, coriolis):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != zeta.device:
+            raise TypeError('%s: operands must be contiguous float32 tensors on one device' % who)
+        require_device(t, who)
+    if zeta.dim() < 2 or u.shape != zeta.shape or v.shape != zeta.shape:
+        raise ValueError('%s: zeta, u and v must have one shape (..., nlat, L)' % who)
+    nlat, L = int(zeta.shape[-2]), int(zeta.shape[-1])
+    if coriolis.dim() != 1 or int(coriolis.numel()) != nlat:
+        raise ValueError('%s: %d Coriolis values for %d latitudes' % (who, int(coriolis.numel()), nlat))
+    outs = []
+    for o in (out_f, out_g):
+        if o is None:
+            o = torch.empty_like(zeta)
+        else:
+            require_device(o, who)
+            if o.dtype != torch.float32 or o.shape != zeta.shape or not o.is_contiguous() or o.device != zeta.device:
+                raise ValueError('%s: an output must be a contiguous float32 tensor of the shape of zeta' % who)
+        outs.append(o)
+    if _may_overlap(outs[0], outs[1]) or any(_may_overlap(o, t) for o in outs for t in (zeta, u, v)):
+        raise ValueError('%s: an output overlaps the other output or an input' % who)
+    fields = int(zeta.numel()) // (nlat * L) if nlat * L else 0
+    if fields:
+        with torch.cuda.device(zeta.device):
+            check(lib().dlwpcs_barotropic_flux(fields, nlat, L, ptr(coriolis), ptr(zeta), ptr(u), ptr(v), ptr(outs[0]), ptr(outs[1]),
+                                               stream_ptr()), 'dlwpcs_barotropic_flux')
+    return outs[0], outs[1]
+
+
+def barotropic_update(tend, zeta, zeta_prev, damp, dt, robert, first_step):
+    """One time step of the barotropic model in place on the contiguous complex64 device tensors zeta, zeta_prev (..., rows), given
+    the tendency `tend` of that shape (a third buffer) and the float32 device vector `damp` of rows damping rates (include/dlwpcs.h
+    dlwpcs_barotropic_update states the scheme).  One launch.  Returns (zeta, zeta_prev)."""
+    who = 'barotropic_update'
+    for t in (tend, zeta, zeta_prev):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.complex64:
+            raise TypeError('%s: tend, zeta and zeta_prev must be complex64 tensors' % who)
+        require_device(torch.view_as_real(t), who)
+        if not t.is_contiguous() or t.shape != zeta.shape or t.device != zeta.device:
+            raise ValueError('%s: tend, zeta and zeta_prev must be contiguous, of one shape and on one device' % who)
+    require_device(damp, who)
+    if zeta.dim() < 1:
+        raise ValueError('%s: the coefficients need an axis' % who)
+    rows = int(zeta.shape[-1])
+    if damp.dtype != torch.float32 or damp.dim() != 1 or int(damp.numel()) != rows or not damp.is_contiguous() or damp.device != zeta.device:
+        raise ValueError('%s: damp must be a contiguous float32 vector of %d rates on the device of zeta' % (who, rows))
+    parts = [torch.view_as_real(t) for t in (tend, zeta, zeta_prev)]
+    if _may_overlap(parts[1], parts[2]):
+        raise ValueError('%s: zeta and zeta_prev must be two buffers' % who)
+    if _may_overlap(parts[0], parts[1]) or _may_overlap(parts[0], parts[2]):
+        raise ValueError('%s: tend overlaps a state' % who)
+    fields = int(zeta.numel()) // rows if rows else 0
+    if fields:
+        with torch.cuda.device(zeta.device):
+            check(lib().dlwpcs_barotropic_update(fields, rows, ptr(damp), float(dt), float(robert), int(bool(first_step)),
+                                                 ptr(torch.view_as_real(tend)), ptr(torch.view_as_real(zeta)),
+                                                 ptr(torch.view_as_real(zeta_prev)), stream_ptr()), 'dlwpcs_barotropic_update')
+    return zeta, zeta_prev
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
 # Ensemble scores (DLWP/verify.py ensemble_* / rank_histogram), include/dlwpcs.h dlwpcs_ensemble_stats
 # ------------------------------------------------------------------------------------------------------------------ #
 

@@ -12,6 +12,14 @@ Synthesis with a real response r_n (device: ops.spherical_synthesis / dlwpcs_sht
     x[i, j] = sum_{m=0..T} c_m Re( exp(+2 pi i j m / L) sum_{n=m..T} r_n a_n^m Pbar_n^m(mu_i) );   Im a_n^0 is ignored,
 and synthesis(analysis(x)) = x for a field band-limited to T.  Coefficients are packed in the order of packed_row(m, n, T).
 
+Vector harmonics (device: ops.spherical_vector_synthesis / spherical_vector_analysis, dlwpcs_sht_vector_*).  With phi the latitude,
+D_n^m = dPbar_n^m / dphi and Q_n^m = m Pbar_n^m / cos(phi) (derivative_table, zonal_table; their limits at a pole row), potentials
+psi_n^m = rpsi_n A_n^m, chi_n^m = rchi_n B_n^m give the wind u = -dpsi/dphi + (1/cos) dchi/dlambda, v = (1/cos) dpsi/dlambda + dchi/dphi:
+    U_m(i) = sum_n [-D psi + i Q chi],   V_m(i) = sum_n [i Q psi + D chi],   then the inverse Fourier stage of the synthesis,
+and a wind gives  vrt_n^m = r_n sum_i (w_i / 2) [i Q V_m + D U_m] / L,   div_n^m = r_n sum_i (w_i / 2) [i Q U_m - D V_m] / L.
+The factor 1 / radius lives in the responses (uv_from_vrtdiv, vrtdiv_from_uv, gradient put it there).  The largest truncation of
+the scalar transform serves the vector forms too.
+
 Three latitude layouts are recognised (either direction):
     'gauss'            the nodes of numpy.polynomial.legendre.leggauss(nlat); exact for T <= nlat - 1
     'clenshaw-curtis'  equally spaced with both poles; exact while 2 T <= nlat - 1
@@ -152,6 +160,76 @@ def unweighted_table(lat, truncation):
     return p32, p64
 
 
+def _vector_functions(kind, nlat, T):
+    """(D, Q) north to south, float64 (packed rows of T, nlat): D_n^m = dPbar_n^m / dphi and Q_n^m = m Pbar_n^m / cos(phi), with their
+    limits at a pole row (zero but for m = 1, where p_n = Pbar_n^1 / cos(phi) gives Q = p_n and D = -mu p_n)"""
+    mu = _nodes(kind, nlat)[1]
+    cos_lat = np.sqrt(np.maximum(1.0 - mu * mu, 0.0))
+    pole = cos_lat == 0.0
+    inv_cos = 1.0 / np.where(pole, 1.0, cos_lat)
+    P = legendre_functions(mu, T + 1)
+    D, Q = np.zeros((packed_rows(T), nlat)), np.zeros((packed_rows(T), nlat))
+    for m in range(T + 1):
+        r, r1 = packed_row(m, m, T), packed_row(m, m, T + 1)
+        for n in range(m, T + 1):
+            e1 = np.sqrt(((n + 1.0) ** 2 - m * m) / (4.0 * (n + 1.0) ** 2 - 1.0))
+            d = -n * e1 * P[r1 + n + 1 - m]
+            if n > m:
+                d = d + (n + 1.0) * np.sqrt((n * n - m * m) / (4.0 * n * n - 1.0)) * P[r1 + n - 1 - m]
+            D[r + n - m] = d * inv_cos
+            Q[r + n - m] = m * P[r1 + n - m] * inv_cos
+    if pole.any():
+        D[:, pole], Q[:, pole] = 0.0, 0.0
+        if T >= 1:
+            x = mu[pole]
+            p = np.zeros((T + 1, x.size))               # p_n = Pbar_n^1 / cos(phi): the recurrence of legendre_functions, m = 1
+            p[1] = np.sqrt(1.5)
+            if T >= 2:
+                p[2] = np.sqrt(5.0) * x * p[1]
+            for n in range(3, T + 1):
+                A = np.sqrt((4.0 * n * n - 1.0) / (n * n - 1.0))
+                B = np.sqrt(((n - 1.0) ** 2 - 1.0) / (4.0 * (n - 1.0) ** 2 - 1.0))
+                p[n] = A * (x * p[n - 1] - B * p[n - 2])
+            r = packed_row(1, 1, T)
+            Q[r:r + T, pole] = p[1:]
+            D[r:r + T, pole] = -x * p[1:]
+    return D, Q
+
+
+def _vector_table(lat, truncation, which, weighted):
+    kind, flipped = _classify(lat)
+    nlat = np.asarray(getattr(lat, 'values', lat)).size
+    T = int(truncation)
+    if T < 0 or T > (nlat - 1 if kind == 'gauss' else (nlat - 1) // 2):
+        raise ValueError("%s_table: truncation %d is outside what %d '%s' latitudes integrate exactly (0 .. %d)"
+                         % (('derivative', 'zonal')[which], T, nlat, kind, nlat - 1 if kind == 'gauss' else (nlat - 1) // 2))
+    t64 = _vector_functions(kind, nlat, T)[which]
+    if weighted:
+        t64 = t64 * (0.5 * _weights(kind, nlat))[None, :]
+    if flipped:
+        t64 = np.ascontiguousarray(t64[:, ::-1])
+    t32 = np.zeros((t64.shape[0], (nlat + 3) // 4 * 4), dtype=np.float32)
+    t32[:, :nlat] = t64
+    return t32, t64
+
+
+def derivative_table(lat, truncation, weighted=False):
+    """(float32 packed table (rows, nlat padded with zeros to a multiple of 4), its float64 parent (rows, nlat)):
+    D_n^m(mu_i) = dPbar_n^m / dphi = [-n eps_{n+1}^m Pbar_{n+1}^m + (n + 1) eps_n^m Pbar_{n-1}^m] / cos(phi_i),
+    eps_n^m = sqrt((n^2 - m^2) / (4 n^2 - 1)), in the order of `lat` and the packing of legendre_table; weighted: times w_i / 2.
+    Every entry is evaluated in float64 and rounded once.  At a pole row the entry is the limit: -mu p_n for m = 1 with
+    p_n = Pbar_n^1 / cos(phi), zero otherwise."""
+    return _vector_table(lat, truncation, 0, weighted)
+
+
+def zonal_table(lat, truncation, weighted=False):
+    """as derivative_table, for Q_n^m(mu_i) = m Pbar_n^m(mu_i) / cos(phi_i); at a pole row p_n for m = 1, zero otherwise"""
+    return _vector_table(lat, truncation, 1, weighted)
+
+
+VECTOR_TABLES = ('D', 'Q', 'wD', 'wQ')
+
+
 def truncation_response(T, cutoff):
     """(T + 1,) float64: 1 for the degrees n <= cutoff, 0 above"""
     T, cutoff = int(T), int(cutoff)
@@ -167,6 +245,15 @@ def laplacian_response(T, radius=6371200., inverse=False):
     r = -n * (n + 1.0) / float(radius) ** 2
     if inverse:
         r[1:] = 1.0 / r[1:]
+    return r
+
+
+def uv_response(T, radius=6371200.):
+    """(T + 1,) float64: -radius / (n (n + 1)), 0 at n = 0: vorticity (divergence) to the streamfunction (velocity potential)
+    times 1 / radius, the response of uv_from_vrtdiv"""
+    n = np.arange(int(T) + 1, dtype=np.float64)
+    r = np.zeros(int(T) + 1)
+    r[1:] = -float(radius) / (n[1:] * (n[1:] + 1.0))
     return r
 
 
@@ -196,6 +283,7 @@ class SphericalTransform(object):
         self.table32, self.table64 = legendre_table(self.lat, T)
         self._device = {}
         self._unweighted, self._device_unweighted = None, {}
+        self._vector, self._device_vector = None, {}
 
     def device_tables(self, device):
         """(twiddle table, Legendre table) on `device`, uploaded at the first use there (not inside a graph capture)"""
@@ -230,6 +318,120 @@ class SphericalTransform(object):
             hit = (ops.spectrum_twiddle(self.n_lon, device), torch.from_numpy(self.synthesis_tables()[0]).to(device))
             self._device_unweighted[key] = hit
         return hit
+
+    def vector_tables(self):
+        """dict of the (float32, float64) tables 'D', 'Q' (derivative_table, zonal_table) and 'wD', 'wQ' (their weighted forms), made
+        at the first use"""
+        if self._vector is None:
+            self._vector = {'D': derivative_table(self.lat, self.truncation), 'Q': zonal_table(self.lat, self.truncation),
+                            'wD': derivative_table(self.lat, self.truncation, weighted=True),
+                            'wQ': zonal_table(self.lat, self.truncation, weighted=True)}
+        return self._vector
+
+    def device_vector_tables(self, device):
+        """(twiddle table, D, Q, wD, wQ) on `device`, uploaded at the first use there (not inside a graph capture)"""
+        import torch
+        from .. import ops
+        key = str(torch.device(device))
+        hit = self._device_vector.get(key)
+        if hit is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise ops.nat.NativeError('spherical_vector: first use of this transform inside a graph capture (run it once '
+                                          'eagerly first)')
+            t = self.vector_tables()
+            hit = (ops.spectrum_twiddle(self.n_lon, device),) + tuple(torch.from_numpy(t[k][0]).to(device) for k in VECTOR_TABLES)
+            self._device_vector[key] = hit
+        return hit
+
+    def _response(self, r):
+        T = self.truncation
+        r = np.ones(T + 1) if r is None else np.asarray(r, dtype=np.float64).reshape(-1)
+        if r.shape != (T + 1,):
+            raise ValueError('SphericalTransform: a response of %d factors, truncation %d needs %d' % (r.size, T, T + 1))
+        return r
+
+    def vector_synthesis(self, A=None, B=None, rpsi=None, rchi=None):
+        """(u, v) float64 (..., nlat, n_lon) of the potentials psi_n^m = rpsi_n A_n^m and chi_n^m = rchi_n B_n^m (complex, packed;
+        either may be None, not both):  u = -dpsi/dphi + (1/cos) dchi/dlambda,  v = (1/cos) dpsi/dlambda + dchi/dphi,  per order
+        U_m = sum_n [-D psi + i Q chi],  V_m = sum_n [i Q psi + D chi].  The factor 1 / radius belongs in the responses.
+        Im of order 0 is ignored."""
+        if A is None and B is None:
+            raise ValueError('SphericalTransform: vector_synthesis needs a potential')
+        T, L = self.truncation, self.n_lon
+        pots = []
+        for c, r in ((A, rpsi), (B, rchi)):
+            if c is None:
+                pots.append(None)
+                continue
+            c = np.asarray(c, dtype=np.complex128)
+            if c.shape[-1:] != (packed_rows(T),):
+                raise ValueError('SphericalTransform: %s coefficients per field, truncation %d has %d'
+                                 % (c.shape[-1:], T, packed_rows(T)))
+            pots.append((c, self._response(r)))
+        if pots[0] is not None and pots[1] is not None and pots[0][0].shape != pots[1][0].shape:
+            raise ValueError('SphericalTransform: the two potentials must have one shape')
+        t = self.vector_tables()
+        D, Q = t['D'][1], t['Q'][1]
+        lead = (pots[0] or pots[1])[0].shape[:-1]
+        U = np.zeros(lead + (self.nlat, L // 2 + 1), dtype=np.complex128)
+        V = np.zeros_like(U)
+        for m in range(T + 1):
+            s = packed_row(m, m, T)
+            sl = slice(s, s + T + 1 - m)
+            if pots[0] is not None:
+                a = pots[0][0][..., sl] * pots[0][1][m:]
+                if m == 0:
+                    a = a.real.astype(np.complex128)
+                U[..., m] -= np.einsum('ni,...n->...i', D[sl], a)
+                V[..., m] += 1j * np.einsum('ni,...n->...i', Q[sl], a)
+            if pots[1] is not None:
+                b = pots[1][0][..., sl] * pots[1][1][m:]
+                if m == 0:
+                    b = b.real.astype(np.complex128)
+                U[..., m] += 1j * np.einsum('ni,...n->...i', Q[sl], b)
+                V[..., m] += np.einsum('ni,...n->...i', D[sl], b)
+        return np.fft.irfft(U * L, n=L, axis=-1), np.fft.irfft(V * L, n=L, axis=-1)
+
+    def vector_analysis(self, u, v, response=None, want=('vrt', 'div')):
+        """the coefficients named in `want` ('vrt', 'div'; a tuple in that order) of the float64 fields u, v (..., nlat, n_lon):
+        zeta_n^m = r_n sum_i (w_i / 2) [i Q V_m + D U_m] / L,  delta_n^m = r_n sum_i (w_i / 2) [i Q U_m - D V_m] / L, complex
+        (..., packed rows).  response: T + 1 real factors (None: ones; 1 / radius for vorticity and divergence)."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in ('vrt', 'div') for w in want) or len(set(want)) != len(want):
+            raise ValueError("SphericalTransform: want %s, a non-empty choice of ('vrt', 'div')" % (want,))
+        u, v = np.asarray(u, dtype=np.float64), np.asarray(v, dtype=np.float64)
+        if u.shape != v.shape or u.shape[-2:] != (self.nlat, self.n_lon):
+            raise ValueError('SphericalTransform: fields of %s and %s, the transform is for %s'
+                             % (u.shape, v.shape, (self.nlat, self.n_lon)))
+        T = self.truncation
+        r = self._response(response)
+        t = self.vector_tables()
+        wD, wQ = t['wD'][1], t['wQ'][1]
+        U = np.fft.rfft(u, axis=-1)[..., :T + 1] / self.n_lon
+        V = np.fft.rfft(v, axis=-1)[..., :T + 1] / self.n_lon
+        out = {w: np.empty(u.shape[:-2] + (packed_rows(T),), dtype=np.complex128) for w in want}
+        for m in range(T + 1):
+            s = packed_row(m, m, T)
+            sl = slice(s, s + T + 1 - m)
+            if 'vrt' in out:
+                out['vrt'][..., sl] = r[m:] * (1j * np.einsum('ni,...i->...n', wQ[sl], V[..., m])
+                                               + np.einsum('ni,...i->...n', wD[sl], U[..., m]))
+            if 'div' in out:
+                out['div'][..., sl] = r[m:] * (1j * np.einsum('ni,...i->...n', wQ[sl], U[..., m])
+                                               - np.einsum('ni,...i->...n', wD[sl], V[..., m]))
+        return tuple(out[w] for w in want)
+
+    def uv_from_vrtdiv(self, vrt=None, div=None, radius=6371200.):
+        """(u, v) of the vorticity and divergence coefficients (either may be None): psi = lap^-1 zeta, chi = lap^-1 delta"""
+        return self.vector_synthesis(vrt, div, uv_response(self.truncation, radius), uv_response(self.truncation, radius))
+
+    def vrtdiv_from_uv(self, u, v, radius=6371200., want=('vrt', 'div')):
+        """the vorticity and divergence coefficients of the wind (u, v) on a sphere of `radius` metres"""
+        return self.vector_analysis(u, v, np.full(self.truncation + 1, 1.0 / float(radius)), want)
+
+    def gradient(self, coef, radius=6371200.):
+        """(ds/dlambda / (radius cos), ds/dphi / radius) of the scalar with the coefficients `coef`"""
+        return self.vector_synthesis(None, coef, None, np.full(self.truncation + 1, 1.0 / float(radius)))
 
     def synthesis(self, coef, response=None):
         """x[i, j] = sum_m c_m Re(e^{2 pi i j m / L} sum_n r_n a_n^m Pbar_n^m(mu_i)) of complex coefficients (..., packed rows):

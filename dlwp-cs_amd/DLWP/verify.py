@@ -1313,6 +1313,128 @@ def spherical_laplacian(x, lat=None, lat_axis=-2, lon_axis=-1, truncation=None, 
 
 
 # --------------------------------------------------------------------------------------------------------------------- #
+# Vector spherical harmonics: winds, vorticity and divergence, gradients
+# --------------------------------------------------------------------------------------------------------------------- #
+#
+# Winds from vorticity and divergence, vorticity and divergence from winds, and the gradient of a scalar, on a sphere of `radius`
+# metres (DLWP/remap/spharm.py states the definitions).  numpy inputs run on the host in float64, device tensors through
+# dlwpcs_sht_vector_synthesis / dlwpcs_sht_vector_analysis (float32 / complex64, device tensors come back); neither path falls
+# back to the other.
+
+def _uv_response(T, radius, dev=None):
+    from .remap.spharm import uv_response
+    r = uv_response(T, radius)
+    return r if dev is None else _response_on(r, dev)
+
+
+def _grid_forecast(values, src, tr, name):
+    """a Forecast of grid fields over the dims of the coefficients `src` with 'lat' and 'lon' in place of the coefficient dim"""
+    dims = tuple(src.dims)[:-1] + ('lat', 'lon')
+    coords = {d: np.asarray(getattr(src.coords[d], 'values', src.coords[d])) for d in dims if d in getattr(src, 'coords', {})}
+    coords['lat'] = tr.lat.copy()
+    coords['lon'] = np.arange(tr.n_lon) * 360.0 / tr.n_lon
+    return Forecast(values, dims, coords, name=name)
+
+
+def spherical_uv(vrt, div, lat, n_lon, radius=6371200.):
+    """
+    The wind (u, v) whose vorticity and divergence have the coefficients `vrt` and `div` (leading axes..., (T + 1)(T + 2) / 2), as
+    `spherical_vrtdiv` returns them, on the latitudes `lat` (degrees) and n_lon longitudes: psi = lap^-1 vrt, chi = lap^-1 div,
+    u = -dpsi/dphi / radius + dchi/dlambda / (radius cos), v = dpsi/dlambda / (radius cos) + dchi/dphi / radius.
+
+    :param vrt, div: complex ndarrays, complex64 device tensors or labelled arrays of one shape; either may be None (taken as zero)
+    :return: (u, v), each (leading axes..., nlat, n_lon): float64 numpy for host inputs, float32 device tensors for device inputs,
+        Forecasts with the dims 'lat' and 'lon' in place of the coefficient dim for labelled inputs
+    """
+    if vrt is None and div is None:
+        raise ValueError('spherical_uv: vorticity and divergence are both absent')
+    first = vrt if vrt is not None else div
+    if vrt is not None and div is not None and tuple(vrt.shape) != tuple(div.shape):
+        raise ValueError('spherical_uv: vorticity %s and divergence %s must have one shape' % (tuple(vrt.shape), tuple(div.shape)))
+    if len(first.shape) < 1:
+        raise ValueError('the coefficients need an axis')
+    T = _truncation_of_rows(int(first.shape[-1]))
+    tr = _spherical_transform(lat, n_lon, T)
+    if _on_device(*[c for c in (vrt, div) if c is not None]):
+        import torch
+        from . import ops as dops
+        dev = _device_of(first)
+        with torch.cuda.device(dev):
+            cs = [None if c is None else (_raw(c) if _raw(c).dtype == torch.complex64 else _raw(c).to(torch.complex64)) for c in (vrt, div)]
+            r = _uv_response(T, radius, dev)
+            u, v = dops.spherical_vector_synthesis(cs[0], cs[1], tr, r, r)
+    else:
+        u, v = tr.uv_from_vrtdiv(None if vrt is None else _host(vrt), None if div is None else _host(div), radius)
+    if not hasattr(first, 'dims'):
+        return u, v
+    return _grid_forecast(u, first, tr, 'u'), _grid_forecast(v, first, tr, 'v')
+
+
+def spherical_vrtdiv(u, v, lat=None, lat_axis=-2, lon_axis=-1, truncation=None, radius=6371200.):
+    """
+    The coefficients (vrt, div) of the vorticity and the divergence of the wind (u, v) on a sphere of `radius` metres.
+
+    :param u, v: ndarrays, device tensors or labelled arrays of one shape; grid axes, `lat` and `truncation` as for
+        `spherical_spectrum`
+    :return: (vrt, div), complex (leading axes..., (T + 1)(T + 2) / 2) as `spherical_analysis` returns coefficients.  A field with
+        a NaN or an infinity in u or in v has NaN coefficients in both.
+    """
+    _check_labels(u, v)
+    if tuple(u.shape) != tuple(v.shape):
+        raise ValueError('spherical_vrtdiv: u %s and v %s must have one shape' % (tuple(u.shape), tuple(v.shape)))
+    la, lo, tr = _sht_grid(u, lat, lat_axis, lon_axis, truncation)
+    if _on_device(u, v):
+        import torch
+        from . import ops as dops
+        dev = next(_raw(x).device for x in (u, v) if _is_tensor(_raw(x)) and _raw(x).is_cuda)
+        with torch.cuda.device(dev):
+            r = _response_on(np.full(tr.truncation + 1, 1.0 / float(radius)), dev)
+            vrt, div = dops.spherical_vector_analysis(_dev_operand(u, dev), _dev_operand(v, dev), tr, r, lat_axis=la, lon_axis=lo)
+    else:
+        arrs = [np.moveaxis(np.asarray(_host(x), dtype=np.float64), (la, lo), (-2, -1)) for x in (u, v)]
+        counted = np.isfinite(arrs[0]).all(axis=(-2, -1)) & np.isfinite(arrs[1]).all(axis=(-2, -1))
+        arrs = [np.where(counted[..., None, None], x, 0.0) for x in arrs]
+        vrt, div = tr.vrtdiv_from_uv(arrs[0], arrs[1], radius)
+        vrt[~counted] = complex(np.nan, np.nan)
+        div[~counted] = complex(np.nan, np.nan)
+    dims = _coef_dims(u, la, lo)
+    dims = None if dims is None else dims + ('coefficient',)
+    return _sht_label(vrt, dims, u, 'vorticity'), _sht_label(div, dims, u, 'divergence')
+
+
+def spherical_gradient(x, lat=None, lat_axis=-2, lon_axis=-1, truncation=None, radius=6371200.):
+    """
+    The gradient (dx/dlambda / (radius cos(phi)), dx/dphi / radius) of the scalar `x` on a sphere of `radius` metres: analysis up
+    to `truncation`, then the vector synthesis of the potential chi = x.  Arguments as for `spherical_filter`; the two results
+    have the shape, axis order and labels of `x`.
+    """
+    la, lo, tr = _sht_grid(x, lat, lat_axis, lon_axis, truncation)
+    T = tr.truncation
+    nd = len(x.shape)
+    lead_axes = [i for i in range(nd) if i not in (la, lo)]
+    if _on_device(x):
+        import torch
+        from . import ops as dops
+        dev = _device_of(x)
+        with torch.cuda.device(dev):
+            xt = _dev_operand(x, dev)
+            coef = dops.spherical_analysis(xt, tr, lat_axis=la, lon_axis=lo)
+            order = [i for i in range(nd) if i != lo] + [lo]
+            outs = []
+            for _ in range(2):
+                buf = torch.empty([int(xt.shape[i]) for i in order], dtype=torch.float32, device=dev)
+                outs.append(buf.permute([order.index(i) for i in range(nd)]))
+            r = _response_on(np.full(T + 1, 1.0 / float(radius)), dev)
+            dops.spherical_vector_synthesis(None, coef, tr, None, r, out_u=outs[0].permute(lead_axes + [la, lo]),
+                                            out_v=outs[1].permute(lead_axes + [la, lo]))
+    else:
+        coef, _ = _analysis_host(_host(x), la, lo, tr)
+        outs = [np.moveaxis(g, (-2, -1), (la, lo)) for g in tr.gradient(coef, radius)]
+    dims = tuple(x.dims) if hasattr(x, 'dims') else None
+    return _sht_label(outs[0], dims, x, 'gradient_lon'), _sht_label(outs[1], dims, x, 'gradient_lat')
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
 # Ensembles: probabilistic scores over a member axis
 # --------------------------------------------------------------------------------------------------------------------- #
 #

@@ -26,7 +26,8 @@
 //
 // Analysis and synthesis (dlwpcs_sht_analysis, dlwpcs_sht_synthesis) share this geometry: the coefficient kernel is stage B's
 // product with the coefficients as its output, the inverse pair (sht_ilegendre_kernel, sht_ifourier_kernel) is described where it
-// stands below.
+// stands below.  The vector forms (dlwpcs_sht_vector_synthesis, dlwpcs_sht_vector_analysis) are the same two products with four
+// accumulators against the derivative and zonal tables, and the barotropic model's two streaming kernels close the file.
 #include "mfma_common.h"
 
 namespace dlwpcs {
@@ -583,6 +584,317 @@ __global__ void __launch_bounds__(SH_THREADS) sht_ifourier_kernel(ShGeom G, cons
     }
 }
 
+// ---- vector harmonics (dlwpcs_sht_vector_synthesis, dlwpcs_sht_vector_analysis) ------------------------------------------------
+// Winds from potentials and vorticity / divergence from winds.  D = dPbar_n^m / dphi and Q = m Pbar_n^m / cos(phi) are the caller's
+// fp32 tables in the packing of the Legendre table (unweighted for the synthesis, times w_i / 2 for the analysis):
+//   U_m(i) = sum_n [ -D psi + i Q chi ],   V_m(i) = sum_n [ i Q psi + D chi ],      psi = fl(rpsi_n A_n^m), chi = fl(rchi_n B_n^m)
+//   zeta_n^m = r_n sum_i [ i wQ V_m + wD U_m ] / L,   delta_n^m = r_n sum_i [ i wQ U_m - wD V_m ] / L.
+// The factor i is carried in the B operand: a swap of Re and Im and a negation, both exact.
+//
+// Inverse vector Legendre (sht_vilegendre_kernel): the grid, tile and operand mapping of sht_ilegendre_kernel with four accumulators
+//   U_re += D (-psi_re), Q (-chi_im)    U_im += D (-psi_im), Q (chi_re)    V_re += Q (-psi_im), D (chi_re)    V_im += Q (psi_re), D (chi_im)
+// per pair of degrees, the psi term before the chi term.  An absent potential is compiled out: it costs no MFMA.  Im of order 0
+// enters as zero.  Degrees > T, latitudes >= nlat and fields beyond the last are selected to zero in both operands.  The result
+// goes to gs[u | v][field][m][re | im][nlat_pad]; sht_ifourier_kernel then runs once per component through that output's strides.
+template <bool HAS_A, bool HAS_B>
+__global__ void __launch_bounds__(64) sht_vilegendre_kernel(ShGeom G, const float2 *__restrict__ coef_a, const float2 *__restrict__ coef_b,
+                                                            const float *__restrict__ rpsi, const float *__restrict__ rchi,
+                                                            const float *__restrict__ dtable, const float *__restrict__ qtable,
+                                                            float *__restrict__ gs) {
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int T = G.T, K = T + 1, nlat = G.nlat, nlp = G.nlp;
+    if (bid >= G.n_ft * G.n_lt * K) return;
+    const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
+    const int m = (int)(bid % K);
+    const int lt = (int)((bid / K) % G.n_lt);
+    const int64_t ft = bid / K / G.n_lt;
+    const int iA = lt * SH_TILE + r32;                   // this lane's latitude as the row of the A operand
+    const int64_t fB = ft * SH_TILE + r32;               // this lane's field as the column of the B operand
+    const bool a_ok = iA < nlat, f_ok = fB < G.fields;
+    const int64_t R = (int64_t)K * (K + 1) / 2;
+    const int64_t row0 = (int64_t)m * K - (int64_t)m * (m - 1) / 2;               // row (m, m)
+    const int count = K - m;                             // degrees m .. T
+    const int64_t a_off = row0 * nlp + (a_ok ? iA : 0);
+    const int64_t b_off = (f_ok ? fB : 0) * R + row0;
+
+    f32x16 acc[2][2];                                    // [u | v][re | im]
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int cs = 0; cs < 2; ++cs)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[c][cs][i] = 0.f;
+    for (int k0 = 0; k0 < count; k0 += 2 * SH_KU) {
+        float dv[SH_KU], qv[SH_KU];
+        float2 pv[SH_KU], cv[SH_KU];
+#pragma unroll
+        for (int u = 0; u < SH_KU; ++u) {
+            const int k = k0 + 2 * u + h;
+            const bool on = k < count;
+            dv[u] = 0.f;
+            qv[u] = 0.f;
+            pv[u] = make_float2(0.f, 0.f);
+            cv[u] = make_float2(0.f, 0.f);
+            if (on && a_ok) {
+                dv[u] = dtable[a_off + (int64_t)k * nlp];
+                qv[u] = qtable[a_off + (int64_t)k * nlp];
+            }
+            if (on && f_ok) {
+                if constexpr (HAS_A) {
+                    const float2 c = coef_a[b_off + k];
+                    const float r = rpsi ? rpsi[m + k] : 1.f;
+                    pv[u] = make_float2(r * c.x, m == 0 ? 0.f : r * c.y);
+                }
+                if constexpr (HAS_B) {
+                    const float2 c = coef_b[b_off + k];
+                    const float r = rchi ? rchi[m + k] : 1.f;
+                    cv[u] = make_float2(r * c.x, m == 0 ? 0.f : r * c.y);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < SH_KU; ++u) {
+            if (k0 + 2 * u >= count) break;              // (wave-uniform)
+            if constexpr (HAS_A) {
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(dv[u], -pv[u].x, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(dv[u], -pv[u].y, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(qv[u], -pv[u].y, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(qv[u], pv[u].x, acc[1][1], 0, 0, 0);
+            }
+            if constexpr (HAS_B) {
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(qv[u], -cv[u].y, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(qv[u], cv[u].x, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(dv[u], cv[u].x, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(dv[u], cv[u].y, acc[1][1], 0, 0, 0);
+            }
+        }
+    }
+
+    // the lane holds field fB (the column) and the latitudes 32 lt + 8 q + 4 h + (0 .. 3)
+    if (f_ok) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            float *dst = gs + c * G.op_stride + ((fB * K + m) * 2) * nlp;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = lt * SH_TILE + 8 * q + 4 * h;
+                if (i >= nlat) continue;
+#pragma unroll
+                for (int cs = 0; cs < 2; ++cs) {
+                    float *p = dst + (int64_t)cs * nlp + i;
+                    if (i + 3 < nlat) {
+                        *reinterpret_cast<float4 *>(p) =
+                            make_float4(acc[c][cs][4 * q], acc[c][cs][4 * q + 1], acc[c][cs][4 * q + 2], acc[c][cs][4 * q + 3]);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 3; ++e)
+                            if (i + e < nlat) p[e] = acc[c][cs][4 * q + e];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Vector coefficient stage (sht_vcoef_kernel): the grid, tiles, operand mapping and masks of sht_coef_kernel on the pair-form scratch
+// of stage A (operand 0 = u, operand 1 = v) with the weighted tiles wD and wQ as the A operands.  Per latitude step and accumulator
+//   z_re += wD U_re, wQ (-V_im)    z_im += wD U_im, wQ V_re    d_re += wQ (-U_im), wD (-V_re)    d_im += wQ U_re, wD (-V_im)
+// in that order; an absent output is compiled out.  Rounding contract: the fp32 sum is widened to fp64, divided by L and multiplied
+// by the fp32 response r_n there (NULL: 1), and rounded to fp32 ONCE: coef = fl32(fl64(fl64(sum / L) r_n)), whose error is at most
+// u (1 + 2^-27) of the exact sum r_n / L.  A NULL response gives the bits of a response of ones (x * 1.0 is exact).
+__device__ __forceinline__ float sh_div_l_r(float v, double L, double r) {
+#pragma clang fp contract(off)
+    return (float)(((double)v / L) * r);
+}
+
+template <bool WZ, bool WD>
+__global__ void __launch_bounds__(64) sht_vcoef_kernel(ShGeom G, const float *__restrict__ xs, const int32_t *__restrict__ bad,
+                                                       const float *__restrict__ response, const float *__restrict__ wdtable,
+                                                       const float *__restrict__ wqtable, float2 *__restrict__ vrt,
+                                                       float2 *__restrict__ dvg, int32_t *__restrict__ skipped) {
+    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (bid >= G.n_ft * G.n_nt * G.n_mc) return;
+    const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
+    const int mc = (int)(bid % G.n_mc);
+    const int nt = (int)((bid / G.n_mc) % G.n_nt);
+    const int64_t ft = bid / G.n_mc / G.n_nt;
+    const int T = G.T, K = T + 1, nlat = G.nlat, nlp = G.nlp;
+    const int n0 = nt * SH_TILE;
+    const int m_last = n0 + SH_TILE - 1 < T ? n0 + SH_TILE - 1 : T;
+    const int m_begin = mc * SH_MC;
+    if (m_begin > m_last) return;
+    const int m_end = m_begin + SH_MC - 1 < m_last ? m_begin + SH_MC - 1 : m_last;
+    const int nA = n0 + r32;
+    const int64_t fB = ft * SH_TILE + r32;
+    const bool f_ok = fB < G.fields;
+    const int64_t R = (int64_t)K * (K + 1) / 2;
+
+    int isbad = 0;
+    if (f_ok)
+        for (int i = h; i < nlat; i += 2) isbad |= bad[fB * nlat + i];
+    isbad |= __shfl_xor(isbad, 32, 64);
+
+    const double Ld = (double)G.L;
+    const float nan = __uint_as_float(0x7fc00000u);
+    const int n_steps = (nlp + 2 * SH_KV * 4 - 1) / (2 * SH_KV * 4);
+    for (int m = m_begin; m <= m_end; ++m) {
+        f32x16 acc[2][2];                                // [vrt | div][re | im]
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int cs = 0; cs < 2; ++cs)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[c][cs][i] = 0.f;
+        const bool a_on = nA >= m && nA <= T;
+        const int64_t row = (int64_t)m * K - (int64_t)m * (m - 1) / 2 + (nA - m);
+        const int64_t a_off = (a_on ? row : 0) * nlp;
+        const float *pb = xs + (((f_ok ? fB : 0) * K + m) * 2) * nlp;
+        for (int t = 0; t < n_steps; ++t) {
+            const int i0 = 2 * SH_KV * 4 * t + SH_KV * 4 * h;
+            float4 dv[SH_KV], qv[SH_KV], xv[2][2][SH_KV];    // xv[u | v][re | im]
+#pragma unroll
+            for (int u = 0; u < SH_KV; ++u) {
+                const int iu = i0 + 4 * u;
+                const bool in = iu < nlp;                // (nlp is a multiple of 4: the 16 bytes lie inside the line or outside)
+                dv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                qv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (a_on && in) {
+                    dv[u] = *reinterpret_cast<const float4 *>(wdtable + a_off + iu);
+                    qv[u] = *reinterpret_cast<const float4 *>(wqtable + a_off + iu);
+                }
+#pragma unroll
+                for (int op = 0; op < 2; ++op)
+#pragma unroll
+                    for (int cs = 0; cs < 2; ++cs) {
+                        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                        if (f_ok && in) v = *reinterpret_cast<const float4 *>(pb + op * G.op_stride + (int64_t)cs * nlp + iu);
+                        v.x = iu < nlat ? v.x : 0.f;    // the padding of xs is never written
+                        v.y = iu + 1 < nlat ? v.y : 0.f;
+                        v.z = iu + 2 < nlat ? v.z : 0.f;
+                        v.w = iu + 3 < nlat ? v.w : 0.f;
+                        xv[op][cs][u] = v;
+                    }
+            }
+#pragma unroll
+            for (int u = 0; u < SH_KV; ++u) {
+                if (2 * SH_KV * 4 * t + 4 * u >= nlp) break;        // (wave-uniform: both halves of these MFMAs lie beyond the lines)
+                const float de[4] = {dv[u].x, dv[u].y, dv[u].z, dv[u].w}, qe[4] = {qv[u].x, qv[u].y, qv[u].z, qv[u].w};
+                const float4 ur4 = xv[0][0][u], ui4 = xv[0][1][u], vr4 = xv[1][0][u], vi4 = xv[1][1][u];
+                const float ur[4] = {ur4.x, ur4.y, ur4.z, ur4.w}, ui[4] = {ui4.x, ui4.y, ui4.z, ui4.w};
+                const float vr[4] = {vr4.x, vr4.y, vr4.z, vr4.w}, vi[4] = {vi4.x, vi4.y, vi4.z, vi4.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (WZ) {
+                        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(de[e], ur[e], acc[0][0], 0, 0, 0);
+                        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(de[e], ui[e], acc[0][1], 0, 0, 0);
+                    }
+                    if constexpr (WD) {
+                        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(qe[e], -ui[e], acc[1][0], 0, 0, 0);
+                        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(qe[e], ur[e], acc[1][1], 0, 0, 0);
+                    }
+                    if constexpr (WZ) {
+                        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(qe[e], -vi[e], acc[0][0], 0, 0, 0);
+                        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(qe[e], vr[e], acc[0][1], 0, 0, 0);
+                    }
+                    if constexpr (WD) {
+                        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(de[e], -vr[e], acc[1][0], 0, 0, 0);
+                        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(de[e], -vi[e], acc[1][1], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        if (!f_ok) continue;
+        const int64_t row0 = (int64_t)m * K - (int64_t)m * (m - 1) / 2 - m;       // row (m, n) = row0 + n
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int n = n0 + 8 * (i >> 2) + 4 * h + (i & 3);
+            if (n < m || n > T) continue;
+            const double r = response ? (double)response[n] : 1.0;
+            if constexpr (WZ)
+                vrt[fB * R + row0 + n] = isbad ? make_float2(nan, nan)
+                                               : make_float2(sh_div_l_r(acc[0][0][i], Ld, r), sh_div_l_r(acc[0][1][i], Ld, r));
+            if constexpr (WD)
+                dvg[fB * R + row0 + n] = isbad ? make_float2(nan, nan)
+                                               : make_float2(sh_div_l_r(acc[1][0][i], Ld, r), sh_div_l_r(acc[1][1][i], Ld, r));
+        }
+    }
+    if (skipped && f_ok && nt == 0 && mc == 0 && h == 0) skipped[fB] = isbad ? 1 : 0;
+}
+
+// ---- the barotropic model's streaming kernels (dlwpcs_barotropic_flux, dlwpcs_barotropic_update) -------------------------------
+// flux: (F, G) = ((f_i + zeta) u, (f_i + zeta) v) on dense (fields, nlat, L) fp32 grids, one Coriolis value per latitude.  A thread
+// owns four neighbouring longitudes (VEC: 16-byte accesses, L % 4 == 0 so that they share a latitude) or one element.
+template <bool VEC>
+__global__ void __launch_bounds__(256) barotropic_flux_kernel(int64_t n, int32_t nlat, int32_t L, const float *__restrict__ coriolis,
+                                                              const float *__restrict__ zeta, const float *__restrict__ u,
+                                                              const float *__restrict__ v, float *__restrict__ F, float *__restrict__ Gv) {
+#pragma clang fp contract(off)
+    const int64_t t = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+    const int64_t e = VEC ? 4 * t : t;
+    if (e >= n) return;
+    const float f = coriolis[(e / L) % nlat];
+    if constexpr (VEC) {
+        const float4 z = *reinterpret_cast<const float4 *>(zeta + e), a = *reinterpret_cast<const float4 *>(u + e),
+                     b = *reinterpret_cast<const float4 *>(v + e);
+        const float4 s = make_float4(f + z.x, f + z.y, f + z.z, f + z.w);
+        *reinterpret_cast<float4 *>(F + e) = make_float4(s.x * a.x, s.y * a.y, s.z * a.z, s.w * a.w);
+        *reinterpret_cast<float4 *>(Gv + e) = make_float4(s.x * b.x, s.y * b.y, s.z * b.z, s.w * b.w);
+    } else {
+        const float s = f + zeta[e];
+        F[e] = s * u[e];
+        Gv[e] = s * v[e];
+    }
+}
+
+// update: one leapfrog step with implicit damping and the Robert filter on (fields, rows) complex fp32, in place:
+//   t = (tend - d zeta_prev) / (1 + d dt),  d = damp[row]
+//   first step:  new = zeta + dt t,  zeta' = zeta + rc (new - zeta)
+//   afterwards:  z1 = zeta + rc (zeta_prev - 2 zeta),  new = zeta_prev + 2 dt t,  zeta' = z1 + rc new
+//   zeta_prev <- zeta',  zeta <- new.
+// Every operation is one fp32 rounding in the order written (no contraction); Re and Im alike.
+__device__ __forceinline__ void baro_update1(float tend, float &z, float &zp, float d, float dt, float rc, bool first) {
+#pragma clang fp contract(off)
+    const float t = (tend - d * zp) / (1.f + d * dt);
+    float nw, zf;
+    if (first) {
+        nw = z + dt * t;
+        zf = z + rc * (nw - z);
+    } else {
+        const float z1 = z + rc * (zp - 2.f * z);
+        nw = zp + (2.f * dt) * t;
+        zf = z1 + rc * nw;
+    }
+    zp = zf;
+    z = nw;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) barotropic_update_kernel(int64_t n, int64_t rows, const float *__restrict__ damp, float dt, float rc,
+                                                                int first, const float *__restrict__ tend, float *__restrict__ zeta,
+                                                                float *__restrict__ zeta_prev) {
+    const int64_t t = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;     // n floats = 2 * fields * rows
+    const int64_t e = VEC ? 4 * t : 2 * t;
+    if (e >= n) return;
+    if constexpr (VEC) {
+        const float d0 = damp[(e / 2) % rows], d1 = damp[(e / 2 + 1) % rows];
+        const float4 tn = *reinterpret_cast<const float4 *>(tend + e);
+        float4 z = *reinterpret_cast<const float4 *>(zeta + e), zp = *reinterpret_cast<const float4 *>(zeta_prev + e);
+        baro_update1(tn.x, z.x, zp.x, d0, dt, rc, first != 0);
+        baro_update1(tn.y, z.y, zp.y, d0, dt, rc, first != 0);
+        baro_update1(tn.z, z.z, zp.z, d1, dt, rc, first != 0);
+        baro_update1(tn.w, z.w, zp.w, d1, dt, rc, first != 0);
+        *reinterpret_cast<float4 *>(zeta + e) = z;
+        *reinterpret_cast<float4 *>(zeta_prev + e) = zp;
+    } else {
+        const float d = damp[(e / 2) % rows];
+        float zr = zeta[e], zi = zeta[e + 1], pr = zeta_prev[e], pi = zeta_prev[e + 1];
+        baro_update1(tend[e], zr, pr, d, dt, rc, first != 0);
+        baro_update1(tend[e + 1], zi, pi, d, dt, rc, first != 0);
+        zeta[e] = zr; zeta[e + 1] = zi;
+        zeta_prev[e] = pr; zeta_prev[e + 1] = pi;
+    }
+}
+
 namespace {
 
 struct ShPlan {
@@ -786,4 +1098,140 @@ extern "C" int dlwpcs_sht_synthesis(const dlwpcs_sht_synthesis_desc *d, const fl
     if (vec) hipLaunchKernelGGL((sht_ifourier_kernel<true>), grid_f, dim3(SH_THREADS), 0, s, G, (const float *)gs, tw, out);
     else hipLaunchKernelGGL((sht_ifourier_kernel<false>), grid_f, dim3(SH_THREADS), 0, s, G, (const float *)gs, tw, out);
     return check_launch("sht_synthesis");
+}
+
+// gs for u and for v: the pair form's scratch without the row flags
+extern "C" size_t dlwpcs_sht_vector_synthesis_scratch_bytes(const dlwpcs_sht_spectrum_desc *d) {
+    ShPlan P;
+    if (sh_plan(d, true, P, "sht_vector_synthesis") != DLWPCS_OK) return 0;
+    return P.xs_bytes;
+}
+
+extern "C" int dlwpcs_sht_vector_synthesis(const dlwpcs_sht_spectrum_desc *d, const float *coef_a, const float *coef_b, const float *rpsi,
+                                           const float *rchi, const float *twiddle, const float *dtable, const float *qtable,
+                                           void *scratch, float *out_u, float *out_v, dlwpcs_stream_t stream) {
+    const char *who = "sht_vector_synthesis";
+    ShPlan P;
+    const int rc = sh_plan(d, true, P, who);
+    if (rc != DLWPCS_OK) return rc;
+    const ShGeom &G = P.G;
+    if (G.n_ft * G.n_lt * (G.T + 1) > SH_MAX_GRID || G.n_rt * G.n_jt > SH_MAX_GRID)
+        return fail(DLWPCS_E_UNSUPPORTED, "%s: too many workgroups", who);
+    if (!twiddle || !dtable || !qtable) return fail(DLWPCS_E_INVALID, "%s: null twiddle, derivative or zonal table", who);
+    if (((uintptr_t)twiddle) & 7) return fail(DLWPCS_E_INVALID, "%s: the twiddle table is not aligned to 8 bytes", who);
+    if ((((uintptr_t)dtable) | ((uintptr_t)qtable)) & 15) return fail(DLWPCS_E_INVALID, "%s: a table is not aligned to 16 bytes", who);
+    if (!coef_a && !coef_b) return fail(DLWPCS_E_INVALID, "%s: both potentials are absent", who);
+    if (G.fields == 0) return DLWPCS_OK;
+    if (!out_u || !out_v) return fail(DLWPCS_E_INVALID, "%s: null output", who);
+    if ((((uintptr_t)out_u) | ((uintptr_t)out_v) | ((uintptr_t)rpsi) | ((uintptr_t)rchi)) & 3)
+        return fail(DLWPCS_E_INVALID, "%s: an operand is not aligned to its 4-byte elements", who);
+    if ((((uintptr_t)coef_a) | ((uintptr_t)coef_b)) & 7)
+        return fail(DLWPCS_E_INVALID, "%s: the coefficients are not aligned to their 8-byte pairs", who);
+    if (!scratch || (((uintptr_t)scratch) & 15))
+        return fail(DLWPCS_E_INVALID, "%s: this descriptor needs a 16-byte aligned scratch of %zu bytes", who, P.xs_bytes);
+    float *gs = (float *)scratch;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid_l = sh_grid(G.n_ft * G.n_lt * (G.T + 1)), grid_f = sh_grid(G.n_rt * G.n_jt);
+    const float2 *tw = (const float2 *)twiddle, *ca = (const float2 *)coef_a, *cb = (const float2 *)coef_b;
+    if (ca && cb) hipLaunchKernelGGL((sht_vilegendre_kernel<true, true>), grid_l, dim3(64), 0, s, G, ca, cb, rpsi, rchi, dtable, qtable, gs);
+    else if (ca) hipLaunchKernelGGL((sht_vilegendre_kernel<true, false>), grid_l, dim3(64), 0, s, G, ca, cb, rpsi, rchi, dtable, qtable, gs);
+    else hipLaunchKernelGGL((sht_vilegendre_kernel<false, true>), grid_l, dim3(64), 0, s, G, ca, cb, rpsi, rchi, dtable, qtable, gs);
+    for (int c = 0; c < 2; ++c) {
+        ShGeom Gc = G;                                  // the inverse Fourier stage reads operand 0's strides
+        Gc.lat_stride[0] = G.lat_stride[c];
+        for (int i = 0; i < G.n_dims; ++i) Gc.stride[0][i] = G.stride[c][i];
+        float *out = c == 0 ? out_u : out_v;
+        const float *gc = gs + c * G.op_stride;
+        bool vec = G.L % 4 == 0 && Gc.lat_stride[0] % 4 == 0 && !(((uintptr_t)out) & 15);
+        for (int i = 0; i < G.n_dims; ++i) vec = vec && Gc.stride[0][i] % 4 == 0;
+        if (vec) hipLaunchKernelGGL((sht_ifourier_kernel<true>), grid_f, dim3(SH_THREADS), 0, s, Gc, gc, tw, out);
+        else hipLaunchKernelGGL((sht_ifourier_kernel<false>), grid_f, dim3(SH_THREADS), 0, s, Gc, gc, tw, out);
+    }
+    return check_launch(who);
+}
+
+extern "C" size_t dlwpcs_sht_vector_analysis_scratch_bytes(const dlwpcs_sht_spectrum_desc *d) {
+    ShPlan P;
+    if (sh_plan(d, true, P, "sht_vector_analysis") != DLWPCS_OK) return 0;
+    return P.xs_bytes + P.bad_bytes;
+}
+
+extern "C" int dlwpcs_sht_vector_analysis(const dlwpcs_sht_spectrum_desc *d, const float *u, const float *v, const float *response,
+                                          const float *twiddle, const float *wdtable, const float *wqtable, void *scratch, float *vrt,
+                                          float *div, int32_t *skipped, dlwpcs_stream_t stream) {
+    const char *who = "sht_vector_analysis";
+    ShPlan P;
+    const int rc = sh_plan(d, true, P, who);
+    if (rc != DLWPCS_OK) return rc;
+    const ShGeom &G = P.G;
+    if (G.n_ft * G.n_nt * G.n_mc > SH_MAX_GRID) return fail(DLWPCS_E_UNSUPPORTED, "%s: too many workgroups", who);
+    if (!twiddle || !wdtable || !wqtable) return fail(DLWPCS_E_INVALID, "%s: null twiddle, derivative or zonal table", who);
+    if (((uintptr_t)twiddle) & 7) return fail(DLWPCS_E_INVALID, "%s: the twiddle table is not aligned to 8 bytes", who);
+    if ((((uintptr_t)wdtable) | ((uintptr_t)wqtable)) & 15) return fail(DLWPCS_E_INVALID, "%s: a table is not aligned to 16 bytes", who);
+    if (!vrt && !div) return fail(DLWPCS_E_INVALID, "%s: both outputs are absent", who);
+    if (G.fields == 0) return DLWPCS_OK;
+    if (!u || !v) return fail(DLWPCS_E_INVALID, "%s: null wind component", who);
+    if ((((uintptr_t)u) | ((uintptr_t)v) | ((uintptr_t)response) | ((uintptr_t)skipped)) & 3)
+        return fail(DLWPCS_E_INVALID, "%s: an operand is not aligned to its 4-byte elements", who);
+    if ((((uintptr_t)vrt) | ((uintptr_t)div)) & 7)
+        return fail(DLWPCS_E_INVALID, "%s: the coefficients are not aligned to their 8-byte pairs", who);
+    if (!scratch || (((uintptr_t)scratch) & 15))
+        return fail(DLWPCS_E_INVALID, "%s: this descriptor needs a 16-byte aligned scratch of %zu bytes", who, P.xs_bytes + P.bad_bytes);
+    float *xs = (float *)scratch;
+    int32_t *bad = (int32_t *)((char *)scratch + P.xs_bytes);
+    const bool vec = P.vec_ok && !((((uintptr_t)u) | ((uintptr_t)v)) & 15);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid_a = sh_grid(G.n_rt * G.n_mt), grid_b = sh_grid(G.n_ft * G.n_nt * G.n_mc);
+    const float2 *tw = (const float2 *)twiddle;
+    if (vec) hipLaunchKernelGGL((sht_fourier_kernel<true, true>), grid_a, dim3(SH_THREADS), 0, s, G, u, v, tw, xs, bad);
+    else hipLaunchKernelGGL((sht_fourier_kernel<true, false>), grid_a, dim3(SH_THREADS), 0, s, G, u, v, tw, xs, bad);
+    float2 *z = (float2 *)vrt, *dv = (float2 *)div;
+    const int32_t *cbad = bad;
+    const float *cxs = xs;
+    if (z && dv) hipLaunchKernelGGL((sht_vcoef_kernel<true, true>), grid_b, dim3(64), 0, s, G, cxs, cbad, response, wdtable, wqtable, z, dv, skipped);
+    else if (z) hipLaunchKernelGGL((sht_vcoef_kernel<true, false>), grid_b, dim3(64), 0, s, G, cxs, cbad, response, wdtable, wqtable, z, dv, skipped);
+    else hipLaunchKernelGGL((sht_vcoef_kernel<false, true>), grid_b, dim3(64), 0, s, G, cxs, cbad, response, wdtable, wqtable, z, dv, skipped);
+    return check_launch(who);
+}
+
+extern "C" int dlwpcs_barotropic_flux(int64_t fields, int32_t nlat, int32_t L, const float *coriolis, const float *zeta, const float *u,
+                                      const float *v, float *F, float *G, dlwpcs_stream_t stream) {
+    if (fields < 0 || nlat < 1 || L < 1) return fail(DLWPCS_E_INVALID, "barotropic_flux: fields = %lld, nlat = %d, L = %d", (long long)fields, nlat, L);
+    if (fields >= (1ll << 31) / nlat) return fail(DLWPCS_E_UNSUPPORTED, "barotropic_flux: too many fields");     // (n below fits int64)
+    if (fields == 0) return DLWPCS_OK;
+    if (!coriolis || !zeta || !u || !v || !F || !G) return fail(DLWPCS_E_INVALID, "barotropic_flux: null operand");
+    const uintptr_t all = ((uintptr_t)coriolis) | ((uintptr_t)zeta) | ((uintptr_t)u) | ((uintptr_t)v) | ((uintptr_t)F) | ((uintptr_t)G);
+    if (all & 3) return fail(DLWPCS_E_INVALID, "barotropic_flux: an operand is not aligned to its 4-byte elements");
+    const int64_t n = fields * nlat * L;
+    const bool vec = L % 4 == 0 && !((((uintptr_t)zeta) | ((uintptr_t)u) | ((uintptr_t)v) | ((uintptr_t)F) | ((uintptr_t)G)) & 15);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t threads = vec ? n / 4 : n;
+    if ((threads + 255) / 256 > SH_MAX_GRID) return fail(DLWPCS_E_UNSUPPORTED, "barotropic_flux: too many workgroups");
+    const dim3 grid = sh_grid((threads + 255) / 256);
+    if (vec) hipLaunchKernelGGL((barotropic_flux_kernel<true>), grid, dim3(256), 0, s, n, nlat, L, coriolis, zeta, u, v, F, G);
+    else hipLaunchKernelGGL((barotropic_flux_kernel<false>), grid, dim3(256), 0, s, n, nlat, L, coriolis, zeta, u, v, F, G);
+    return check_launch("barotropic_flux");
+}
+
+extern "C" int dlwpcs_barotropic_update(int64_t fields, int64_t rows, const float *damp, float dt, float robert, int32_t first_step,
+                                        const float *tend, float *zeta, float *zeta_prev, dlwpcs_stream_t stream) {
+    if (fields < 0 || rows < 1) return fail(DLWPCS_E_INVALID, "barotropic_update: fields = %lld, rows = %lld", (long long)fields, (long long)rows);
+    if (rows >= (1ll << 31) || fields >= (1ll << 31)) return fail(DLWPCS_E_UNSUPPORTED, "barotropic_update: too many coefficients");
+    if (!(dt == dt) || !(robert == robert)) return fail(DLWPCS_E_INVALID, "barotropic_update: dt or the Robert coefficient is NaN");
+    if (fields == 0) return DLWPCS_OK;
+    if (!damp || !tend || !zeta || !zeta_prev) return fail(DLWPCS_E_INVALID, "barotropic_update: null operand");
+    if (zeta == zeta_prev) return fail(DLWPCS_E_INVALID, "barotropic_update: zeta and zeta_prev are one buffer");
+    if (tend == zeta || tend == zeta_prev) return fail(DLWPCS_E_INVALID, "barotropic_update: tend and a state are one buffer");
+    if (((uintptr_t)damp) & 3) return fail(DLWPCS_E_INVALID, "barotropic_update: the damping table is not aligned to its 4-byte elements");
+    const uintptr_t all = ((uintptr_t)tend) | ((uintptr_t)zeta) | ((uintptr_t)zeta_prev);
+    if (all & 7) return fail(DLWPCS_E_INVALID, "barotropic_update: the coefficients are not aligned to their 8-byte pairs");
+    const int64_t n = 2 * fields * rows;
+    const bool vec = n % 4 == 0 && !(all & 15);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t threads = vec ? n / 4 : n / 2;                       // (n < 2^63: both factors are below 2^31)
+    if ((threads + 255) / 256 > SH_MAX_GRID) return fail(DLWPCS_E_UNSUPPORTED, "barotropic_update: too many workgroups");
+    const dim3 grid = sh_grid((threads + 255) / 256);
+    if (vec) hipLaunchKernelGGL((barotropic_update_kernel<true>), grid, dim3(256), 0, s, n, rows, damp, dt, robert, (int)first_step, tend, zeta, zeta_prev);
+    else hipLaunchKernelGGL((barotropic_update_kernel<false>), grid, dim3(256), 0, s, n, rows, damp, dt, robert, (int)first_step, tend, zeta, zeta_prev);
+    return check_launch("barotropic_update");
 }

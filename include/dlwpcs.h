@@ -834,6 +834,72 @@ int dlwpcs_sht_synthesis(const dlwpcs_sht_synthesis_desc *d, const float *coef, 
                          const float *twiddle, const float *legendre, void *scratch, float *out, dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Vector spherical harmonics (DLWP/verify.py spherical_uv, spherical_vrtdiv, spherical_gradient; DLWP/barotropic), with the
+ * definitions, packing, twiddle table and limits of dlwpcs_sht_spectrum above.  With phi the latitude and
+ * eps_n^m = sqrt((n^2 - m^2) / (4 n^2 - 1)) the caller supplies two more fp32 tables in the packing, padding and alignment of the
+ * Legendre table, each entry evaluated in fp64 and rounded once (DLWP/remap/spharm.py derivative_table, zonal_table):
+ *   D_n^m(mu_i) = dPbar_n^m / dphi = [ -n eps_{n+1}^m Pbar_{n+1}^m + (n + 1) eps_n^m Pbar_{n-1}^m ] / cos(phi_i)
+ *   Q_n^m(mu_i) = m Pbar_n^m / cos(phi_i);      at a pole row both are their limits (zero but for m = 1).
+ * The descriptor is dlwpcs_sht_spectrum_desc with operand 0 = u and operand 1 = v (each its own leading and latitude strides,
+ * longitude at unit stride).  Coefficients are fp32 {re, im} pairs, dense, (T + 1)(T + 2) / 2 rows per field, 8-byte aligned.
+ *
+ * dlwpcs_sht_vector_synthesis: with psi_n^m = fl(rpsi_n A_n^m), chi_n^m = fl(rchi_n B_n^m) (coef_a = A, coef_b = B; rpsi, rchi:
+ *   T + 1 floats or NULL = ones with the same bits; Im of order 0 enters as zero),
+ *     u = -dpsi/dphi + (1/cos) dchi/dlambda,  v = (1/cos) dpsi/dlambda + dchi/dphi:
+ *     U_m(i) = sum_n [ -D psi + i Q chi ],   V_m(i) = sum_n [ i Q psi + D chi ],   then the inverse Fourier stage of the synthesis.
+ *   The factor 1 / radius belongs in the responses.  dtable, qtable: the UNWEIGHTED D and Q.  Either potential may be NULL and
+ *   then costs no matrix instruction; both NULL is refused.  Three launches: the inverse vector Legendre stage -- the grid and
+ *   tile of the scalar one, four accumulators, the factor i carried as the exact swap and negation of the B operand, per pair of
+ *   degrees the psi term before the chi term -- into scratch as gs[u | v][field][m][re | im][nlat_pad], then the scalar
+ *   synthesis' inverse Fourier kernel once per component through that output's strides.  Masked degrees, latitudes, longitudes
+ *   and fields are selected to zero in both operands.  scratch >= dlwpcs_sht_vector_synthesis_scratch_bytes(d), 16-byte aligned.
+ *
+ * dlwpcs_sht_vector_analysis: with X_m stage A of dlwpcs_sht_spectrum in its pair form (U_m, V_m),
+ *     vrt_n^m = r_n sum_i [ i wQ V_m + wD U_m ] / L,     div_n^m = r_n sum_i [ i wQ U_m - wD V_m ] / L,
+ *   wdtable, wqtable the WEIGHTED tables (w_i / 2) D and (w_i / 2) Q; response: T + 1 floats r_n (1 / radius for vorticity and
+ *   divergence) or NULL = ones with the same bits.  Either output may be NULL and its matrix work is skipped; both NULL is
+ *   refused.  Two launches: stage A, then the coefficient stage with the grid, tiles and masks of dlwpcs_sht_analysis and up to
+ *   four accumulators; per latitude the wD term before the wQ term in vrt, the wQ term before the wD term in div.  Rounding: the
+ *   fp32 sum over the latitudes is widened to fp64, divided by L and multiplied by r_n there, and rounded to fp32 once.  A field
+ *   with a NaN or an infinity in u or in v gets all-NaN coefficients in both outputs and a 1 in skipped (may be NULL; 0 for every
+ *   other field).  scratch >= dlwpcs_sht_vector_analysis_scratch_bytes(d), 16-byte aligned.
+ * Both: no atomics, a fixed summation order (bitwise repeatable), no host synchronisation, no allocation; a field's result
+ * depends on its own data only; zero fields is success without a launch.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t dlwpcs_sht_vector_synthesis_scratch_bytes(const dlwpcs_sht_spectrum_desc *d);
+int dlwpcs_sht_vector_synthesis(const dlwpcs_sht_spectrum_desc *d, const float *coef_a /* may be NULL */,
+                                const float *coef_b /* may be NULL */, const float *rpsi /* NULL: ones */,
+                                const float *rchi /* NULL: ones */, const float *twiddle, const float *dtable, const float *qtable,
+                                void *scratch, float *out_u, float *out_v, dlwpcs_stream_t stream);
+size_t dlwpcs_sht_vector_analysis_scratch_bytes(const dlwpcs_sht_spectrum_desc *d);
+int dlwpcs_sht_vector_analysis(const dlwpcs_sht_spectrum_desc *d, const float *u, const float *v, const float *response /* NULL: ones */,
+                               const float *twiddle, const float *wdtable, const float *wqtable, void *scratch,
+                               float *vrt /* may be NULL */, float *div /* may be NULL */, int32_t *skipped /* may be NULL */,
+                               dlwpcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- *
+ * The barotropic vorticity model's streaming kernels (DLWP/barotropic).  One launch each, on the current stream, no atomics, no
+ * host synchronisation, no allocation; 16-byte accesses where the extents and pointers allow, element accesses of the same values
+ * otherwise; every operation one fp32 rounding in the order written (no contraction).  Zero fields is success without a launch.
+ *
+ * dlwpcs_barotropic_flux: F = (f_i + zeta) u, G = (f_i + zeta) v on dense (fields, nlat, L) fp32 grids; coriolis: nlat floats f_i.
+ *
+ * dlwpcs_barotropic_update: one time step on dense (fields, rows) fp32 {re, im} coefficients, in place, Re and Im alike, with
+ *   d = damp[row] (rows floats, the damping rate of the row's degree):
+ *     t = (tend - d zeta_prev) / (1 + d dt)
+ *     first_step != 0:  new = zeta + dt t,            zeta' = zeta + robert (new - zeta)
+ *     otherwise:        z1 = zeta + robert (zeta_prev - 2 zeta),  new = zeta_prev + (2 dt) t,  zeta' = z1 + robert new
+ *     zeta_prev <- zeta',  zeta <- new.
+ *   tend, zeta and zeta_prev must be three buffers.
+ * Limits: fields * nlat < 2^31 (flux), fields and rows < 2^31 (update), and at most 65536 * 65535 workgroups of 256 threads
+ * (four elements or one coefficient per thread); beyond: DLWPCS_E_UNSUPPORTED, before any launch.
+ * ------------------------------------------------------------------------------------------------------------- */
+int dlwpcs_barotropic_flux(int64_t fields, int32_t nlat, int32_t L, const float *coriolis, const float *zeta, const float *u,
+                           const float *v, float *F, float *G, dlwpcs_stream_t stream);
+int dlwpcs_barotropic_update(int64_t fields, int64_t rows, const float *damp, float dt, float robert, int32_t first_step,
+                             const float *tend, float *zeta, float *zeta_prev, dlwpcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Ensemble scores (DLWP/verify.py ensemble_mean, ensemble_spread, ensemble_crps, ensemble_error, rank_histogram): the member
  * axis of an fp32 ensemble collapsed element by element.  The element dims arrive as n_dims merged dims with an extent and an
  * element stride per operand (0: ens, 1: valid; 0 = broadcast), the members lie member_stride elements apart: a permuted view
