@@ -172,6 +172,18 @@ class EnsembleDesc(ctypes.Structure):
                 ('stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 2)]
 
 
+QUANTILE_MAX_PROBS = 16
+CATEGORY_MAX_M = 1024
+CATEGORY_MAX_Q = 16
+
+
+class CategoryDesc(ctypes.Structure):
+    """struct dlwpcs_category_desc (include/dlwpcs.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ('M', 'Q', 'n_dims', 'fair')] + \
+               [('member_stride', ctypes.c_int64), ('thr_stride', ctypes.c_int64), ('ext', ctypes.c_int64 * SCORE_MAX_DIMS),
+                ('stride', (ctypes.c_int64 * SCORE_MAX_DIMS) * 3), ('ref_prob', ctypes.c_float * CATEGORY_MAX_Q)]
+
+
 AFFINE_MUL_ADD, AFFINE_SUB_DIV = 0, 1
 AFFINE_MAX_CHANNELS = 1024
 
@@ -264,6 +276,9 @@ PROTOTYPES = {
     'dlwpcs_group_mean': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_void_p, c_void_p,
                                   c_void_p, c_size_t, c_void_p]),
     'dlwpcs_rows_gather': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
+    'dlwpcs_group_quantile': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p, c_int, c_void_p,
+                                      ctypes.c_int64, c_void_p, c_void_p]),
+    'dlwpcs_group_quantile_plan_info': (c_int, [c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_void_p]),
     'dlwpcs_sparse_map_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),
@@ -285,6 +300,8 @@ PROTOTYPES = {
     'dlwpcs_barotropic_update': (c_int, [ctypes.c_int64, ctypes.c_int64, c_void_p, c_float, c_float, ctypes.c_int32] + [c_void_p] * 4),
     'dlwpcs_ensemble_stats': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_ensemble_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_ensemble_category': (c_int, [c_void_p] * 10),
+    'dlwpcs_ensemble_category_plan_info': (c_int, [c_void_p] * 5),
     'dlwpcs_overlap_count': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_overlap_fill': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p]),
     'dlwpcs_cube_bilinear': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -2695,6 +2695,167 @@ def ensemble_stats(ens, valid=None, member_axis=0, want=ENSEMBLE_OUTPUTS, fair=F
 
 
 # ------------------------------------------------------------------------------------------------------------------ #
+# Category scores of an ensemble (DLWP/verify.py brier_score and friends), include/dlwpcs.h dlwpcs_ensemble_category
+# ------------------------------------------------------------------------------------------------------------------ #
+
+CATEGORY_MAX_M, CATEGORY_MAX_Q = nat.CATEGORY_MAX_M, nat.CATEGORY_MAX_Q
+CATEGORY_OUTPUTS = ('prob', 'brier', 'rps', 'rps_ref', 'code')
+_CATEGORY_PER_THRESHOLD = ('prob', 'brier', 'code')
+
+
+def category_layout(shape, strides, thr_shape, thr_strides, member_axis=0, threshold_axis=0, valid_shape=None, valid_strides=None):
+    """
+    How dlwpcs_ensemble_category walks an ensemble (as ensemble_layout reads it), its verification and the thresholds:
+    (M, member stride, Q, threshold stride, element shape, order, merged dims [(extent, (ens, valid, thr strides))]).  The
+    thresholds carry the element dims of the ensemble (extents of 1 broadcast) with the threshold axis at `threshold_axis`; a
+    bare (Q,) vector serves every element.
+    """
+    shape = tuple(int(s) for s in shape)
+    strides = tuple(int(s) for s in strides)
+    nd = len(shape)
+    if nd < 1 or not -nd <= int(member_axis) < nd:
+        raise ValueError('ensemble_category: member axis %s out of range of %d axes' % (member_axis, nd))
+    ax = int(member_axis) % nd
+    M = shape[ax]
+    if M < 1:
+        raise ValueError('ensemble_category: %d members (at least 1)' % M)
+    eshape = shape[:ax] + shape[ax + 1:]
+    es = strides[:ax] + strides[ax + 1:]
+    tshape = tuple(int(s) for s in thr_shape)
+    tstr = tuple(int(s) for s in thr_strides)
+    if len(tshape) == 1:
+        Q, qs, ts = tshape[0], tstr[0], (0,) * len(eshape)
+    else:
+        if len(tshape) != len(eshape) + 1 or not -len(tshape) <= int(threshold_axis) < len(tshape):
+            raise ValueError('ensemble_category: the thresholds %s must carry the dims of the ensemble without the member axis '
+                             '%s and a threshold axis' % (tshape, eshape))
+        ta = int(threshold_axis) % len(tshape)
+        Q, qs = tshape[ta], tstr[ta]
+        rest, rstr = tshape[:ta] + tshape[ta + 1:], tstr[:ta] + tstr[ta + 1:]
+        if any(t not in (1, e) for t, e in zip(rest, eshape)):
+            raise ValueError('ensemble_category: the thresholds %s without their threshold axis do not match the element dims '
+                             '%s (extents of 1 broadcast)' % (tshape, eshape))
+        ts = tuple(0 if t == 1 else s for t, s in zip(rest, rstr))
+    if Q < 1:
+        raise ValueError('ensemble_category: %d thresholds (at least 1)' % Q)
+    if valid_shape is None:
+        vs = (0,) * len(eshape)
+    else:
+        vshape = tuple(int(s) for s in valid_shape)
+        if len(vshape) != len(eshape) or any(v not in (1, e) for v, e in zip(vshape, eshape)):
+            raise ValueError('ensemble_category: the verification %s must carry the dims of the ensemble without the member axis '
+                             '%s (extents of 1 broadcast)' % (vshape, eshape))
+        vs = tuple(0 if v == 1 else int(s) for v, s in zip(vshape, valid_strides))
+    order = sorted((i for i in range(len(eshape)) if eshape[i] != 1), key=lambda i: -abs(es[i]))
+    merged = _coalesce(order, eshape, [es, vs, ts])
+    if len(merged) > nat.SCORE_MAX_DIMS:
+        raise NotImplementedError('ensemble_category: more than %d element dims after merging' % nat.SCORE_MAX_DIMS)
+    return M, strides[ax], Q, qs, eshape, order, merged
+
+
+def category_desc(M, member_stride, Q, thr_stride, merged, fair=False, ref_prob=None):
+    """nat.CategoryDesc of M members and Q thresholds over the merged dims of category_layout"""
+    d = nat.CategoryDesc()
+    d.M, d.Q, d.n_dims, d.fair = int(M), int(Q), len(merged), int(bool(fair))
+    d.member_stride, d.thr_stride = int(member_stride), int(thr_stride)
+    for i, (e, s) in enumerate(merged):
+        d.ext[i] = e
+        d.stride[0][i], d.stride[1][i], d.stride[2][i] = s
+    if ref_prob is not None:
+        rp = np.asarray(ref_prob, dtype=np.float32).reshape(-1)
+        if rp.size != Q:
+            raise ValueError('ensemble_category: %d reference probabilities for %d thresholds' % (rp.size, Q))
+        for j in range(min(Q, CATEGORY_MAX_Q)):
+            d.ref_prob[j] = float(rp[j])
+    return d
+
+
+def ensemble_category_plan(shape, strides, thr_shape, thr_strides, member_axis=0, threshold_axis=0, valid_shape=None,
+                           valid_strides=None, ens_ptr=1 << 20, valid_ptr=None, thr_ptr=1 << 22, fair=False):
+    """
+    Which code ensemble_category would run (host only: no device is touched, the addresses are looked at for alignment):
+    dict(q_class = threshold slots of the instantiation, vec = 16-byte loads of the ensemble, valid = -1 absent / 0 element by
+    element / 1 16-byte loads, thr = 0 element by element / 1 16-byte loads / 2 one vector for every element, grid, threads).
+    Raises what ensemble_category would raise: NotImplementedError beyond 1024 members or 16 thresholds.
+    """
+    M, ms, Q, qs, _, _, merged = category_layout(shape, strides, thr_shape, thr_strides, member_axis, threshold_axis, valid_shape,
+                                                 valid_strides)
+    d = category_desc(M, ms, Q, qs, merged, fair)
+    if valid_ptr is None and valid_shape is not None:
+        valid_ptr = 1 << 21
+    info = (ctypes.c_int32 * 8)()
+    check(lib().dlwpcs_ensemble_category_plan_info(ctypes.byref(d), int(ens_ptr), valid_ptr or None, int(thr_ptr), info),
+          'dlwpcs_ensemble_category_plan_info')
+    return dict(q_class=info[0], vec=bool(info[1]), valid=info[2], thr=info[3], grid=(info[4], info[5]), threads=info[6])
+
+
+def ensemble_category(ens, valid, thresholds, member_axis=0, threshold_axis=0, want=None, fair=False, ref_prob=None):
+    """
+    Category scores of the float32 device ensemble `ens` against Q thresholds, element by element, with k_j the members at or
+    below threshold j and o_j = 1{valid <= threshold j}: dict of device tensors, those named in `want` --
+    'prob' (Q, ...) k_j / M;  'brier' (Q, ...) ((k_j - o_j M) / M)^2;  'rps' (...) the sum of the Brier scores over the
+    thresholds (fair=True: minus sum_j k_j (M - k_j) / (M^2 (M - 1)));  'rps_ref' (...) sum_j (ref_prob[j] - o_j)^2, the score
+    of the reference forecast `ref_prob`;  'code' (Q, ...) int32 2 k_j + o_j.  (...) is the shape of `ens` without the member
+    axis.  want=None: every output the operands allow.  `thresholds`: a float32 device tensor with the element dims of `ens`
+    (extents of 1 broadcast) and the threshold axis at `threshold_axis`, or a bare (Q,) vector; `valid` as in ensemble_stats,
+    None when only 'prob' is wanted.  Missing values: NaN / -1 (include/dlwpcs.h).  Views are read through their strides; the
+    results may come back as permuted views.  One launch on the current stream, no host synchronisation.
+    """
+    if want is None:
+        want = ('prob',) if valid is None else tuple(w for w in CATEGORY_OUTPUTS if w != 'rps_ref' or ref_prob is not None)
+    want = tuple(want)
+    if not want or any(w not in CATEGORY_OUTPUTS for w in want):
+        raise ValueError('ensemble_category: want %s, a non-empty choice of %s' % (want, CATEGORY_OUTPUTS))
+    require_device(ens, 'ensemble_category')
+    require_device(thresholds, 'ensemble_category')
+    if ens.dtype != torch.float32 or thresholds.dtype != torch.float32 or thresholds.device != ens.device:
+        raise TypeError('ensemble_category: the ensemble and the thresholds must be float32 tensors on one device')
+    if valid is not None:
+        require_device(valid, 'ensemble_category')
+        if valid.dtype != torch.float32 or valid.device != ens.device:
+            raise TypeError('ensemble_category: the verification must be a float32 tensor on the device of the ensemble')
+    elif want != ('prob',):
+        raise ValueError("ensemble_category: only 'prob' can be had without a verification")
+    if 'rps_ref' in want and ref_prob is None:
+        raise ValueError("ensemble_category: 'rps_ref' needs the reference probabilities ref_prob")
+    M, ms, Q, qs, eshape, order, merged = category_layout(ens.shape, ens.stride(), thresholds.shape, thresholds.stride(),
+                                                          member_axis, threshold_axis,
+                                                          None if valid is None else valid.shape,
+                                                          None if valid is None else valid.stride())
+    if M > CATEGORY_MAX_M:
+        raise NotImplementedError('ensemble_category: %d members, the kernel serves 1 .. %d' % (M, CATEGORY_MAX_M))
+    if Q > CATEGORY_MAX_Q:
+        raise NotImplementedError('ensemble_category: %d thresholds, the kernel serves 1 .. %d' % (Q, CATEGORY_MAX_Q))
+    if fair and M < 2:
+        raise ValueError('ensemble_category: the fair score needs at least 2 members')
+    d = category_desc(M, ms, Q, qs, merged, fair, ref_prob)
+    n = 1
+    for e in eshape:
+        n *= e
+    perm = [order.index(i) for i in sorted(order)]
+    flat, res = {}, {}
+    for name in CATEGORY_OUTPUTS:
+        if name in want:
+            lead = [Q] if name in _CATEGORY_PER_THRESHOLD else []
+            flat[name] = torch.empty(lead + [n], dtype=torch.int32 if name == 'code' else torch.float32, device=ens.device)
+            if n:
+                t = flat[name].view(lead + [eshape[i] for i in order]).permute(list(range(len(lead))) + [len(lead) + q for q in perm])
+                for i, e in enumerate(eshape):
+                    if e == 1:
+                        t = t.unsqueeze(len(lead) + i)
+                res[name] = t
+            else:
+                res[name] = flat[name].view(lead + list(eshape))
+    if n:
+        with torch.cuda.device(ens.device):
+            check(lib().dlwpcs_ensemble_category(ctypes.byref(d), ptr(ens), ptr(valid) or None, ptr(thresholds),
+                                                 ptr(flat.get('prob')) or None, ptr(flat.get('brier')) or None,
+                                                 ptr(flat.get('rps')) or None, ptr(flat.get('rps_ref')) or None,
+                                                 ptr(flat.get('code')) or None, stream_ptr()), 'dlwpcs_ensemble_category')
+    return res
+
+
+# ------------------------------------------------------------------------------------------------------------------ #
 # Climatologies (DLWP/verify.py): grouped mean over rows and indexed row gather, include/dlwpcs.h dlwpcs_rows_desc
 # ------------------------------------------------------------------------------------------------------------------ #
 
@@ -2705,19 +2866,31 @@ def _rows_desc(src, row_axis, out_perm, n_out):
     require_device(src, 'rows')
     if src.dtype != torch.float32:
         raise TypeError('rows: the source must be float32, got %s' % src.dtype)
-    nd = src.dim()
+    d, oshape = rows_layout(src.shape, src.stride(), row_axis, out_perm, n_out)
+    return d, torch.empty(oshape, dtype=torch.float32, device=src.device)
+
+
+def rows_layout(shape, strides, row_axis, out_perm, n_out):
+    """_rows_desc on a shape and element strides alone (host only): (descriptor, shape of the contiguous output)"""
+    shape = tuple(int(s) for s in shape)
+    strides = tuple(int(s) for s in strides)
+    nd = len(shape)
     row_axis = row_axis % nd
     perm = tuple(range(nd)) if out_perm is None else tuple(int(a) % nd for a in out_perm)
     if sorted(perm) != list(range(nd)):
         raise ValueError('rows: out_perm %s is not a permutation of %d dims' % (out_perm, nd))
-    out = torch.empty([n_out if a == row_axis else int(src.shape[a]) for a in perm], dtype=torch.float32, device=src.device)
+    oshape = [n_out if a == row_axis else shape[a] for a in perm]
+    ostride, run = [0] * nd, 1
+    for pos in range(nd - 1, -1, -1):
+        ostride[pos] = run
+        run *= max(oshape[pos], 1)                              # (torch's strides of a contiguous tensor)
     dims, out_row = [], 0
     for pos, a in enumerate(perm):
         if a == row_axis:
-            out_row = int(out.stride(pos))
+            out_row = ostride[pos]
             dims.append(None)                                   # the row axis separates what may merge
-        elif int(src.shape[a]) != 1:
-            cur = (int(src.shape[a]), int(src.stride(a)), int(out.stride(pos)))
+        elif shape[a] != 1:
+            cur = (shape[a], strides[a], ostride[pos])
             if dims and dims[-1] is not None and dims[-1][1] == cur[1] * cur[0] and dims[-1][2] == cur[2] * cur[0]:
                 dims[-1] = (dims[-1][0] * cur[0], cur[1], cur[2])
             else:
@@ -2730,10 +2903,10 @@ def _rows_desc(src, row_axis, out_perm, n_out):
         raise NotImplementedError('rows: more than %d inner dims after merging' % nat.SCORE_MAX_DIMS)
     d = nat.RowsDesc()
     d.n_inner = len(dims)
-    d.src_row_stride, d.out_row_stride = int(src.stride(row_axis)), out_row
+    d.src_row_stride, d.out_row_stride = strides[row_axis], out_row
     for i, (e, ss, os_) in enumerate(dims):
         d.inner_ext[i], d.src_stride[i], d.out_stride[i] = e, ss, os_
-    return d, out
+    return d, oshape
 
 
 def _int32_dev(x, dev):
@@ -2801,6 +2974,68 @@ def rows_gather(src, index, row_axis=0, out_perm=None):
         check(lib().dlwpcs_rows_gather(ctypes.byref(d), src.data_ptr(), idx.data_ptr(), n, out.data_ptr(), stream_ptr()),
               'dlwpcs_rows_gather')
     return out
+
+
+QUANTILE_MAX_PROBS = nat.QUANTILE_MAX_PROBS
+
+
+def _probs(probs, who):
+    p = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+    if not 1 <= p.size <= QUANTILE_MAX_PROBS:
+        raise ValueError('%s: %d probabilities (1 .. %d)' % (who, p.size, QUANTILE_MAX_PROBS))
+    if not np.all((p >= 0.) & (p <= 1.)):
+        raise ValueError('%s: probabilities %s outside [0, 1]' % (who, p[~((p >= 0.) & (p <= 1.))]))
+    return p
+
+
+def group_quantile_plan(shape, strides, n_groups, max_group_rows, n_probs, row_axis=0, out_perm=None):
+    """
+    Which code group_quantile would run for a source of this shape and these element strides (host only, no device is touched):
+    dict(form = 'staged' / 'long', rows, lanes = the class (long: 0 rows, the threads of a workgroup), p_class = probability
+    slots of the instantiation, grid, lds_bytes).  Raises what group_quantile would raise for these counts.
+    """
+    d, _ = rows_layout(shape, strides, row_axis, out_perm, n_groups)
+    info = (ctypes.c_int32 * 8)()
+    check(lib().dlwpcs_group_quantile_plan_info(ctypes.byref(d), 1 << 20, int(n_groups), int(max_group_rows), int(n_probs), info),
+          'dlwpcs_group_quantile_plan_info')
+    return dict(form='long' if info[0] else 'staged', rows=info[1], lanes=info[2], p_class=info[3], grid=(info[4], info[5]),
+                lds_bytes=info[6])
+
+
+def group_quantile(src, group_start, row_index, probs, row_axis=0, out_perm=None, counts=False):
+    """
+    Per-element quantiles over groups of rows of the fp32 device tensor `src` (any strides): group k holds the rows
+    row_index[group_start[k]:group_start[k + 1]] of `row_axis` (numpy int arrays in CSR form, checked here and uploaded), `probs`
+    up to 16 probabilities in [0, 1].  NaN entries are no members; an element with no member left is NaN.  numpy's default
+    ('linear') quantile, interpolated in fp64 and rounded to fp32 once (include/dlwpcs.h states the operations).  The result has
+    a leading dim len(probs), then src's dims in the order `out_perm` (default: unchanged) with the row axis K long, contiguous.
+    counts=True also returns the int32 member counts (one slice).  One launch on the current stream, no host synchronisation.
+    """
+    p = _probs(probs, 'group_quantile')
+    gs = np.asarray(group_start, dtype=np.int64).reshape(-1)
+    ri = np.asarray(row_index, dtype=np.int64).reshape(-1)
+    if gs.size < 1 or gs[0] != 0 or np.any(np.diff(gs) < 0) or gs[-1] != ri.size:
+        raise ValueError('group_quantile: group_start must rise from 0 to len(row_index)')
+    n_rows = int(src.shape[row_axis])
+    if ri.size and (ri.min() < 0 or ri.max() >= n_rows):
+        raise IndexError('group_quantile: row index out of range of the %d source rows' % n_rows)
+    K = gs.size - 1
+    require_device(src, 'group_quantile')
+    if src.dtype != torch.float32:
+        raise TypeError('group_quantile: the source must be float32, got %s' % src.dtype)
+    d, oshape = rows_layout(src.shape, src.stride(), row_axis, out_perm, K)
+    out = torch.empty([p.size] + oshape, dtype=torch.float32, device=src.device)
+    cnt = torch.empty(oshape, dtype=torch.int32, device=src.device) if counts else None
+    if K == 0 or out.numel() == 0:
+        return (out, cnt) if counts else out
+    longest = int(np.diff(gs).max())
+    dev = src.device
+    with torch.cuda.device(dev):
+        gs_d, ri_d = _int32_dev(gs, dev), _int32_dev(ri if ri.size else np.zeros(1), dev)
+        check(lib().dlwpcs_group_quantile(ctypes.byref(d), src.data_ptr(), gs_d.data_ptr(), ri_d.data_ptr(), K, longest,
+                                          p.ctypes.data, p.size, out.data_ptr(), int(out.stride(0)), ptr(cnt), stream_ptr()),
+              'dlwpcs_group_quantile')
+    return (out, cnt) if counts else out
 
 
 # ------------------------------------------------------------------------------------------------------------------ #

@@ -652,6 +652,39 @@ int dlwpcs_rows_gather(const dlwpcs_rows_desc *d, const float *src, const int32_
                        dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Grouped quantiles along the row axis (DLWP/verify.py climatology_quantiles): the row set and the CSR of dlwpcs_group_mean
+ * (strides in elements, lanes along the last inner dim, a trusted CSR; groups may be empty, a row may appear in several groups;
+ * max_group_rows >= the longest group: it chooses the form, and the staged form reads no more rows of a group).  out[q] for probs[q] lies at
+ * q * out_prob_stride elements; below that the layout is dlwpcs_group_mean's output layout.  count (may be NULL): int32, the
+ * layout of one q slice, the members that entered each (group, element).  probs is a HOST array, read during the call.
+ *
+ * Definition (the tests compare bits against it).  The members of a (group, element) are the entries of the group's rows there
+ * that are not NaN, n of them; +-inf are values like any other, -0 enters as +0.  n = 0: the result is the quiet NaN 0x7fc00000
+ * and the count is 0.  Otherwise, with the members sorted x_(0) <= .. <= x_(n-1), in fp64 and with contraction off:
+ *   h = (n - 1) * p;   j = floor(h);   g = h - j;   v = (g == 0) ? x_(j) : x_(j) + g * (x_(j+1) - x_(j))
+ * and v is rounded to fp32 once: numpy's default ('linear') quantile, np.nanquantile.  A v that is NaN (inf - inf between
+ * infinite neighbours) is stored as 0x7fc00000 too.  0 <= probs[q] <= 1 and 1 <= n_probs <= DLWPCS_QUANTILE_MAX_PROBS, anything
+ * else is DLWPCS_E_INVALID.
+ *
+ * One lane owns one (group, element) column and selects by bitwise radix selection on order-preserving 32-bit keys, 32 passes
+ * over the column shared by all n_probs order statistics (classes of 1, 2, 4, 8, 16 probabilities) and one more for x_(j+1):
+ * no sort, exact.  Staged form: the column lies in LDS ([slot][lane]), read from memory once; classes of rows x lanes
+ * 64 x 256, 128 x 128, 256 x 64 (64 KiB) and 640 x 64 (160 KiB), the smallest that holds max_group_rows.  Long form (longer
+ * groups): the same passes read the rows from memory each time, 34 reads of the group.  One launch, no atomics, no allocation,
+ * no host synchronisation (capturable); a zero extent launches nothing; the result does not depend on the grid.
+ *
+ * dlwpcs_group_quantile_plan_info (host only; src is looked at for NULL, never dereferenced): info[0] = form (0 staged, 1 long),
+ * info[1] / info[2] = rows and lanes of the class (long: 0 and the threads of a workgroup), info[3] = the n_probs class,
+ * info[4] / info[5] = the grid, info[6] = LDS bytes of a workgroup, info[7] = 0.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_QUANTILE_MAX_PROBS 16
+int dlwpcs_group_quantile(const dlwpcs_rows_desc *d, const float *src, const int32_t *group_start, const int32_t *row_index,
+                          int n_groups, int64_t max_group_rows, const double *probs /* host */, int n_probs,
+                          float *out, int64_t out_prob_stride, int32_t *count /* may be NULL */, dlwpcs_stream_t stream);
+int dlwpcs_group_quantile_plan_info(const dlwpcs_rows_desc *d, const void *src, int n_groups, int64_t max_group_rows,
+                                    int n_probs, int32_t info[8]);   /* host only, pointers never dereferenced */
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Offline-map remapping (cubed sphere <-> lat-lon, DLWP/remap): one sparse matrix in CSR form applied to a stack of fields,
  *   y[o, r, k] = sum_{j in [row_ptr[r], row_ptr[r+1])} val[j] * x[o, col[j], k]      for r < n_b,
  * the terms of each output added in CSR order with fp32 fma (no atomics, no split rows: bitwise repeatable, and eager and
@@ -941,6 +974,50 @@ typedef struct dlwpcs_ensemble_desc {
 int dlwpcs_ensemble_stats(const dlwpcs_ensemble_desc *d, const float *ens, const float *valid /* may be NULL */,
                           float *out_mean, float *out_spread, float *out_crps, int32_t *out_rank, dlwpcs_stream_t stream);
 int dlwpcs_ensemble_plan_info(const dlwpcs_ensemble_desc *d, const void *ens, const void *valid, int32_t info[8]);
+
+/* ------------------------------------------------------------------------------------------------------------- *
+ * Category scores of an ensemble (DLWP/verify.py ensemble_probability, brier_score, ranked_probability_score,
+ * categorical_error, reliability_counts): per element, with members x_1..x_M, thresholds t_0 <= .. <= t_{Q-1} (their order is
+ * the caller's business, nothing checks it) and verification y,
+ *   k_j = #{i : x_i <= t_j},   o_j = 1{y <= t_j}.
+ * Operands as in dlwpcs_ensemble_stats: merged element dims with a stride in elements per operand (0: ens, 1: valid, 2: thr;
+ * 0 = broadcast), members member_stride apart, thresholds thr_stride apart.  Outputs (each may be NULL) are contiguous in the
+ * row-major order of the element dims, E elements; the per-threshold ones have the threshold as the leading dim:
+ *   prob    (Q, E)  (float)k_j / (float)M
+ *   brier   (Q, E)  e_j * e_j,  e_j = (float)(k_j - o_j M) / (float)M
+ *   rps     (E)     brier_0 + brier_1 + .. added in that order from 0.f; `fair`: minus
+ *                   (float)(sum_j k_j (M - k_j)) / ((float)(M M) * (float)(M - 1))   (needs M >= 2)
+ *   rps_ref (E)     sum_j (ref_prob[j] - (float)o_j)^2 in the same order from 0.f
+ *   code    (Q, E)  int32 2 k_j + o_j: what a reliability diagram is counted from
+ * Every fp32 operation happens once, in that order, with contraction off; the integers are exact (the fair sum stays below 2^24).
+ * Missing values: an element with a NaN or infinite member is NaN / -1 in every output; a NaN or infinite y in brier, rps,
+ * rps_ref and code (prob is still given); a NaN t_j in threshold j's outputs and in rps and rps_ref; +-inf thresholds are
+ * compared as they are.  Without valid only prob may be asked for.  1 <= M <= DLWPCS_CATEGORY_MAX_M and 1 <= Q <=
+ * DLWPCS_CATEGORY_MAX_Q, DLWPCS_E_UNSUPPORTED beyond.  One lane per element, thresholds and counters in registers (classes of
+ * 1, 2, 4, 8, 16 thresholds; unused slots hold +inf and are never stored), one loop over the members that reads ens once.  16-byte
+ * form (four neighbours along the last dim per lane) in the classes up to 8 under the conditions of dlwpcs_ensemble_stats: the
+ * same bits.  One launch, no scratch, no atomics, no allocation, no host synchronisation (capturable); a zero extent launches
+ * nothing.
+ *
+ * dlwpcs_ensemble_category_plan_info (host only; pointers looked at for NULL and alignment): info[0] = the Q class, info[1] = 1:
+ * 16-byte loads of ens, info[2] = how valid is read (-1 absent, 0 element by element, 1 16-byte loads), info[3] = how thr is
+ * read (0 element by element, 1 16-byte loads, 2 one vector for every element), info[4] / info[5] = the grid, info[6] = threads
+ * of a workgroup, info[7] = 0.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_CATEGORY_MAX_M 1024
+#define DLWPCS_CATEGORY_MAX_Q 16
+typedef struct dlwpcs_category_desc {
+    int32_t M, Q, n_dims, fair;
+    int64_t member_stride, thr_stride;                    /* elements: between members of ens, between thresholds of thr */
+    int64_t ext[DLWPCS_SCORE_MAX_DIMS];
+    int64_t stride[3][DLWPCS_SCORE_MAX_DIMS];             /* ens, valid, thr; 0 = broadcast */
+    float ref_prob[DLWPCS_CATEGORY_MAX_Q];                /* climatological P(y <= t_j): the reference forecast of the skill score */
+} dlwpcs_category_desc;
+int dlwpcs_ensemble_category(const dlwpcs_category_desc *d, const float *ens, const float *valid /* may be NULL */,
+                             const float *thr, float *out_prob, float *out_brier, float *out_rps, float *out_rps_ref,
+                             int32_t *out_code, dlwpcs_stream_t stream);
+int dlwpcs_ensemble_category_plan_info(const dlwpcs_category_desc *d, const void *ens, const void *valid, const void *thr,
+                                       int32_t info[8]);
 
 /* ------------------------------------------------------------------------------------------------------------- *
  * Conservative offline maps made on the device (DLWP/remap/overlap.py is the host twin and states the maths): A[r, c], the
