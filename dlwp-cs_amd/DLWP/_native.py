@@ -173,6 +173,7 @@ class EnsembleDesc(ctypes.Structure):
 
 
 QUANTILE_MAX_PROBS = 16
+TIME_FILTER_MAX_TAPS = 4096
 CATEGORY_MAX_M = 1024
 CATEGORY_MAX_Q = 16
 
@@ -279,6 +280,10 @@ PROTOTYPES = {
     'dlwpcs_group_quantile': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p, c_int, c_void_p,
                                       ctypes.c_int64, c_void_p, c_void_p]),
     'dlwpcs_group_quantile_plan_info': (c_int, [c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_void_p]),
+    'dlwpcs_time_filter': (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                   c_int, c_float, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_time_filter_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, ctypes.c_int64, c_int,
+                                             c_int, ctypes.c_int64, c_void_p]),
     'dlwpcs_sparse_map_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),

@@ -2976,6 +2976,94 @@ def rows_gather(src, index, row_axis=0, out_perm=None):
     return out
 
 
+TIME_FILTER_MAX_TAPS = nat.TIME_FILTER_MAX_TAPS
+_FILTER_MODES = {'sum': 0, 'mean': 1}
+_FILTER_FORMS = {None: -1, 'streaming': 0, 'gather': 1}
+
+
+def _filter_args(n_rows, n_taps, step, origin, n_out, mode, form, slab_rows):
+    if mode not in _FILTER_MODES:
+        raise ValueError("time_filter: mode must be 'sum' or 'mean', got %r" % (mode,))
+    if form not in _FILTER_FORMS:
+        raise ValueError("time_filter: form must be None, 'streaming' or 'gather', got %r" % (form,))
+    step, origin = int(step), int(origin)
+    if not 1 <= n_taps <= TIME_FILTER_MAX_TAPS:
+        raise ValueError('time_filter: %d taps (1 .. %d)' % (n_taps, TIME_FILTER_MAX_TAPS))
+    if step < 1:
+        raise ValueError('time_filter: step %d' % step)
+    if not 0 <= origin < n_taps:
+        raise ValueError('time_filter: origin %d outside the %d taps' % (origin, n_taps))
+    if n_out is None:
+        n_out = max(0, (n_rows - n_taps) // step + 1)
+    n_out = int(n_out)
+    if n_out < 0:
+        raise ValueError('time_filter: n_out %d' % n_out)
+    slab = 0 if slab_rows is None else int(slab_rows)
+    if slab < 0 or (slab_rows is not None and slab == 0):
+        raise ValueError('time_filter: slab_rows %r' % (slab_rows,))
+    return step, origin, n_out, _FILTER_MODES[mode], _FILTER_FORMS[form], slab
+
+
+def time_filter_plan(shape, strides, n_taps, row_axis=0, step=1, n_out=None, mode='sum', out_perm=None, form=None, slab_rows=None,
+                     aligned=True):
+    """
+    Which code time_filter would run for a source of this shape and these element strides (host only, no device is touched):
+    dict(form = 'streaming' / 'gather', a_class = accumulators per element (gather: 0), vec = 16-byte chunks, slab_rows = output
+    rows per time slab, grid).  aligned=False: as for pointers that are not on 16 bytes.  Raises what time_filter would raise.
+    """
+    n_rows = int(shape[row_axis])
+    step, _, n_out, m, f, slab = _filter_args(n_rows, int(n_taps), step, 0, n_out, mode, form, slab_rows)
+    d, _ = rows_layout(shape, strides, row_axis, out_perm, n_out)
+    info = (ctypes.c_int32 * 8)()
+    p = (1 << 20) if aligned else (1 << 20) + 4
+    check(lib().dlwpcs_time_filter_plan_info(ctypes.byref(d), p, p, n_rows, int(n_taps), step, n_out, m, f, slab, info),
+          'dlwpcs_time_filter_plan_info')
+    return dict(form='gather' if info[0] else 'streaming', a_class=info[1], vec=bool(info[2]), slab_rows=info[3],
+                grid=(info[4], info[5]), lds_bytes=info[6])
+
+
+def time_filter(src, taps, row_axis=0, step=1, origin=0, n_out=None, mode='sum', min_weight=0., out_perm=None, form=None,
+                slab_rows=None, counts=False):
+    """
+    A finite-impulse-response filter along `row_axis` of the fp32 device tensor `src` (any strides), in fp32 and in tap order
+    (include/dlwpcs.h states the operations): output row j is the sum over k of taps[k] * src[j * step + k - origin].  A row outside
+    the source and a NaN entry are missing.  mode='sum': an output with a missing entry is NaN.  mode='mean': the weighted mean of
+    the entries present, NaN where their weight is below `min_weight` or none is present.  `taps`: a numpy array (checked, uploaded)
+    or an fp32 device tensor (trusted: finite).  n_out: output rows, by default the windows that lie inside the source at origin 0.
+    The result has src's dims in the order `out_perm` (default: unchanged) with the row axis n_out long, contiguous.  form: None =
+    the library chooses, 'streaming' / 'gather' forces it; slab_rows: output rows per time slab (None = chosen): the same bits
+    whatever they are.  counts=True also returns the int32 number of entries present.  One launch on the current stream, no host
+    synchronisation, nothing allocated but the results.
+    """
+    require_device(src, 'time_filter')
+    dev = src.device
+    if isinstance(taps, torch.Tensor):
+        if taps.dtype != torch.float32 or taps.device != dev or taps.dim() != 1 or not taps.is_contiguous():
+            raise TypeError('time_filter: device taps must be a contiguous 1-d float32 tensor on the device of the source')
+        h = taps
+    else:
+        hh = np.asarray(taps, dtype=np.float64).reshape(-1)
+        h32 = np.ascontiguousarray(hh, dtype=np.float32)
+        if not np.all(np.isfinite(h32)):
+            raise ValueError('time_filter: the taps must be finite in float32')
+        if mode == 'mean' and hh.size and not (np.all(h32 >= 0.) and float(h32.sum(dtype=np.float64)) > 0.):
+            raise ValueError("time_filter: mode 'mean' needs taps >= 0 with a positive sum")
+        h = None
+    n_taps = int(h.numel()) if h is not None else int(hh.size)
+    n_rows = int(src.shape[row_axis])
+    step, origin, n_out, m, f, slab = _filter_args(n_rows, n_taps, step, origin, n_out, mode, form, slab_rows)
+    d, out = _rows_desc(src, row_axis, out_perm, n_out)
+    cnt = torch.empty(out.shape, dtype=torch.int32, device=dev) if counts else None
+    if out.numel() == 0:
+        return (out, cnt) if counts else out
+    with torch.cuda.device(dev):
+        if h is None:
+            h = torch.from_numpy(h32).pin_memory().to(dev, non_blocking=True)
+        check(lib().dlwpcs_time_filter(ctypes.byref(d), src.data_ptr(), n_rows, h.data_ptr(), n_taps, step, origin, n_out, m,
+                                       float(min_weight), f, slab, out.data_ptr(), ptr(cnt), stream_ptr()), 'dlwpcs_time_filter')
+    return (out, cnt) if counts else out
+
+
 QUANTILE_MAX_PROBS = nat.QUANTILE_MAX_PROBS
 
 

@@ -2043,3 +2043,234 @@ def reliability_counts(ens, valid, thresholds, axis=None, member_axis=0, thresho
     counts = np.asarray(counts, dtype=np.int64).reshape(kshape + [Q, M + 1, 2])
     tail = [('threshold', np.arange(Q) if tcoord is None else tcoord), ('members_below', np.arange(M + 1)), ('observed', np.arange(2))]
     return _category_label(counts, ens, tail=tail, name='reliability_counts', drop=ax)
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# Filters along time: running means, Lanczos low-pass and band-pass (the reference leaves xarray's rolling().mean() to the user)
+# --------------------------------------------------------------------------------------------------------------------- #
+
+_FILTER_LABELS = ('end', 'centre', 'start')
+
+
+def lanczos_weights(n, cutoff, cutoff_high=None):
+    """
+    The 2 n + 1 taps of a Lanczos low-pass filter with the cut-off frequency `cutoff` in cycles per row (Duchon 1979):
+    w_k = 2 fc sinc(2 fc k) sinc(k / (n + 1)) for k = -n .. n with sinc(x) = sin(pi x) / (pi x), normalised to sum 1.  With
+    `cutoff_high` the band-pass low(cutoff_high) - low(cutoff), which sums to 0: it keeps the periods between 1 / cutoff_high
+    and 1 / cutoff rows (2 to 6 days of 6-hourly data: cutoff = 1 / 24, cutoff_high = 1 / 8).  float64, symmetric to the last
+    bit.  Host only.
+    """
+    n = int(n)
+    if n < 1:
+        raise ValueError('lanczos_weights: n must be at least 1, got %d' % n)
+    for fc in (cutoff,) if cutoff_high is None else (cutoff, cutoff_high):
+        if not 0. < float(fc) <= 0.5:
+            raise ValueError('lanczos_weights: a cut-off of %r cycles per row is outside (0, 0.5]' % (fc,))
+    if cutoff_high is not None and not float(cutoff_high) > float(cutoff):
+        raise ValueError('lanczos_weights: cutoff_high must lie above cutoff')
+
+    def low(fc):
+        k = np.arange(1, n + 1, dtype=np.float64)
+        half = 2. * fc * np.sinc(2. * fc * k) * np.sinc(k / (n + 1.))
+        w = np.concatenate([half[::-1], [2. * fc], half])
+        return w / (2. * fc + 2. * half.sum())
+
+    w = low(float(cutoff))
+    if cutoff_high is None:
+        return w
+    b = low(float(cutoff_high)) - w
+    # the two halves are the same numbers in mirrored order, so the sum below is the only thing left to centre
+    b[n] -= b.sum()
+    return b
+
+
+def _filter_axis(x, axis, name):
+    dims = tuple(getattr(x, 'dims', ()))
+    nd = len(_raw(x).shape)
+    if axis is None:
+        return dims.index(name) if name in dims else 0
+    if isinstance(axis, str):
+        if axis not in dims:
+            raise ValueError("the data has no '%s' dimension (dims: %s)" % (axis, ', '.join(dims)))
+        return dims.index(axis)
+    if not -nd <= int(axis) < nd:
+        raise ValueError('axis %d is out of range of %d dims' % (axis, nd))
+    return int(axis) % nd
+
+
+def _fp32_sum(h32):
+    s = np.float32(0.)
+    for v in h32:
+        s = np.float32(s + v)
+    return s
+
+
+def _time_filter_host(x, h, axis, step, origin, n_out, mean, threshold):
+    """the definition of dlwpcs_time_filter in float64: (values, int32 counts)"""
+    v = np.moveaxis(np.asarray(x, dtype=np.float64), axis, 0)
+    T, K = v.shape[0], len(h)
+    acc = np.zeros((n_out,) + v.shape[1:], dtype=np.float64)
+    w = np.zeros_like(acc)
+    n = np.zeros(acc.shape, dtype=np.int32)
+    j = np.arange(n_out, dtype=np.int64)
+    tail = (slice(None),) + (None,) * (v.ndim - 1)
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        for k in range(K):
+            r = j * step + k - origin
+            inside = (r >= 0) & (r < T)
+            rows = v[np.clip(r, 0, max(T - 1, 0))] if T else np.full(acc.shape, np.nan)
+            present = inside[tail] & ~np.isnan(rows)
+            acc = acc + np.where(present, h[k] * np.where(present, rows, 0.), 0.)
+            w = w + np.where(present, h[k], 0.)
+            n += present
+        if mean:
+            q = acc / w
+            out = np.where((n > 0) & (w >= threshold) & ~np.isnan(q), q, np.nan)
+        else:
+            out = np.where((n == K) & ~np.isnan(acc), acc, np.nan)
+    return np.moveaxis(out, 0, axis), np.moveaxis(n, 0, axis)
+
+
+def _filter_label(x, axis, rows, values, name):
+    """`values` labelled like x, the coordinate of `axis` taken at the source rows `rows`"""
+    if not hasattr(x, 'dims'):
+        return values
+    dims = tuple(x.dims)
+    coords = {}
+    for i, d in enumerate(dims):
+        if d in getattr(x, 'coords', {}):
+            c = _coord(x, d)
+            coords[d] = c[rows] if i == axis else c
+    out = Forecast(values, dims, coords, name=name)
+    if hasattr(x, 'lat'):
+        out.lat = x.lat
+    return out
+
+
+def _time_filter_apply(x, h, axis, step, mode, mean, min_weight, relative, label, return_count, name):
+    if mode not in ('valid', 'same'):
+        raise ValueError("'mode' must be 'valid' or 'same'")
+    if label is None:
+        label = 'end' if mode == 'valid' else 'centre'
+    if label not in _FILTER_LABELS:
+        raise ValueError("'label' must be 'end', 'centre' or 'start'")
+    h = np.asarray(h, dtype=np.float64).reshape(-1)
+    K, step = int(h.size), int(step)
+    if K < 1:
+        raise ValueError('%s: no weights' % name)
+    if step < 1:
+        raise ValueError('%s: step must be at least 1, got %d' % (name, step))
+    if not np.all(np.isfinite(h)):
+        raise ValueError('%s: the weights must be finite' % name)
+    if mean and not (np.all(h >= 0.) and h.sum() > 0.):
+        raise ValueError("%s: skipping missing values needs weights >= 0 with a positive sum" % name)
+    v = _raw(x)
+    T = int(v.shape[axis])
+    if mode == 'valid':
+        origin, J = 0, max(0, (T - K) // step + 1)
+    else:
+        origin, J = (K - 1) // 2, -(-T // step)
+    first = np.arange(J, dtype=np.int64) * step - origin
+    rows = first + {'end': K - 1, 'centre': (K - 1) // 2, 'start': 0}[label]
+    if hasattr(x, 'dims') and J and (rows[0] < 0 or rows[-1] >= T):
+        raise ValueError("%s: label='%s' lies outside the series in mode '%s'" % (name, label, mode))
+    if _is_tensor(v) and v.is_cuda:
+        import torch
+        from . import ops as dops
+        h32 = h.astype(np.float32)
+        thr = np.float32(np.float32(min_weight) * _fp32_sum(h32)) if relative else np.float32(min_weight)
+        with torch.cuda.device(v.device):
+            src = v if v.dtype == torch.float32 else v.to(torch.float32)
+            res = dops.time_filter(src, h, row_axis=axis, step=step, origin=origin, n_out=J, mode='mean' if mean else 'sum',
+                                   min_weight=float(thr), counts=return_count)
+        out, cnt = res if return_count else (res, None)
+    else:
+        tot = 0.
+        for hk in h:
+            tot = tot + hk
+        thr = float(min_weight) * tot if relative else float(min_weight)
+        out, cnt = _time_filter_host(_host(v), h, axis, step, origin, J, mean, thr)
+    out = _filter_label(x, axis, rows, out, name)
+    return (out, _filter_label(x, axis, rows, cnt, name + '_count')) if return_count else out
+
+
+def time_filter(x, weights, axis=None, step=1, mode='valid', missing='propagate', min_weight=0.5, label=None, return_count=False):
+    """
+    Filter a series along time with the weights `weights` (K of them, at most 4096): output j is the sum over k of
+    weights[k] * x[j * step + k - origin].
+
+    :param x: a `Forecast` (or anything with `.dims`, `.coords`, `.values`), a numpy array or a torch tensor.  Values on a HIP
+        device are filtered there (dlwpcs_time_filter: fp32, in tap order, one launch) and the result stays there; numpy values
+        are filtered on the host in float64 by the same rules.
+    :param weights: the taps, host values (e.g. `lanczos_weights`)
+    :param axis: the axis to filter along, a position or a dim name; None: the 'time' dim of a labelled input, else axis 0
+    :param step: keep every step-th output
+    :param mode: 'valid': the windows that lie inside the series, origin 0, max(0, (T - K) // step + 1) outputs.  'same': the
+        window is centred (origin (K - 1) // 2), ceil(T / step) outputs, the windows over the ends have missing entries
+    :param missing: a NaN entry, or one outside the series, is missing.  'propagate': the output is NaN.  'skip': the weighted
+        mean of the entries present (weights >= 0), NaN where their weight is below `min_weight` times the sum of the weights
+    :param label: the time coordinate of an output is that of its window's 'end' (default for 'valid'), 'centre' (default for
+        'same') or 'start'
+    :param return_count: also return the int32 number of entries present in each window
+    :return: labelled like the input (a plain array for a plain input)
+    """
+    if missing not in ('propagate', 'skip'):
+        raise ValueError("'missing' must be 'propagate' or 'skip'")
+    return _time_filter_apply(x, weights, _filter_axis(x, axis, 'time'), step, mode, missing == 'skip', min_weight, True, label, return_count,
+                   'time_filter')
+
+
+def running_mean(x, n, axis=None, step=1, mode='valid', min_count=None, label=None, return_count=False):
+    """
+    The mean over windows of `n` rows along time (`time_filter` with n weights of one): the sum of the entries present, in row
+    order, over their exact count; NaN where fewer than `min_count` are present.  min_count=None: n, every entry present, the
+    default of xarray's rolling().  The weekly mean of 6-hourly data is running_mean(x, 28), every day of it step=4.
+    """
+    n = int(n)
+    if n < 1:
+        raise ValueError('running_mean: a window of %d rows' % n)
+    mc = n if min_count is None else int(min_count)
+    if not 1 <= mc <= n:
+        raise ValueError('running_mean: min_count %d outside 1 .. %d' % (mc, n))
+    return _time_filter_apply(x, np.ones(n), _filter_axis(x, axis, 'time'), step, mode, True, mc, False, label, return_count, 'running_mean')
+
+
+def lead_window_mean(x, windows, axis=None, min_count=None):
+    """
+    Means over unequal windows of the lead axis (week 3, week 4, weeks 5 to 6 of a forecast): window i holds the rows
+    windows[i][0] .. windows[i][1] - 1.  NaN entries are skipped; a window with fewer than `min_count` entries present (None:
+    its length) is NaN.  axis=None: the 'f_hour' dim of a labelled input, else axis 0.  The coordinate of a window is that of
+    its last row.  Device values are reduced there (dlwpcs_group_mean, fp64 sums), numpy values on the host in fp64.
+    """
+    axis = _filter_axis(x, axis, 'f_hour')
+    v = _raw(x)
+    T = int(v.shape[axis])
+    win = np.asarray(windows, dtype=np.int64).reshape(-1, 2)
+    if win.shape[0] < 1 or np.any(win[:, 0] < 0) or np.any(win[:, 1] > T) or np.any(win[:, 1] <= win[:, 0]):
+        raise ValueError('lead_window_mean: windows must be (start, stop) row pairs with 0 <= start < stop <= %d' % T)
+    length = win[:, 1] - win[:, 0]
+    mc = length if min_count is None else np.broadcast_to(np.asarray(min_count, dtype=np.int64), length.shape)
+    if np.any(mc < 1) or np.any(mc > length):
+        raise ValueError('lead_window_mean: min_count outside 1 .. the length of its window')
+    start = np.concatenate([[0], np.cumsum(length)])
+    order = np.concatenate([np.arange(a, b) for a, b in win])
+    shape = [1] * len(v.shape)
+    shape[axis] = len(mc)
+    if _is_tensor(v) and v.is_cuda:
+        import torch
+        from . import ops as dops
+        with torch.cuda.device(v.device):
+            src = v if v.dtype == torch.float32 else v.to(torch.float32)
+            out, cnt = dops.group_mean(src, start, order, row_axis=axis, counts=True)
+            need = torch.from_numpy(np.ascontiguousarray(mc.reshape(shape), dtype=np.int32)).to(v.device)
+            out = torch.where(cnt >= need, out, torch.full_like(out, float('nan')))
+    else:
+        h = np.moveaxis(np.asarray(_host(v), dtype=np.float64), axis, 0)
+        out = np.empty((len(mc),) + h.shape[1:], dtype=np.float32)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            for i, (a, b) in enumerate(win):
+                ok = ~np.isnan(h[a:b])
+                n = ok.sum(axis=0)
+                out[i] = np.where(n >= mc[i], np.where(ok, h[a:b], 0.).sum(axis=0) / np.maximum(n, 1), np.nan)
+        out = np.moveaxis(out, 0, axis)
+    return _filter_label(x, axis, win[:, 1] - 1, out, 'lead_window_mean')

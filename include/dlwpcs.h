@@ -685,6 +685,49 @@ int dlwpcs_group_quantile_plan_info(const dlwpcs_rows_desc *d, const void *src, 
                                     int n_probs, int32_t info[8]);   /* host only, pointers never dereferenced */
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Filters along the row axis (DLWP/verify.py time_filter / running_mean): a finite-impulse-response filter with a decimation
+ * step over the n_rows rows of a row set (dlwpcs_rows_desc: strides in elements, lanes along the last inner dim).  taps is an
+ * fp32 DEVICE array of n_taps finite values, trusted.  Output row j < n_out lies at j * out_row_stride.
+ *
+ * Definition (the tests compare bits against it).  With T = n_rows, K = n_taps, s = step, o = origin, output row j at element e
+ * is, in fp32, every operation rounded once, in this order, no contraction:
+ *     acc = 0.f; w = 0.f; n = 0; bad = false
+ *     for k = 0 .. K-1:                     r = j*s + k - o
+ *         missing = (r < 0 || r >= T) || isnan(x[r, e])
+ *         if missing: bad = true                      (nothing is added, in either mode)
+ *         else:       acc = acc + h[k] * x[r, e];  w = w + h[k];  n = n + 1
+ *     DLWPCS_FILTER_SUM  (0): out = (bad || isnan(acc)) ? QNAN : acc
+ *     DLWPCS_FILTER_MEAN (1): q = acc / w (IEEE division);  out = (n > 0 && w >= min_weight && !isnan(q)) ? q : QNAN
+ * QNAN is 0x7fc00000: every NaN that is stored has these bits.  +-inf are values like any other; 0 * inf and inf - inf end as
+ * QNAN.  count (may be NULL): int32 in the output's layout, n.  1 <= K <= DLWPCS_TIME_FILTER_MAX_TAPS, s >= 1, 0 <= o < K,
+ * n_rows >= 0, n_out >= 0, mode 0 / 1, form -1 / 0 / 1 and slab_rows >= 0; anything else is DLWPCS_E_INVALID.  A zero extent or
+ * n_out = 0 launches nothing.  One launch, no atomics, no host synchronisation, no allocation, no scratch (capturable); the
+ * result does not depend on the grid, the slab length or the form.
+ *
+ * The grid is column tiles of 256 chunks x time slabs of slab_rows output rows (0: the library chooses).  A chunk is four
+ * elements (16-byte loads) where the layout, the pointers and the class allow it, else one.
+ * form 0, streaming: a lane walks the input rows of its slab once, in order, and keeps the A = ceil(K / s) outputs a row
+ * contributes to in registers, in classes of 1, 2, 4, 8, 16, 32 accumulators whose slot is a compile-time index (the row loop
+ * is unrolled over one period of the class); a slab re-reads the K - s rows it shares with its predecessor.  A > 32 is refused.
+ * form 1, gather: a lane computes the outputs of its slab eight at a time from one pass over the rows they read; any K and s.
+ * form -1: streaming where A <= 8, else gather (measured: classes 16 and 32 are slower than the gather form).  Both forms do the
+ * additions above in tap order: the same bits.
+ *
+ * dlwpcs_time_filter_plan_info (host only; src and out are looked at for NULL and for 16-byte alignment, never dereferenced):
+ * info[0] = form, info[1] = the accumulator class (gather: 0), info[2] = 1 for 16-byte chunks, info[3] = output rows per slab,
+ * info[4] / info[5] = the grid, info[6] = LDS bytes of a workgroup (0: the taps come through the scalar cache), info[7] = 0.
+ * Returns what the entry point would return for the same arguments.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_TIME_FILTER_MAX_TAPS 4096
+#define DLWPCS_FILTER_SUM 0
+#define DLWPCS_FILTER_MEAN 1
+int dlwpcs_time_filter(const dlwpcs_rows_desc *d, const float *src, int64_t n_rows, const float *taps /* device */, int n_taps,
+                       int64_t step, int64_t origin, int64_t n_out, int mode, float min_weight, int form, int64_t slab_rows,
+                       float *out, int32_t *count /* may be NULL */, dlwpcs_stream_t stream);
+int dlwpcs_time_filter_plan_info(const dlwpcs_rows_desc *d, const void *src, const void *out, int64_t n_rows, int n_taps,
+                                 int64_t step, int64_t n_out, int mode, int form, int64_t slab_rows, int32_t info[8]);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Offline-map remapping (cubed sphere <-> lat-lon, DLWP/remap): one sparse matrix in CSR form applied to a stack of fields,
  *   y[o, r, k] = sum_{j in [row_ptr[r], row_ptr[r+1])} val[j] * x[o, col[j], k]      for r < n_b,
  * the terms of each output added in CSR order with fp32 fma (no atomics, no split rows: bitwise repeatable, and eager and
