@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .layout import element_layout, member_split, merge_dims
 from .options import option
 from ._native import ConvDesc, GConvDesc, check, lib, ptr, require_device, stream_ptr
 
@@ -1786,18 +1787,6 @@ SCORE_METHODS = {'mse': nat.SCORE_MSE, 'rmse': nat.SCORE_RMSE, 'mae': nat.SCORE_
                  'cos': nat.SCORE_COS, 'mean': nat.SCORE_MEAN}
 
 
-def _coalesce(dims, shape, strides):
-    """[(extent, (stride per operand))] of `dims` in order, adjacent entries merged where every operand allows it."""
-    out = []
-    for i in dims:
-        e, s = int(shape[i]), tuple(int(st[i]) for st in strides)
-        if out and all(ps == cs * e for ps, cs in zip(out[-1][1], s)):
-            out[-1] = (out[-1][0] * e, s)
-        else:
-            out.append((e, s))
-    return out
-
-
 def score_reduce(method, operands, shape, reduced, lagged=None, out_f32=False, indexed=None):
     """
     Reduce fp32 device operands [a (forecast), b (verification), c (climatology), w (weights)] -- each None or
@@ -1866,7 +1855,8 @@ def score_reduce(method, operands, shape, reduced, lagged=None, out_f32=False, i
             d.kc_stride[k] = strides[k][kept[-1]]
         kept = kept[:-1]
     d.kc = kc
-    keep_c, red_c = _coalesce(kept, shape, strides), _coalesce(red, shape, strides)
+    keep_c, red_c = ([(e, s) for e, s, _ in merge_dims((shape[i], [st[i] for st in strides], None) for i in dims)]
+                     for dims in (kept, red))
     if len(keep_c) > nat.SCORE_MAX_DIMS or len(red_c) > nat.SCORE_MAX_DIMS:
         raise NotImplementedError('score: more than %d kept or reduced dims after merging' % nat.SCORE_MAX_DIMS)
     d.n_keep, d.n_red = len(keep_c), len(red_c)
@@ -1926,16 +1916,7 @@ def spectrum_dims(shape, strides, reduced):
     """
     shape = tuple(int(e) for e in shape)
     reduced = set(int(r) % len(shape) for r in reduced) if shape else set()
-    out = []
-    for i, e in enumerate(shape):
-        if e == 1:
-            continue
-        st, kept = tuple(int(s[i]) for s in strides), i not in reduced
-        if out and out[-1][2] == kept and all(ps == cs * e for ps, cs in zip(out[-1][1], st)):
-            out[-1] = (out[-1][0] * e, st, kept)
-        else:
-            out.append((e, st, kept))
-    return out
+    return merge_dims((e, [s[i] for s in strides], i not in reduced) for i, e in enumerate(shape))
 
 
 def spectrum_desc(L, dims, n_wave=None, remove_mean=False):
@@ -2585,33 +2566,10 @@ def ensemble_layout(shape, strides, member_axis=0, valid_shape=None, valid_strid
     and a verification of `valid_shape` / `valid_strides` (the ensemble's dims without the member axis, extents of 1 broadcast):
     (M, member stride, element shape, order, merged dims).  `order` lists the element dims of extent > 1 from the largest stride
     of the ensemble to the smallest, so that the lanes run along the dim that is contiguous in memory whatever view the caller
-    holds; the outputs are laid out in that order and handed back as views of the element shape.  Merged dims as _coalesce makes
-    them: [(extent, (ensemble stride, verification stride))].
+    holds; the outputs are laid out in that order and handed back as views of the element shape.  Merged dims as
+    layout.merge_dims makes them: [(extent, (ensemble stride, verification stride))].
     """
-    shape = tuple(int(s) for s in shape)
-    strides = tuple(int(s) for s in strides)
-    nd = len(shape)
-    if nd < 1 or not -nd <= int(member_axis) < nd:
-        raise ValueError('ensemble_stats: member axis %s out of range of %d axes' % (member_axis, nd))
-    ax = int(member_axis) % nd
-    M = shape[ax]
-    if M < 2:
-        raise ValueError('ensemble_stats: %d members (at least 2)' % M)
-    eshape = shape[:ax] + shape[ax + 1:]
-    es = strides[:ax] + strides[ax + 1:]
-    if valid_shape is None:
-        vs = (0,) * len(eshape)
-    else:
-        vshape = tuple(int(s) for s in valid_shape)
-        if len(vshape) != len(eshape) or any(v not in (1, e) for v, e in zip(vshape, eshape)):
-            raise ValueError('ensemble_stats: the verification %s must carry the dims of the ensemble without the member axis %s '
-                             '(extents of 1 broadcast)' % (vshape, eshape))
-        vs = tuple(0 if v == 1 else int(s) for v, s in zip(vshape, valid_strides))
-    order = sorted((i for i in range(len(eshape)) if eshape[i] != 1), key=lambda i: -abs(es[i]))
-    merged = _coalesce(order, eshape, [es, vs])
-    if len(merged) > nat.SCORE_MAX_DIMS:
-        raise NotImplementedError('ensemble_stats: more than %d element dims after merging' % nat.SCORE_MAX_DIMS)
-    return M, strides[ax], eshape, order, merged
+    return element_layout(shape, strides, member_axis, [(valid_shape, valid_strides)], 'ensemble_stats', 2, nat.SCORE_MAX_DIMS)
 
 
 def ensemble_desc(M, member_stride, merged, fair=False, ddof=1, variance=False):
@@ -2644,6 +2602,30 @@ def ensemble_plan(shape, strides, member_axis=0, valid_shape=None, valid_strides
     return dict(m_class=info[0], vec=bool(info[1]), valid=info[2], lds=bool(info[3]), grid=(info[4], info[5]), threads=info[6])
 
 
+def _ordered_outputs(names, int_names, per_q, Q, eshape, order, device):
+    """
+    The outputs of a kernel that writes flat in `order` (layout.element_layout): ({name: flat buffer}, {name: view of it with the
+    element shape}); the names in `per_q` carry a leading dim of Q.  float32, int32 for `int_names`.
+    """
+    n = 1
+    for e in eshape:
+        n *= e
+    perm = [order.index(i) for i in sorted(order)]
+    flat, res = {}, {}
+    for name in names:
+        lead = [Q] if name in per_q else []
+        flat[name] = torch.empty(lead + [n], dtype=torch.int32 if name in int_names else torch.float32, device=device)
+        if n:
+            t = flat[name].view(lead + [eshape[i] for i in order]).permute(list(range(len(lead))) + [len(lead) + q for q in perm])
+            for i, e in enumerate(eshape):
+                if e == 1:
+                    t = t.unsqueeze(len(lead) + i)
+            res[name] = t
+        else:
+            res[name] = flat[name].view(lead + list(eshape))
+    return n, flat, res
+
+
 def ensemble_stats(ens, valid=None, member_axis=0, want=ENSEMBLE_OUTPUTS, fair=False, ddof=1, variance=False):
     """
     Collapse the member axis of the float32 device tensor `ens` element by element: dict of device tensors shaped like `ens`
@@ -2672,20 +2654,7 @@ def ensemble_stats(ens, valid=None, member_axis=0, want=ENSEMBLE_OUTPUTS, fair=F
     if M > ENSEMBLE_MAX_M:
         raise NotImplementedError('ensemble_stats: %d members, the kernel serves 2 .. %d' % (M, ENSEMBLE_MAX_M))
     d = ensemble_desc(M, ms, merged, fair, ddof, variance)
-    n = 1
-    for e in eshape:
-        n *= e
-    dims = sorted(order)
-    perm = [order.index(i) for i in dims]
-    flat, res = {}, {}
-    for name in ENSEMBLE_OUTPUTS:
-        if name in want:
-            flat[name] = torch.empty(n, dtype=torch.int32 if name == 'rank' else torch.float32, device=ens.device)
-            t = flat[name].view([eshape[i] for i in order]).permute(perm) if order else flat[name].view(())
-            for i, e in enumerate(eshape):
-                if e == 1:
-                    t = t.unsqueeze(i)
-            res[name] = t if n else flat[name].view(eshape)
+    n, flat, res = _ordered_outputs([w for w in ENSEMBLE_OUTPUTS if w in want], ('rank',), (), 0, eshape, order, ens.device)
     if n:
         with torch.cuda.device(ens.device):
             check(lib().dlwpcs_ensemble_stats(ctypes.byref(d), ptr(ens), ptr(valid) or None, ptr(flat.get('mean')) or None,
@@ -2710,17 +2679,7 @@ def category_layout(shape, strides, thr_shape, thr_strides, member_axis=0, thres
     thresholds carry the element dims of the ensemble (extents of 1 broadcast) with the threshold axis at `threshold_axis`; a
     bare (Q,) vector serves every element.
     """
-    shape = tuple(int(s) for s in shape)
-    strides = tuple(int(s) for s in strides)
-    nd = len(shape)
-    if nd < 1 or not -nd <= int(member_axis) < nd:
-        raise ValueError('ensemble_category: member axis %s out of range of %d axes' % (member_axis, nd))
-    ax = int(member_axis) % nd
-    M = shape[ax]
-    if M < 1:
-        raise ValueError('ensemble_category: %d members (at least 1)' % M)
-    eshape = shape[:ax] + shape[ax + 1:]
-    es = strides[:ax] + strides[ax + 1:]
+    _, _, eshape, _ = member_split(shape, strides, member_axis, 'ensemble_category', 1)
     tshape = tuple(int(s) for s in thr_shape)
     tstr = tuple(int(s) for s in thr_strides)
     if len(tshape) == 1:
@@ -2738,19 +2697,9 @@ def category_layout(shape, strides, thr_shape, thr_strides, member_axis=0, thres
         ts = tuple(0 if t == 1 else s for t, s in zip(rest, rstr))
     if Q < 1:
         raise ValueError('ensemble_category: %d thresholds (at least 1)' % Q)
-    if valid_shape is None:
-        vs = (0,) * len(eshape)
-    else:
-        vshape = tuple(int(s) for s in valid_shape)
-        if len(vshape) != len(eshape) or any(v not in (1, e) for v, e in zip(vshape, eshape)):
-            raise ValueError('ensemble_category: the verification %s must carry the dims of the ensemble without the member axis '
-                             '%s (extents of 1 broadcast)' % (vshape, eshape))
-        vs = tuple(0 if v == 1 else int(s) for v, s in zip(vshape, valid_strides))
-    order = sorted((i for i in range(len(eshape)) if eshape[i] != 1), key=lambda i: -abs(es[i]))
-    merged = _coalesce(order, eshape, [es, vs, ts])
-    if len(merged) > nat.SCORE_MAX_DIMS:
-        raise NotImplementedError('ensemble_category: more than %d element dims after merging' % nat.SCORE_MAX_DIMS)
-    return M, strides[ax], Q, qs, eshape, order, merged
+    M, ms, eshape, order, merged = element_layout(shape, strides, member_axis, [(valid_shape, valid_strides), (None, ts)],
+                                                  'ensemble_category', 1, nat.SCORE_MAX_DIMS)
+    return M, ms, Q, qs, eshape, order, merged
 
 
 def category_desc(M, member_stride, Q, thr_stride, merged, fair=False, ref_prob=None):
@@ -2829,23 +2778,8 @@ def ensemble_category(ens, valid, thresholds, member_axis=0, threshold_axis=0, w
     if fair and M < 2:
         raise ValueError('ensemble_category: the fair score needs at least 2 members')
     d = category_desc(M, ms, Q, qs, merged, fair, ref_prob)
-    n = 1
-    for e in eshape:
-        n *= e
-    perm = [order.index(i) for i in sorted(order)]
-    flat, res = {}, {}
-    for name in CATEGORY_OUTPUTS:
-        if name in want:
-            lead = [Q] if name in _CATEGORY_PER_THRESHOLD else []
-            flat[name] = torch.empty(lead + [n], dtype=torch.int32 if name == 'code' else torch.float32, device=ens.device)
-            if n:
-                t = flat[name].view(lead + [eshape[i] for i in order]).permute(list(range(len(lead))) + [len(lead) + q for q in perm])
-                for i, e in enumerate(eshape):
-                    if e == 1:
-                        t = t.unsqueeze(len(lead) + i)
-                res[name] = t
-            else:
-                res[name] = flat[name].view(lead + list(eshape))
+    n, flat, res = _ordered_outputs([w for w in CATEGORY_OUTPUTS if w in want], ('code',), _CATEGORY_PER_THRESHOLD, Q, eshape, order,
+                                    ens.device)
     if n:
         with torch.cuda.device(ens.device):
             check(lib().dlwpcs_ensemble_category(ctypes.byref(d), ptr(ens), ptr(valid) or None, ptr(thresholds),
@@ -2884,18 +2818,11 @@ def rows_layout(shape, strides, row_axis, out_perm, n_out):
     for pos in range(nd - 1, -1, -1):
         ostride[pos] = run
         run *= max(oshape[pos], 1)                              # (torch's strides of a contiguous tensor)
-    dims, out_row = [], 0
-    for pos, a in enumerate(perm):
-        if a == row_axis:
-            out_row = ostride[pos]
-            dims.append(None)                                   # the row axis separates what may merge
-        elif shape[a] != 1:
-            cur = (shape[a], strides[a], ostride[pos])
-            if dims and dims[-1] is not None and dims[-1][1] == cur[1] * cur[0] and dims[-1][2] == cur[2] * cur[0]:
-                dims[-1] = (dims[-1][0] * cur[0], cur[1], cur[2])
-            else:
-                dims.append(cur)
-    dims = [x for x in dims if x is not None]
+    at = perm.index(row_axis)
+    out_row = ostride[at]
+    # (the tag: the row axis separates what may merge)
+    dims = [(e, ss, os_) for e, (ss, os_), _ in
+            merge_dims((shape[a], (strides[a], ostride[pos]), pos > at) for pos, a in enumerate(perm) if a != row_axis)]
     unit = [i for i, x in enumerate(dims) if x[1] == 1]
     if unit:
         dims.append(dims.pop(unit[-1]))
@@ -3139,19 +3066,6 @@ def _space_stride(shape, strides):
     return run[-1][1] if run else 1
 
 
-def _fold(dims):
-    """[(extent, x stride, y stride)] with extent-1 dims dropped and neighbours merged where both operands allow it"""
-    out = []
-    for e, xs, ys in dims:
-        if e == 1:
-            continue
-        if out and out[-1][1] == xs * e and out[-1][2] == ys * e:
-            out[-1] = (out[-1][0] * e, xs, ys)
-        else:
-            out.append((e, xs, ys))
-    return out
-
-
 def sparse_map_apply(m, x, space_axes, out=None, skipna=False, min_valid=0.5, renormalize=True, frac_out=None):
     """
     y = m applied to the source grid in the consecutive `space_axes` of the fp32 / bf16 device tensor x (DLWP.remap.OfflineMap;
@@ -3209,9 +3123,10 @@ def sparse_map_apply(m, x, space_axes, out=None, skipna=False, min_valid=0.5, re
         ys = _space_stride(yv.shape[a0:b1], yv.stride()[a0:b1])
         if xs is None or ys is None:
             return None
-        pre = _fold([(xv.shape[i], xv.stride(i), yv.stride(i)) for i in range(a0)])
-        post = _fold([(xv.shape[i], xv.stride(i), yv.stride(i - a1 + b1)) for i in range(a1, xv.dim())])
-        rest = pre + post
+        # (the tag: the dims before and after the space axes do not merge with each other)
+        rest = [(e, sx, sy) for e, (sx, sy), _ in
+                merge_dims([(xv.shape[i], (xv.stride(i), yv.stride(i)), 0) for i in range(a0)] +
+                           [(xv.shape[i], (xv.stride(i), yv.stride(i - a1 + b1)), 1) for i in range(a1, xv.dim())])]
         # inner (lanes span it): the dim of smallest output stride, if x is also denser along it than along the space axis;
         # otherwise it becomes the fastest outer dim, whose consecutive slices a lane handles together
         inner = min(range(len(rest)), key=lambda i: (abs(rest[i][2]), -i)) if rest else None
@@ -3353,7 +3268,8 @@ def _chan_desc(x, axis, y=None, row0=False):
     else:
         ks = [k for k in [1, 0] + list(range(2, axis + 1)) if k <= axis]
     for k in ks:
-        rows, inner = _fold(dims[:k]), _fold(dims[k:axis] + dims[axis + 1:])
+        rows, inner = ([(e,) + st for e, st, _ in merge_dims((e, (sx, sy), None) for e, sx, sy in group)]
+                       for group in (dims[:k], dims[k:axis] + dims[axis + 1:]))
         if len(rows) > 1 or len(inner) > 1:
             continue
         r, s = (rows or [(1, 0, 0)])[0], (inner or [(1, 0, 0)])[0]

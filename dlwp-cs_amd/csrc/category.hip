@@ -10,7 +10,7 @@
 //
 // No profiler tags: the launch profiler's registry is the convolution family's (tests/test_conv_coverage_tags.py closes it over the
 // convolution case table), as for the other verification kernels.
-#include "common.h"
+#include "strided.h"
 
 namespace dlwpcs {
 
@@ -32,61 +32,9 @@ struct CatGeom {
     float ref[CAT_MAXQ];
 };
 
-__device__ __forceinline__ bool cat_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-__device__ __forceinline__ float cat_nan() { return __uint_as_float(0x7fc00000u); }
-__device__ __forceinline__ float cat_inf() { return __uint_as_float(0x7f800000u); }
-
 // offsets (elements) of element e in ens, valid and thr
 __device__ __forceinline__ void cat_offsets(const CatGeom &G, int64_t e, int64_t &eo, int64_t &vo, int64_t &to) {
-    eo = 0; vo = 0; to = 0;
-    if (G.small) {
-        uint32_t q = (uint32_t)e;
-        for (int d = G.n_dims - 1; d >= 0; --d) {
-            const uint32_t x = (uint32_t)G.ext[d], c = q % x;
-            q /= x;
-            eo += (int64_t)c * G.es[d];
-            vo += (int64_t)c * G.vs[d];
-            to += (int64_t)c * G.ts[d];
-        }
-    } else {
-        int64_t q = e;
-        for (int d = G.n_dims - 1; d >= 0; --d) {
-            const int64_t x = G.ext[d], c = q % x;
-            q /= x;
-            eo += c * G.es[d];
-            vo += c * G.vs[d];
-            to += c * G.ts[d];
-        }
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void cat_load(const float *__restrict__ p, float (&x)[V]) {
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        x[0] = t.x; x[V > 1 ? 1 : 0] = t.y; x[V > 2 ? 2 : 0] = t.z; x[V - 1] = t.w;
-    } else {
-        x[0] = *p;
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void cat_store(float *__restrict__ p, const float (&x)[V], bool wide) {
-    if (V == 4 && wide) {
-        *reinterpret_cast<float4 *>(p) = make_float4(x[0], x[V > 1 ? 1 : 0], x[V > 2 ? 2 : 0], x[V - 1]);
-    } else {
-#pragma unroll
-        for (int v = 0; v < V; ++v) p[v] = x[v];
-    }
-}
-template <int V>
-__device__ __forceinline__ void cat_store(int32_t *__restrict__ p, const int32_t (&x)[V], bool wide) {
-    if (V == 4 && wide) {
-        *reinterpret_cast<int4 *>(p) = make_int4(x[0], x[V > 1 ? 1 : 0], x[V > 2 ? 2 : 0], x[V - 1]);
-    } else {
-#pragma unroll
-        for (int v = 0; v < V; ++v) p[v] = x[v];
-    }
+    flat_offsets_either<1>(G.small != 0, G.n_dims, G.ext, e, Strided{G.es, eo}, Strided{G.vs, vo}, Strided{G.ts, to});
 }
 
 template <int QC, bool VEC>
@@ -97,7 +45,7 @@ __global__ void __launch_bounds__(CAT_THREADS) ensemble_category_kernel(CatGeom 
                                                                         float *__restrict__ o_ref, int32_t *__restrict__ o_code) {
 #pragma clang fp contract(off)
     constexpr int V = VEC ? 4 : 1;
-    const int64_t item = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * CAT_THREADS + threadIdx.x;
+    const int64_t item = flat_block() * CAT_THREADS + threadIdx.x;
     const int64_t e0 = item * V;
     if (e0 >= G.E) return;                              // (16-byte form: the last extent is a multiple of 4, so is E)
     int64_t eo, vo, to;
@@ -112,14 +60,14 @@ __global__ void __launch_bounds__(CAT_THREADS) ensemble_category_kernel(CatGeom 
         if (j < Q) {
             const float *p = thr + to + (int64_t)j * G.tstride;
             if (VEC && G.tmode == 1) {
-                cat_load<V>(p, t[j]);
+                load_chunk<V>(p, t[j]);
             } else {
 #pragma unroll
                 for (int v = 0; v < V; ++v) t[j][v] = p[v * tl];
             }
         } else {
 #pragma unroll
-            for (int v = 0; v < V; ++v) t[j][v] = cat_inf();
+            for (int v = 0; v < V; ++v) t[j][v] = pos_inf();
         }
 #pragma unroll
         for (int v = 0; v < V; ++v) k[j][v] = 0;
@@ -134,10 +82,10 @@ __global__ void __launch_bounds__(CAT_THREADS) ensemble_category_kernel(CatGeom 
 #pragma unroll
         for (int u = 0; u < CAT_UNROLL; ++u) {
             if (i0 + u < M) {
-                cat_load<V>(pe + (int64_t)(i0 + u) * G.mstride, x[u]);
+                load_chunk<V>(pe + (int64_t)(i0 + u) * G.mstride, x[u]);
             } else {
 #pragma unroll
-                for (int v = 0; v < V; ++v) x[u][v] = cat_inf();
+                for (int v = 0; v < V; ++v) x[u][v] = pos_inf();
             }
         }
 #pragma unroll
@@ -145,7 +93,7 @@ __global__ void __launch_bounds__(CAT_THREADS) ensemble_category_kernel(CatGeom 
             if (i0 + u < M) {
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    bad[v] |= cat_nonfinite(x[u][v]);
+                    bad[v] |= nonfinite(x[u][v]);
 #pragma unroll
                     for (int j = 0; j < QC; ++j) k[j][v] += x[u][v] <= t[j][v] ? 1 : 0;
                 }
@@ -157,7 +105,7 @@ __global__ void __launch_bounds__(CAT_THREADS) ensemble_category_kernel(CatGeom 
 #pragma unroll
     for (int v = 0; v < V; ++v) y[v] = 0.f;
     if (VEC && G.vmode == 1) {
-        cat_load<V>(valid + vo, y);
+        load_chunk<V>(valid + vo, y);
     } else if (has_y) {
 #pragma unroll
         for (int v = 0; v < V; ++v) y[v] = valid[vo + v * vl];
@@ -171,7 +119,7 @@ __global__ void __launch_bounds__(CAT_THREADS) ensemble_category_kernel(CatGeom 
 #pragma unroll
     for (int v = 0; v < V; ++v) {
         rps[v] = 0.f; ref[v] = 0.f; pair[v] = 0; anyt[v] = false;
-        ybad[v] = !has_y || cat_nonfinite(y[v]);
+        ybad[v] = !has_y || nonfinite(y[v]);
     }
 #pragma unroll
     for (int j = 0; j < QC; ++j)
@@ -190,14 +138,14 @@ __global__ void __launch_bounds__(CAT_THREADS) ensemble_category_kernel(CatGeom 
                 pair[v] += kk * (M - kk);
                 anyt[v] |= tnan;
                 const bool miss = bad[v] || tnan;
-                pr[v] = miss ? cat_nan() : (float)kk / fm;
-                br[v] = (miss || ybad[v]) ? cat_nan() : b;
+                pr[v] = miss ? quiet_nan() : (float)kk / fm;
+                br[v] = (miss || ybad[v]) ? quiet_nan() : b;
                 cd[v] = (miss || ybad[v]) ? -1 : 2 * kk + o;
             }
             const int64_t at = (int64_t)j * G.E + e0;
-            if (o_prob) cat_store<V>(o_prob + at, pr, wide);
-            if (o_brier) cat_store<V>(o_brier + at, br, wide);
-            if (o_code) cat_store<V>(o_code + at, cd, wide);
+            if (o_prob) store_chunk<V>(o_prob + at, pr, wide, 1);
+            if (o_brier) store_chunk<V>(o_brier + at, br, wide, 1);
+            if (o_code) store_chunk<V>(o_code + at, cd, wide, 1);
         }
     if (o_rps || o_ref) {
         float r[V], f[V];
@@ -206,11 +154,11 @@ __global__ void __launch_bounds__(CAT_THREADS) ensemble_category_kernel(CatGeom 
             const bool miss = bad[v] || ybad[v] || anyt[v];
             float s = rps[v];
             if (G.fair) s = s - (float)pair[v] / ((float)(M * M) * (float)(M - 1));
-            r[v] = miss ? cat_nan() : s;
-            f[v] = miss ? cat_nan() : ref[v];
+            r[v] = miss ? quiet_nan() : s;
+            f[v] = miss ? quiet_nan() : ref[v];
         }
-        if (o_rps) cat_store<V>(o_rps + e0, r, wide);
-        if (o_ref) cat_store<V>(o_ref + e0, f, wide);
+        if (o_rps) store_chunk<V>(o_rps + e0, r, wide, 1);
+        if (o_ref) store_chunk<V>(o_ref + e0, f, wide, 1);
     }
 }
 
@@ -220,12 +168,6 @@ struct CatPlan {
     bool vec_ok, vvec_ok, tvec_ok, tuniform, vec;
     int64_t nblk;
 };
-
-dim3 cat_grid(int64_t n) {
-    if (n <= 0) return dim3(0, 0);                      // (a zero extent: reported by the plan query, never launched)
-    const int64_t gx = n < 65536 ? n : 65536;
-    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
-}
 
 // everything the descriptor decides: the class, whether extents and strides allow 16-byte loads
 int cat_plan(const dlwpcs_category_desc *d, CatPlan &P) {
@@ -286,19 +228,19 @@ int cat_settle(CatPlan &P, const void *ens, const void *valid, const void *thr) 
     if (P.G.E > 0 && (!ens || !thr)) return fail(DLWPCS_E_INVALID, "ensemble_category: null ensemble or thresholds");
     if ((((uintptr_t)ens) | ((uintptr_t)valid) | ((uintptr_t)thr)) & 3)
         return fail(DLWPCS_E_INVALID, "ensemble_category: an operand is not aligned to its 4-byte elements");
-    P.vec = P.vec_ok && !(((uintptr_t)ens) & 15);
-    P.G.vmode = !valid ? -1 : (P.vec && P.vvec_ok && !(((uintptr_t)valid) & 15)) ? 1 : 0;
-    P.G.tmode = P.tuniform ? 2 : (P.vec && P.tvec_ok && !(((uintptr_t)thr) & 15)) ? 1 : 0;
+    P.vec = P.vec_ok && aligned16(ens);
+    P.G.vmode = !valid ? -1 : (P.vec && P.vvec_ok && aligned16(valid)) ? 1 : 0;
+    P.G.tmode = P.tuniform ? 2 : (P.vec && P.tvec_ok && aligned16(thr)) ? 1 : 0;
     const int64_t per_blk = (int64_t)CAT_THREADS * (P.vec ? 4 : 1);
     P.nblk = (P.G.E + per_blk - 1) / per_blk;
-    if (P.nblk > 65536ll * 65535ll) return fail(DLWPCS_E_UNSUPPORTED, "ensemble_category: %lld workgroups is too many", (long long)P.nblk);
+    if (P.nblk > MAX_BLOCKS) return fail(DLWPCS_E_UNSUPPORTED, "ensemble_category: %lld workgroups is too many", (long long)P.nblk);
     return DLWPCS_OK;
 }
 
 template <int QC, bool VEC>
 void cat_launch(const CatPlan &P, const float *ens, const float *valid, const float *thr, float *pr, float *br, float *rps, float *ref,
                 int32_t *code, hipStream_t s) {
-    hipLaunchKernelGGL((ensemble_category_kernel<QC, VEC>), cat_grid(P.nblk), dim3(CAT_THREADS), 0, s, P.G, ens, valid, thr, pr, br,
+    hipLaunchKernelGGL((ensemble_category_kernel<QC, VEC>), launch_grid(P.nblk), dim3(CAT_THREADS), 0, s, P.G, ens, valid, thr, pr, br,
                        rps, ref, code);
 }
 
@@ -350,7 +292,7 @@ extern "C" int dlwpcs_ensemble_category_plan_info(const dlwpcs_category_desc *d,
     if (rc != DLWPCS_OK) return rc;
     rc = cat_settle(P, ens, valid, thr);
     if (rc != DLWPCS_OK) return rc;
-    const dim3 grid = cat_grid(P.nblk);
+    const dim3 grid = launch_grid(P.nblk);
     info[0] = P.cls;
     info[1] = P.vec ? 1 : 0;
     info[2] = P.G.vmode;

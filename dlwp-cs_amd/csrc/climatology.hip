@@ -10,7 +10,7 @@
 // its own workgroups and stores the slab sums, group_finish_kernel adds them -- the same additions in the same order, so the
 // two forms give the same bits.  No atomics.
 #include <string.h>
-#include "common.h"
+#include "strided.h"
 
 namespace dlwpcs {
 
@@ -22,58 +22,10 @@ constexpr int GM_SLAB = DLWPCS_GROUP_SLAB_ROWS;
 constexpr int64_t GM_TARGET_BLOCKS = 512;       // 256 CUs x 2: measured, 648 workgroups in one launch already stream at the HBM rate
 
 struct RowsGeom {
-    int32_t n_inner, out_vec;
-    int64_t ext[DLWPCS_SCORE_MAX_DIMS];         // the last extent counts chunks (elements / V)
-    int64_t sst[DLWPCS_SCORE_MAX_DIMS];
-    int64_t ost[DLWPCS_SCORE_MAX_DIMS];
-    int64_t src_row_stride, out_row_stride;
-    int64_t ncol;                               // chunks per row
-    int64_t tiles;                              // column tiles of GM_THREADS chunks
+    RowsAddr A;
+    int32_t out_vec;
     int64_t slabs;                              // slabs per group of the split form
-    int64_t nblk;
 };
-
-__device__ __forceinline__ int64_t flat_block() { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
-
-// chunk q of a row -> element offsets in the source and in the output
-template <int V>
-__device__ __forceinline__ void chunk_offsets(const RowsGeom &G, int64_t q, int64_t &soff, int64_t &ooff) {
-    soff = 0;
-    ooff = 0;
-    for (int d = G.n_inner - 1; d >= 0; --d) {
-        const int64_t e = G.ext[d];
-        int64_t c = q % e;
-        q /= e;
-        if (d == G.n_inner - 1) c *= V;
-        soff += c * G.sst[d];
-        ooff += c * G.ost[d];
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void load_chunk(const float *__restrict__ p, float x[V]) {
-    if constexpr (V == 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(p);
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    } else {
-        x[0] = *p;
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void store_chunk(const RowsGeom &G, float *__restrict__ p, const float x[V]) {
-    if constexpr (V == 4) {
-        if (G.out_vec) {
-            *reinterpret_cast<float4 *>(p) = make_float4(x[0], x[1], x[2], x[3]);
-        } else {
-            const int64_t st = G.ost[G.n_inner - 1];
-#pragma unroll
-            for (int j = 0; j < V; ++j) p[j * st] = x[j];
-        }
-    } else {
-        *p = x[0];
-    }
-}
 
 // rows [j0, j1) of the CSR added to s / n row by row
 template <int V>
@@ -97,13 +49,13 @@ __device__ __forceinline__ void slab_sum(const float *__restrict__ src, const in
 template <int V>
 __device__ __forceinline__ void finish(const RowsGeom &G, const double tot[V], const int32_t cnt[V], float *__restrict__ out,
                                        int32_t *__restrict__ count, int64_t off) {
-    const float nan = __int_as_float(0x7fc00000);
+    const float nan = quiet_nan();
     float r[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) r[v] = cnt[v] ? (float)(tot[v] / (double)cnt[v]) : nan;
-    store_chunk<V>(G, out + off, r);
+    const int64_t st = G.A.last_out_stride();
+    store_chunk<V>(out + off, r, G.out_vec != 0, st);
     if (count) {
-        const int64_t st = G.n_inner ? G.ost[G.n_inner - 1] : 1;
 #pragma unroll
         for (int v = 0; v < V; ++v) count[off + v * st] = cnt[v];
     }
@@ -117,14 +69,14 @@ __global__ void __launch_bounds__(GM_THREADS) group_mean_kernel(RowsGeom G, cons
                                                                int32_t *__restrict__ count) {
     constexpr int V = VEC ? 4 : 1;
     const int64_t bid = flat_block();
-    if (bid >= G.nblk) return;
-    const int64_t unit = bid / G.tiles;
-    const int64_t q = (bid - unit * G.tiles) * GM_THREADS + threadIdx.x;
-    if (q >= G.ncol) return;
+    if (bid >= G.A.nblk) return;
+    const int64_t unit = bid / G.A.tiles;
+    const int64_t q = (bid - unit * G.A.tiles) * GM_THREADS + threadIdx.x;
+    if (q >= G.A.ncol) return;
     const int64_t k = SPLIT ? unit / G.slabs : unit;
     const int64_t g0 = group_start[k], g1 = group_start[k + 1];
     int64_t soff, ooff;
-    chunk_offsets<V>(G, q, soff, ooff);
+    rows_offsets<V, false>(G.A, q, soff, ooff);
     const float *p = src + soff;
     if constexpr (SPLIT) {
         const int64_t slab = unit - k * G.slabs;
@@ -134,8 +86,8 @@ __global__ void __launch_bounds__(GM_THREADS) group_mean_kernel(RowsGeom G, cons
         int32_t n[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) { s[v] = 0.0; n[v] = 0; }
-        slab_sum<V>(p, row_index, G.src_row_stride, j0, j0 + GM_SLAB < g1 ? j0 + GM_SLAB : g1, s, n);
-        const int64_t at = (unit * G.ncol + q) * V;
+        slab_sum<V>(p, row_index, G.A.src_row_stride, j0, j0 + GM_SLAB < g1 ? j0 + GM_SLAB : g1, s, n);
+        const int64_t at = (unit * G.A.ncol + q) * V;
 #pragma unroll
         for (int v = 0; v < V; ++v) { psum[at + v] = s[v]; pcnt[at + v] = n[v]; }
     } else {
@@ -147,11 +99,11 @@ __global__ void __launch_bounds__(GM_THREADS) group_mean_kernel(RowsGeom G, cons
             double s[V];
 #pragma unroll
             for (int v = 0; v < V; ++v) s[v] = 0.0;
-            slab_sum<V>(p, row_index, G.src_row_stride, j0, j0 + GM_SLAB < g1 ? j0 + GM_SLAB : g1, s, cnt);
+            slab_sum<V>(p, row_index, G.A.src_row_stride, j0, j0 + GM_SLAB < g1 ? j0 + GM_SLAB : g1, s, cnt);
 #pragma unroll
             for (int v = 0; v < V; ++v) tot[v] += s[v];
         }
-        finish<V>(G, tot, cnt, out, count, k * G.out_row_stride + ooff);
+        finish<V>(G, tot, cnt, out, count, k * G.A.out_row_stride + ooff);
     }
 }
 
@@ -162,24 +114,24 @@ __global__ void __launch_bounds__(GM_THREADS) group_finish_kernel(RowsGeom G, co
                                                                  int32_t *__restrict__ count) {
     constexpr int V = VEC ? 4 : 1;
     const int64_t bid = flat_block();
-    if (bid >= G.nblk) return;
-    const int64_t k = bid / G.tiles;
-    const int64_t q = (bid - k * G.tiles) * GM_THREADS + threadIdx.x;
-    if (q >= G.ncol) return;
+    if (bid >= G.A.nblk) return;
+    const int64_t k = bid / G.A.tiles;
+    const int64_t q = (bid - k * G.A.tiles) * GM_THREADS + threadIdx.x;
+    if (q >= G.A.ncol) return;
     const int64_t rows = (int64_t)group_start[k + 1] - group_start[k];
     const int64_t nslab = (rows + GM_SLAB - 1) / GM_SLAB;
     int64_t soff, ooff;
-    chunk_offsets<V>(G, q, soff, ooff);
+    rows_offsets<V, false>(G.A, q, soff, ooff);
     double tot[V];
     int32_t cnt[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) { tot[v] = 0.0; cnt[v] = 0; }
     for (int64_t s = 0; s < nslab; ++s) {
-        const int64_t at = ((k * G.slabs + s) * G.ncol + q) * V;
+        const int64_t at = ((k * G.slabs + s) * G.A.ncol + q) * V;
 #pragma unroll
         for (int v = 0; v < V; ++v) { tot[v] += psum[at + v]; cnt[v] += pcnt[at + v]; }
     }
-    finish<V>(G, tot, cnt, out, count, k * G.out_row_stride + ooff);
+    finish<V>(G, tot, cnt, out, count, k * G.A.out_row_stride + ooff);
 }
 
 template <bool VEC>
@@ -187,26 +139,21 @@ __global__ void __launch_bounds__(GM_THREADS) rows_gather_kernel(RowsGeom G, con
                                                                 const int32_t *__restrict__ index, float *__restrict__ out) {
     constexpr int V = VEC ? 4 : 1;
     const int64_t bid = flat_block();
-    if (bid >= G.nblk) return;
-    const int64_t i = bid / G.tiles;
-    const int64_t q = (bid - i * G.tiles) * GM_THREADS + threadIdx.x;
-    if (q >= G.ncol) return;
+    if (bid >= G.A.nblk) return;
+    const int64_t i = bid / G.A.tiles;
+    const int64_t q = (bid - i * G.A.tiles) * GM_THREADS + threadIdx.x;
+    if (q >= G.A.ncol) return;
     int64_t soff, ooff;
-    chunk_offsets<V>(G, q, soff, ooff);
+    rows_offsets<V, false>(G.A, q, soff, ooff);
     const int32_t r = index[i];
     float x[V];
     if (r >= 0) {
-        load_chunk<V>(src + (int64_t)r * G.src_row_stride + soff, x);
+        load_chunk<V>(src + (int64_t)r * G.A.src_row_stride + soff, x);
     } else {
 #pragma unroll
-        for (int v = 0; v < V; ++v) x[v] = __int_as_float(0x7fc00000);
+        for (int v = 0; v < V; ++v) x[v] = quiet_nan();
     }
-    store_chunk<V>(G, out + i * G.out_row_stride + ooff, x);
-}
-
-static dim3 grid_of(int64_t n) {
-    const int64_t gx = n < 65536 ? n : 65536;
-    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
+    store_chunk<V>(out + i * G.A.out_row_stride + ooff, x, G.out_vec != 0, G.A.last_out_stride());
 }
 
 struct RowsPlan {
@@ -216,39 +163,24 @@ struct RowsPlan {
 };
 
 int make_rows_plan(const dlwpcs_rows_desc *d, const char *what, RowsPlan &P) {
-    if (!d) return fail(DLWPCS_E_INVALID, "%s: null descriptor", what);
-    if (d->n_inner < 0 || d->n_inner > DLWPCS_SCORE_MAX_DIMS) return fail(DLWPCS_E_INVALID, "%s: n_inner %d out of range", what, d->n_inner);
     RowsGeom &G = P.G;
     memset(&G, 0, sizeof(G));
-    G.n_inner = d->n_inner;
-    G.src_row_stride = d->src_row_stride;
-    G.out_row_stride = d->out_row_stride;
-    P.inner = 1;
-    for (int i = 0; i < d->n_inner; ++i) {
-        if (d->inner_ext[i] < 0) return fail(DLWPCS_E_INVALID, "%s: inner extent %lld", what, (long long)d->inner_ext[i]);
-        G.ext[i] = d->inner_ext[i];
-        G.sst[i] = d->src_stride[i];
-        G.ost[i] = d->out_stride[i];
-        P.inner *= d->inner_ext[i];
-    }
+    const int rc = rows_addr_init(d, what, G.A, P.inner);
+    if (rc != DLWPCS_OK) return rc;
     // vector path: 16-byte loads along the last dim; every other offset keeps a row chunk on 16 bytes
-    const int L = d->n_inner - 1;
-    bool vec = L >= 0 && d->src_stride[L] == 1 && d->inner_ext[L] % 4 == 0 && d->src_row_stride % 4 == 0;
-    for (int i = 0; i < L && vec; ++i) vec = d->src_stride[i] % 4 == 0;
-    bool ovec = vec && d->out_stride[L] == 1 && d->out_row_stride % 4 == 0;
-    for (int i = 0; i < L && ovec; ++i) ovec = d->out_stride[i] % 4 == 0;
-    P.vec = vec;
+    bool ovec;
+    rows_vector_ok(d, P.vec, ovec);
     G.out_vec = ovec;
     return DLWPCS_OK;
 }
 
 // after the pointers are known: settle the load width, then the chunk counts
 void settle(RowsPlan &P, const void *src, const void *out) {
-    if (P.vec && (((uintptr_t)src) & 15)) P.vec = false;
-    if (P.G.out_vec && (!P.vec || (((uintptr_t)out) & 15))) P.G.out_vec = 0;
-    if (P.vec) P.G.ext[P.G.n_inner - 1] /= 4;
-    P.G.ncol = P.inner / (P.vec ? 4 : 1);
-    P.G.tiles = (P.G.ncol + GM_THREADS - 1) / GM_THREADS;
+    if (P.vec && !aligned16(src)) P.vec = false;
+    if (P.G.out_vec && (!P.vec || !aligned16(out))) P.G.out_vec = 0;
+    if (P.vec) P.G.A.ext[P.G.A.n_inner - 1] /= 4;
+    P.G.A.ncol = P.inner / (P.vec ? 4 : 1);
+    P.G.A.tiles = (P.G.A.ncol + GM_THREADS - 1) / GM_THREADS;
 }
 
 bool want_split(const RowsPlan &P, int n_groups, int64_t max_group_rows, int split) {
@@ -289,9 +221,9 @@ extern "C" int dlwpcs_group_mean(const dlwpcs_rows_desc *d, const float *src, co
     G.slabs = (max_group_rows + GM_SLAB - 1) / GM_SLAB;
     if (G.slabs < 1) G.slabs = 1;
     const bool sp = want_split(P, n_groups, max_group_rows, split);
-    const int64_t finish_blocks = (int64_t)n_groups * G.tiles;
-    G.nblk = sp ? finish_blocks * G.slabs : finish_blocks;
-    if (G.nblk > 65536ll * 65535ll) return fail(DLWPCS_E_INVALID, "group_mean: %lld workgroups is too many", (long long)G.nblk);
+    const int64_t finish_blocks = (int64_t)n_groups * G.A.tiles;
+    G.A.nblk = sp ? finish_blocks * G.slabs : finish_blocks;
+    if (G.A.nblk > MAX_BLOCKS) return fail(DLWPCS_E_INVALID, "group_mean: %lld workgroups is too many", (long long)G.A.nblk);
     double *psum = nullptr;
     int32_t *pcnt = nullptr;
     if (sp) {
@@ -303,7 +235,7 @@ extern "C" int dlwpcs_group_mean(const dlwpcs_rows_desc *d, const float *src, co
         pcnt = (int32_t *)(psum + cells);
     }
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid = grid_of(G.nblk), blk(GM_THREADS);
+    const dim3 grid = launch_grid(G.A.nblk), blk(GM_THREADS);
     if (!sp) {
         if (P.vec) hipLaunchKernelGGL((group_mean_kernel<true, false>), grid, blk, 0, s, G, src, group_start, row_index, psum, pcnt, out, count);
         else hipLaunchKernelGGL((group_mean_kernel<false, false>), grid, blk, 0, s, G, src, group_start, row_index, psum, pcnt, out, count);
@@ -311,9 +243,9 @@ extern "C" int dlwpcs_group_mean(const dlwpcs_rows_desc *d, const float *src, co
     }
     if (P.vec) hipLaunchKernelGGL((group_mean_kernel<true, true>), grid, blk, 0, s, G, src, group_start, row_index, psum, pcnt, out, count);
     else hipLaunchKernelGGL((group_mean_kernel<false, true>), grid, blk, 0, s, G, src, group_start, row_index, psum, pcnt, out, count);
-    G.nblk = finish_blocks;
-    if (P.vec) hipLaunchKernelGGL((group_finish_kernel<true>), grid_of(G.nblk), blk, 0, s, G, group_start, psum, pcnt, out, count);
-    else hipLaunchKernelGGL((group_finish_kernel<false>), grid_of(G.nblk), blk, 0, s, G, group_start, psum, pcnt, out, count);
+    G.A.nblk = finish_blocks;
+    if (P.vec) hipLaunchKernelGGL((group_finish_kernel<true>), launch_grid(G.A.nblk), blk, 0, s, G, group_start, psum, pcnt, out, count);
+    else hipLaunchKernelGGL((group_finish_kernel<false>), launch_grid(G.A.nblk), blk, 0, s, G, group_start, psum, pcnt, out, count);
     return check_launch("group_mean");
 }
 
@@ -327,10 +259,10 @@ extern "C" int dlwpcs_rows_gather(const dlwpcs_rows_desc *d, const float *src, c
     if (!src || !index || !out) return fail(DLWPCS_E_INVALID, "rows_gather: null operand");
     settle(P, src, out);
     RowsGeom &G = P.G;
-    G.nblk = n * G.tiles;
-    if (G.nblk > 65536ll * 65535ll) return fail(DLWPCS_E_INVALID, "rows_gather: %lld workgroups is too many", (long long)G.nblk);
+    G.A.nblk = n * G.A.tiles;
+    if (G.A.nblk > MAX_BLOCKS) return fail(DLWPCS_E_INVALID, "rows_gather: %lld workgroups is too many", (long long)G.A.nblk);
     hipStream_t s = (hipStream_t)stream;
-    if (P.vec) hipLaunchKernelGGL((rows_gather_kernel<true>), grid_of(G.nblk), dim3(GM_THREADS), 0, s, G, src, index, out);
-    else hipLaunchKernelGGL((rows_gather_kernel<false>), grid_of(G.nblk), dim3(GM_THREADS), 0, s, G, src, index, out);
+    if (P.vec) hipLaunchKernelGGL((rows_gather_kernel<true>), launch_grid(G.A.nblk), dim3(GM_THREADS), 0, s, G, src, index, out);
+    else hipLaunchKernelGGL((rows_gather_kernel<false>), launch_grid(G.A.nblk), dim3(GM_THREADS), 0, s, G, src, index, out);
     return check_launch("rows_gather");
 }

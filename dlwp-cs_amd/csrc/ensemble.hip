@@ -20,7 +20,7 @@
 // conflicts whatever row a lane is at), classes of 64 and 128 slots with 256 and 128 lanes per workgroup (64 KiB each, two
 // workgroups per CU).  Runs of 32 go through the register network and back; the sorted runs are then merged as a stream, one head
 // per run in registers, straight into the gap sums.  About 5 LDS accesses per member (a whole network in LDS: 55 at M = 128).
-#include "common.h"
+#include "strided.h"
 
 namespace dlwpcs {
 
@@ -38,30 +38,9 @@ struct EnsGeom {
     int64_t ext[DLWPCS_SCORE_MAX_DIMS], es[DLWPCS_SCORE_MAX_DIMS], vs[DLWPCS_SCORE_MAX_DIMS];
 };
 
-__device__ __forceinline__ bool ens_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-__device__ __forceinline__ float ens_nan() { return __uint_as_float(0x7fc00000u); }
-__device__ __forceinline__ float ens_inf() { return __uint_as_float(0x7f800000u); }
-
 // offsets (elements) of element e in ens and valid
 __device__ __forceinline__ void ens_offsets(const EnsGeom &G, int64_t e, int64_t &eo, int64_t &vo) {
-    eo = 0; vo = 0;
-    if (G.small) {
-        uint32_t q = (uint32_t)e;
-        for (int d = G.n_dims - 1; d >= 0; --d) {
-            const uint32_t x = (uint32_t)G.ext[d], c = q % x;
-            q /= x;
-            eo += (int64_t)c * G.es[d];
-            vo += (int64_t)c * G.vs[d];
-        }
-    } else {
-        int64_t q = e;
-        for (int d = G.n_dims - 1; d >= 0; --d) {
-            const int64_t x = G.ext[d], c = q % x;
-            q /= x;
-            eo += c * G.es[d];
-            vo += c * G.vs[d];
-        }
-    }
+    flat_offsets_either<1>(G.small != 0, G.n_dims, G.ext, e, Strided{G.es, eo}, Strided{G.vs, vo});
 }
 
 struct EnsOut { float mean, spread, crps; int32_t rank; };
@@ -123,11 +102,11 @@ __device__ __forceinline__ EnsOut ens_element_regs(float (&x)[MC], float y, cons
 #pragma unroll
     for (int i = 0; i < MC; ++i)
         if (i < M) {
-            bad |= ens_nonfinite(x[i]);
+            bad |= nonfinite(x[i]);
             rank += (has_y && x[i] < y) ? 1 : 0;
         }
-    const bool ybad = has_y && ens_nonfinite(y);
-    o.mean = o.spread = o.crps = ens_nan();
+    const bool ybad = has_y && nonfinite(y);
+    o.mean = o.spread = o.crps = quiet_nan();
     if (want_ms) {
         const float p = x[0];
         float s = 0.f;
@@ -149,7 +128,7 @@ __device__ __forceinline__ EnsOut ens_element_regs(float (&x)[MC], float y, cons
     }
     if (want_crps) {
 #pragma unroll
-        for (int i = 0; i < MC; ++i) x[i] = i < M ? x[i] - y : ens_inf();
+        for (int i = 0; i < MC; ++i) x[i] = i < M ? x[i] - y : pos_inf();
         ens_sort_regs<MC>(x);
         EnsGapSums g;
         float last = x[0];
@@ -171,7 +150,7 @@ __global__ void __launch_bounds__(ENS_THREADS) ensemble_reg_kernel(EnsGeom G, co
                                                                    float *__restrict__ o_spread, float *__restrict__ o_crps,
                                                                    int32_t *__restrict__ o_rank) {
     constexpr int V = VEC ? 4 : 1;
-    const int64_t item = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * ENS_THREADS + threadIdx.x;
+    const int64_t item = flat_block() * ENS_THREADS + threadIdx.x;
     const int64_t e0 = item * V;
     if (e0 >= G.E) return;                              // (16-byte form: the last extent is a multiple of 4, so is E)
     int64_t eo, vo;
@@ -233,7 +212,7 @@ __global__ void __launch_bounds__(ENS_LDS_FLOATS / MC) ensemble_lds_kernel(EnsGe
 #pragma clang fp contract(off)
     constexpr int T = ENS_LDS_FLOATS / MC;              // lanes of a workgroup = stride between a lane's members
     __shared__ float s_col[MC * T];
-    const int64_t e = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * T + threadIdx.x;
+    const int64_t e = flat_block() * T + threadIdx.x;
     if (e >= G.E) return;                               // (no barrier anywhere: a column belongs to its lane)
     float *col = s_col + threadIdx.x;                   // member i of this lane: col[i * T]
     int64_t eo, vo;
@@ -256,13 +235,13 @@ __global__ void __launch_bounds__(ENS_LDS_FLOATS / MC) ensemble_lds_kernel(EnsGe
             for (int i = 0; i < ENS_RUN; ++i)
                 if (r * ENS_RUN + i < M) {
                     col[(r * ENS_RUN + i) * T] = xr[i];
-                    bad |= ens_nonfinite(xr[i]);
+                    bad |= nonfinite(xr[i]);
                     rank += (has_y && xr[i] < y) ? 1 : 0;
                     if (r == 0 && i == 0) p = xr[0]; else s += xr[i] - p;
                 }
         }
-    const bool ybad = has_y && ens_nonfinite(y);
-    float mean = ens_nan(), spread = ens_nan(), crps = ens_nan();
+    const bool ybad = has_y && nonfinite(y);
+    float mean = quiet_nan(), spread = quiet_nan(), crps = quiet_nan();
     if (o_mean || o_spread) {
         const float tbar = s / (float)M;
         float q = 0.f;
@@ -283,12 +262,12 @@ __global__ void __launch_bounds__(ENS_LDS_FLOATS / MC) ensemble_lds_kernel(EnsGe
         int pos[NR];
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
-            head[r] = ens_inf();
+            head[r] = pos_inf();
             pos[r] = ENS_RUN;
             if (r * ENS_RUN < M) {                      // (uniform: a run without members stays exhausted)
                 float d[ENS_RUN];
 #pragma unroll
-                for (int i = 0; i < ENS_RUN; ++i) d[i] = r * ENS_RUN + i < M ? col[(r * ENS_RUN + i) * T] - y : ens_inf();
+                for (int i = 0; i < ENS_RUN; ++i) d[i] = r * ENS_RUN + i < M ? col[(r * ENS_RUN + i) * T] - y : pos_inf();
                 ens_sort_regs<ENS_RUN>(d);
 #pragma unroll
                 for (int i = 1; i < ENS_RUN; ++i) col[(r * ENS_RUN + i) * T] = d[i];
@@ -309,7 +288,7 @@ __global__ void __launch_bounds__(ENS_LDS_FLOATS / MC) ensemble_lds_kernel(EnsGe
 #pragma unroll
             for (int r = 0; r < NR; ++r)
                 if (sel == r) row = r * ENS_RUN + ++pos[r];
-            const float fresh = (sel >= 0 && (row & (ENS_RUN - 1))) ? col[row * T] : ens_inf();      // (row % 32 == 0: the run is exhausted)
+            const float fresh = (sel >= 0 && (row & (ENS_RUN - 1))) ? col[row * T] : pos_inf();      // (row % 32 == 0: the run is exhausted)
 #pragma unroll
             for (int r = 0; r < NR; ++r)
                 if (sel == r) head[r] = fresh;
@@ -333,12 +312,6 @@ struct EnsPlan {
     int threads, per_lane;
     int64_t nblk;
 };
-
-dim3 ens_grid(int64_t n) {
-    if (n <= 0) return dim3(0, 0);                      // (a zero extent: reported by the plan query, never launched)
-    const int64_t gx = n < 65536 ? n : 65536;
-    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
-}
 
 // everything the descriptor decides: the class, whether extents and strides allow 16-byte loads
 int ens_plan(const dlwpcs_ensemble_desc *d, EnsPlan &P) {
@@ -390,13 +363,13 @@ int ens_settle(EnsPlan &P, const void *ens, const void *valid) {
     if (P.G.E > 0 && !ens) return fail(DLWPCS_E_INVALID, "ensemble_stats: null ensemble");
     if ((((uintptr_t)ens) | ((uintptr_t)valid)) & 3)
         return fail(DLWPCS_E_INVALID, "ensemble_stats: an operand is not aligned to its 4-byte elements");
-    P.vec = P.vec_ok && !(((uintptr_t)ens) & 15);
-    P.G.vmode = !valid ? -1 : (P.vec && P.vvec_ok && !(((uintptr_t)valid) & 15)) ? 1 : 0;
+    P.vec = P.vec_ok && aligned16(ens);
+    P.G.vmode = !valid ? -1 : (P.vec && P.vvec_ok && aligned16(valid)) ? 1 : 0;
     P.threads = P.lds ? ENS_LDS_FLOATS / P.cls : ENS_THREADS;
     P.per_lane = P.vec ? 4 : 1;
     const int64_t per_blk = (int64_t)P.threads * P.per_lane;
     P.nblk = (P.G.E + per_blk - 1) / per_blk;
-    if (P.nblk > 65536ll * 65535ll) return fail(DLWPCS_E_UNSUPPORTED, "ensemble_stats: %lld workgroups is too many", (long long)P.nblk);
+    if (P.nblk > MAX_BLOCKS) return fail(DLWPCS_E_UNSUPPORTED, "ensemble_stats: %lld workgroups is too many", (long long)P.nblk);
     return DLWPCS_OK;
 }
 
@@ -404,11 +377,11 @@ int ens_settle(EnsPlan &P, const void *ens, const void *valid) {
 // convolution case table), as for the other verification kernels.
 template <int MC, bool VEC>
 void ens_launch_reg(const EnsPlan &P, const float *ens, const float *valid, float *m, float *sp, float *c, int32_t *r, hipStream_t s) {
-    hipLaunchKernelGGL((ensemble_reg_kernel<MC, VEC>), ens_grid(P.nblk), dim3(ENS_THREADS), 0, s, P.G, ens, valid, m, sp, c, r);
+    hipLaunchKernelGGL((ensemble_reg_kernel<MC, VEC>), launch_grid(P.nblk), dim3(ENS_THREADS), 0, s, P.G, ens, valid, m, sp, c, r);
 }
 template <int MC>
 void ens_launch_lds(const EnsPlan &P, const float *ens, const float *valid, float *m, float *sp, float *c, int32_t *r, hipStream_t s) {
-    hipLaunchKernelGGL((ensemble_lds_kernel<MC>), ens_grid(P.nblk), dim3(ENS_LDS_FLOATS / MC), 0, s, P.G, ens, valid, m, sp, c, r);
+    hipLaunchKernelGGL((ensemble_lds_kernel<MC>), launch_grid(P.nblk), dim3(ENS_LDS_FLOATS / MC), 0, s, P.G, ens, valid, m, sp, c, r);
 }
 
 }  // namespace
@@ -453,7 +426,7 @@ extern "C" int dlwpcs_ensemble_plan_info(const dlwpcs_ensemble_desc *d, const vo
     if (rc != DLWPCS_OK) return rc;
     rc = ens_settle(P, ens, valid);
     if (rc != DLWPCS_OK) return rc;
-    const dim3 grid = ens_grid(P.nblk);
+    const dim3 grid = launch_grid(P.nblk);
     info[0] = P.cls;
     info[1] = P.vec ? 1 : 0;
     info[2] = P.G.vmode;

@@ -17,7 +17,7 @@
 // channels with 16-B loads (8 codes per lane, half a wave per channel row) and 16-B stores when the gathered channels are the whole
 // output row, and a channels-first form that needs no transpose.  The LDS tiles hold DECODED fp32 values, so the write-out loops
 // are the fp32 gather's.
-#include "common.h"
+#include "strided.h"
 #include <math.h>
 
 namespace dlwpcs {
@@ -30,16 +30,6 @@ constexpr int PK_TILE = PK_THREADS * PK_CHUNK;
 constexpr int RG_UNROLL = 4;                        // rows in flight per lane
 constexpr int64_t RG_TARGET_BLOCKS = 1024;          // 256 CUs x 4
 constexpr int PK_FILL = -32768;
-
-__device__ __forceinline__ int64_t flat_block() { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
-
-static dim3 grid_of(int64_t n) {
-    const int64_t gx = n < 65536 ? n : 65536;
-    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
-}
-constexpr int64_t MAX_BLOCKS = 65536ll * 65535ll;
-
-inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 
 // ---- element arithmetic ----------------------------------------------------------------------------------------------
 
@@ -446,8 +436,8 @@ extern "C" int dlwpcs_channel_range(const float *src, int64_t T, int64_t V, int6
     if (!scratch || scratch_bytes < need || (((uintptr_t)scratch) & 7))
         return fail(DLWPCS_E_WORKSPACE, "channel_range: scratch of %zu bytes, need %zu (8-byte aligned)", scratch_bytes, need);
     RangePart *partial = (RangePart *)scratch;
-    if (vec) hipLaunchKernelGGL(channel_range_kernel<true>, grid_of(G.nblk), blk, 0, s, G, src, partial);
-    else hipLaunchKernelGGL(channel_range_kernel<false>, grid_of(G.nblk), blk, 0, s, G, src, partial);
+    if (vec) hipLaunchKernelGGL(channel_range_kernel<true>, launch_grid(G.nblk), blk, 0, s, G, src, partial);
+    else hipLaunchKernelGGL(channel_range_kernel<false>, launch_grid(G.nblk), blk, 0, s, G, src, partial);
     hipLaunchKernelGGL(channel_range_finish_kernel, dim3((unsigned)V), blk, 0, s, G.units, (const RangePart *)partial, range,
                        nonfinite);
     return check_launch("channel_range");
@@ -461,7 +451,7 @@ extern "C" int dlwpcs_pack_i16(const float *src, int64_t T, int64_t V, int64_t S
     if (!src || !scale || !offset || !dst) return fail(DLWPCS_E_INVALID, "pack_i16: null operand");
     int64_t tiles, nblk;
     if (!rows_plan(T, V, S, tiles, nblk)) return fail(DLWPCS_E_UNSUPPORTED, "pack_i16: too many workgroups");
-    const dim3 grid = grid_of(nblk), blk(PK_THREADS);
+    const dim3 grid = launch_grid(nblk), blk(PK_THREADS);
     if (S % PK_CHUNK == 0 && aligned16(src) && aligned16(dst))
         hipLaunchKernelGGL(pack_i16_kernel<true>, grid, blk, 0, (hipStream_t)stream, nblk, tiles, V, S, src, scale, offset, dst);
     else
@@ -477,7 +467,7 @@ extern "C" int dlwpcs_unpack_i16(const int16_t *src, int64_t T, int64_t V, int64
     if (!src || !scale || !offset || !dst) return fail(DLWPCS_E_INVALID, "unpack_i16: null operand");
     int64_t tiles, nblk;
     if (!rows_plan(T, V, S, tiles, nblk)) return fail(DLWPCS_E_UNSUPPORTED, "unpack_i16: too many workgroups");
-    const dim3 grid = grid_of(nblk), blk(PK_THREADS);
+    const dim3 grid = launch_grid(nblk), blk(PK_THREADS);
     if (S % PK_CHUNK == 0 && aligned16(src) && aligned16(dst))
         hipLaunchKernelGGL(unpack_i16_kernel<true>, grid, blk, 0, (hipStream_t)stream, nblk, tiles, V, S, src, scale, offset, dst);
     else

@@ -19,7 +19,7 @@
 // No profiler tags: the launch profiler's registry is the convolution family's (tests/test_conv_coverage_tags.py closes it over the
 // convolution case table), as for the other verification kernels.
 #include <math.h>
-#include "common.h"
+#include "strided.h"
 
 namespace dlwpcs {
 
@@ -34,38 +34,16 @@ constexpr int QT_NCLASS = 4;
 constexpr QtClass QT_CLASSES[QT_NCLASS] = {{64, 256}, {128, 128}, {256, 64}, {640, 64}};
 
 struct QtGeom {
-    int32_t n_inner, n_probs;
-    int64_t ext[DLWPCS_SCORE_MAX_DIMS];
-    int64_t sst[DLWPCS_SCORE_MAX_DIMS];
-    int64_t ost[DLWPCS_SCORE_MAX_DIMS];
-    int64_t src_row_stride, out_row_stride, out_prob_stride;
-    int64_t ncol;                                   // elements per row
-    int64_t tiles;                                  // column tiles of a workgroup's lanes
-    int64_t nblk;
+    RowsAddr A;                                     // chunks of one element
+    int32_t n_probs;
+    int64_t out_prob_stride;
     double p[QT_MAXP];                              // unused slots: 0
 };
 
-__device__ __forceinline__ int64_t qt_flat_block() { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
-
+// element q of a row -> offsets in the source and in the output; every extent fits 31 bits when ncol does: 32-bit index arithmetic
 __device__ __forceinline__ void qt_offsets(const QtGeom &G, int64_t q, int64_t &soff, int64_t &ooff) {
-    soff = 0;
-    ooff = 0;
-    if (G.ncol < (1ll << 31)) {                         // every extent fits 31 bits: 32-bit index arithmetic
-        uint32_t r = (uint32_t)q;
-        for (int d = G.n_inner - 1; d >= 0; --d) {
-            const uint32_t e = (uint32_t)G.ext[d], c = r % e;
-            r /= e;
-            soff += (int64_t)c * G.sst[d];
-            ooff += (int64_t)c * G.ost[d];
-        }
-        return;
-    }
-    for (int d = G.n_inner - 1; d >= 0; --d) {
-        const int64_t e = G.ext[d], c = q % e;
-        q /= e;
-        soff += c * G.sst[d];
-        ooff += c * G.ost[d];
-    }
+    if (G.A.ncol < (1ll << 31)) rows_offsets<1, true>(G.A, q, soff, ooff);
+    else rows_offsets<1, false>(G.A, q, soff, ooff);
 }
 
 // Every NaN goes to QT_NO_KEY, the key of no value (it would be that of the NaN 0x7fffffff): it sorts behind every member, is
@@ -107,7 +85,7 @@ __device__ __forceinline__ void qt_select(const QtGeom &G, const Column &c, int3
 #pragma clang fp contract(off)
     if (count) count[off] = n;
     if (n == 0) {
-        for (int q = 0; q < G.n_probs; ++q) out[q * G.out_prob_stride + off] = __uint_as_float(0x7fc00000u);
+        for (int q = 0; q < G.n_probs; ++q) out[q * G.out_prob_stride + off] = quiet_nan();
         return;
     }
     const int32_t len = c.size();
@@ -167,7 +145,7 @@ __device__ __forceinline__ void qt_select(const QtGeom &G, const Column &c, int3
                 v = xj + g * (xj1 - xj);
             }
             const float r = (float)v;
-            out[q * G.out_prob_stride + off] = r != r ? __uint_as_float(0x7fc00000u) : r;
+            out[q * G.out_prob_stride + off] = r != r ? quiet_nan() : r;
         }
 }
 
@@ -177,11 +155,11 @@ __global__ void __launch_bounds__(LANES) quantile_staged_kernel(QtGeom G, const 
                                                                 const int32_t *__restrict__ row_index, float *__restrict__ out,
                                                                 int32_t *__restrict__ count) {
     __shared__ uint32_t s_keys[ROWS * LANES];
-    const int64_t bid = qt_flat_block();
-    if (bid >= G.nblk) return;
-    const int64_t k = bid / G.tiles;
-    const int64_t e = (bid - k * G.tiles) * LANES + threadIdx.x;
-    if (e >= G.ncol) return;                            // (no barrier anywhere: a column belongs to its lane)
+    const int64_t bid = flat_block();
+    if (bid >= G.A.nblk) return;
+    const int64_t k = bid / G.A.tiles;
+    const int64_t e = (bid - k * G.A.tiles) * LANES + threadIdx.x;
+    if (e >= G.A.ncol) return;                            // (no barrier anywhere: a column belongs to its lane)
     const int32_t g0 = group_start[k];
     int32_t g1 = group_start[k + 1];
     if (g1 - g0 > ROWS) g1 = g0 + ROWS;                 // (max_group_rows chose the class: rows beyond it are not read)
@@ -194,7 +172,7 @@ __global__ void __launch_bounds__(LANES) quantile_staged_kernel(QtGeom G, const 
         uint32_t u[QT_UNROLL];
 #pragma unroll
         for (int t = 0; t < QT_UNROLL; ++t)
-            u[t] = j + t < g1 ? __float_as_uint(p[(int64_t)row_index[j + t] * G.src_row_stride]) : 0x7fc00000u;
+            u[t] = j + t < g1 ? __float_as_uint(p[(int64_t)row_index[j + t] * G.A.src_row_stride]) : 0x7fc00000u;
 #pragma unroll
         for (int t = 0; t < QT_UNROLL; ++t) {
             const uint32_t key = qt_key(u[t]);
@@ -205,7 +183,7 @@ __global__ void __launch_bounds__(LANES) quantile_staged_kernel(QtGeom G, const 
         }
     }
     const QtLdsColumn<LANES> c = {col, n};
-    qt_select<NP>(G, c, n, out, count, k * G.out_row_stride + ooff);
+    qt_select<NP>(G, c, n, out, count, k * G.A.out_row_stride + ooff);
 }
 
 template <int NP>
@@ -213,25 +191,19 @@ __global__ void __launch_bounds__(QT_LONG_THREADS) quantile_long_kernel(QtGeom G
                                                                         const int32_t *__restrict__ group_start,
                                                                         const int32_t *__restrict__ row_index,
                                                                         float *__restrict__ out, int32_t *__restrict__ count) {
-    const int64_t bid = qt_flat_block();
-    if (bid >= G.nblk) return;
-    const int64_t k = bid / G.tiles;
-    const int64_t e = (bid - k * G.tiles) * QT_LONG_THREADS + threadIdx.x;
-    if (e >= G.ncol) return;
+    const int64_t bid = flat_block();
+    if (bid >= G.A.nblk) return;
+    const int64_t k = bid / G.A.tiles;
+    const int64_t e = (bid - k * G.A.tiles) * QT_LONG_THREADS + threadIdx.x;
+    if (e >= G.A.ncol) return;
     const int32_t g0 = group_start[k], g1 = group_start[k + 1];
     int64_t soff, ooff;
     qt_offsets(G, e, soff, ooff);
-    const QtMemColumn c = {src + soff, row_index + g0, G.src_row_stride, g1 - g0};
+    const QtMemColumn c = {src + soff, row_index + g0, G.A.src_row_stride, g1 - g0};
     int32_t n = 0;
 #pragma unroll QtMemColumn::UNROLL
     for (int32_t i = 0; i < c.len; ++i) n += c.get(i) != QT_NO_KEY ? 1 : 0;
-    qt_select<NP>(G, c, n, out, count, k * G.out_row_stride + ooff);
-}
-
-dim3 qt_grid(int64_t n) {
-    if (n <= 0) return dim3(0, 0);                      // (a zero extent: reported by the plan query, never launched)
-    const int64_t gx = n < 65536 ? n : 65536;
-    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
+    qt_select<NP>(G, c, n, out, count, k * G.A.out_row_stride + ooff);
 }
 
 struct QtPlan {
@@ -243,42 +215,30 @@ struct QtPlan {
 };
 
 int qt_plan(const dlwpcs_rows_desc *d, int n_groups, int64_t max_group_rows, int n_probs, QtPlan &P) {
-    if (!d) return fail(DLWPCS_E_INVALID, "group_quantile: null descriptor");
-    if (d->n_inner < 0 || d->n_inner > DLWPCS_SCORE_MAX_DIMS)
-        return fail(DLWPCS_E_INVALID, "group_quantile: n_inner %d out of range", d->n_inner);
+    QtGeom &G = P.G;
+    memset(&G, 0, sizeof(G));
+    const int rc = rows_addr_init(d, "group_quantile", G.A, P.inner);
+    if (rc != DLWPCS_OK) return rc;
     if (n_groups < 0 || max_group_rows < 0) return fail(DLWPCS_E_INVALID, "group_quantile: negative group / row count");
     if (n_probs < 1 || n_probs > QT_MAXP)
         return fail(DLWPCS_E_INVALID, "group_quantile: %d probabilities (1 .. %d)", n_probs, QT_MAXP);
     if (max_group_rows >= (1ll << 31)) return fail(DLWPCS_E_INVALID, "group_quantile: a group of %lld rows", (long long)max_group_rows);
-    QtGeom &G = P.G;
-    memset(&G, 0, sizeof(G));
-    G.n_inner = d->n_inner;
     G.n_probs = n_probs;
-    G.src_row_stride = d->src_row_stride;
-    G.out_row_stride = d->out_row_stride;
-    P.inner = 1;
-    for (int i = 0; i < d->n_inner; ++i) {
-        if (d->inner_ext[i] < 0) return fail(DLWPCS_E_INVALID, "group_quantile: inner extent %lld", (long long)d->inner_ext[i]);
-        G.ext[i] = d->inner_ext[i];
-        G.sst[i] = d->src_stride[i];
-        G.ost[i] = d->out_stride[i];
-        P.inner *= d->inner_ext[i];
-    }
     P.cls = QT_NCLASS;
     for (int c = QT_NCLASS - 1; c >= 0; --c)
         if (max_group_rows <= QT_CLASSES[c].rows) P.cls = c;
     P.np_class = n_probs <= 1 ? 1 : n_probs <= 2 ? 2 : n_probs <= 4 ? 4 : n_probs <= 8 ? 8 : 16;
     P.lanes = P.cls < QT_NCLASS ? QT_CLASSES[P.cls].lanes : QT_LONG_THREADS;
-    G.ncol = P.inner;
-    G.tiles = (G.ncol + P.lanes - 1) / P.lanes;
-    G.nblk = (int64_t)n_groups * G.tiles;
-    if (G.nblk > 65536ll * 65535ll) return fail(DLWPCS_E_INVALID, "group_quantile: %lld workgroups is too many", (long long)G.nblk);
+    G.A.ncol = P.inner;
+    G.A.tiles = (G.A.ncol + P.lanes - 1) / P.lanes;
+    G.A.nblk = (int64_t)n_groups * G.A.tiles;
+    if (G.A.nblk > MAX_BLOCKS) return fail(DLWPCS_E_INVALID, "group_quantile: %lld workgroups is too many", (long long)G.A.nblk);
     return DLWPCS_OK;
 }
 
 template <int NP>
 void qt_launch(const QtPlan &P, const float *src, const int32_t *gs, const int32_t *ri, float *out, int32_t *count, hipStream_t s) {
-    const dim3 grid = qt_grid(P.G.nblk);
+    const dim3 grid = launch_grid(P.G.A.nblk);
     switch (P.cls) {
     case 0: hipLaunchKernelGGL((quantile_staged_kernel<64, 256, NP>), grid, dim3(256), 0, s, P.G, src, gs, ri, out, count); break;
     case 1: hipLaunchKernelGGL((quantile_staged_kernel<128, 128, NP>), grid, dim3(128), 0, s, P.G, src, gs, ri, out, count); break;
@@ -330,7 +290,7 @@ extern "C" int dlwpcs_group_quantile_plan_info(const dlwpcs_rows_desc *d, const 
     if (rc != DLWPCS_OK) return rc;
     if (n_groups > 0 && P.inner > 0 && !src) return fail(DLWPCS_E_INVALID, "group_quantile: null operand");
     const bool staged = P.cls < QT_NCLASS;
-    const dim3 grid = qt_grid(P.inner > 0 ? P.G.nblk : 0);
+    const dim3 grid = launch_grid(P.inner > 0 ? P.G.A.nblk : 0);
     info[0] = staged ? 0 : 1;
     info[1] = staged ? QT_CLASSES[P.cls].rows : 0;
     info[2] = P.lanes;

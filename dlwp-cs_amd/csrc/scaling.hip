@@ -15,7 +15,7 @@
 // flat: both sides one channels-last stream, 16-byte loads and stores over it, channel = flat index mod C carried incrementally,
 // tables in LDS.  any: one element per lane, lanes along the destination's contiguous dim; with lanes along s a workgroup loops
 // over the channels itself, so a channels-last source is fetched from HBM once and re-read from the cache.
-#include "common.h"
+#include "strided.h"
 
 namespace dlwpcs {
 
@@ -27,14 +27,6 @@ constexpr int CM_UNROLL = 8;                    // rows in flight per lane
 constexpr int64_t CM_TARGET_BLOCKS = 512;       // 256 CUs x 2
 constexpr int CA_THREADS = 256;
 constexpr int CA_UNROLL = 4;                    // 16-byte chunks per lane
-
-__device__ __forceinline__ int64_t flat_block() { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
-
-static dim3 grid_of(int64_t n) {
-    const int64_t gx = n < 65536 ? n : 65536;
-    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
-}
-constexpr int64_t MAX_BLOCKS = 65536ll * 65535ll;
 
 // ---- moments ---------------------------------------------------------------------------------------------------------
 
@@ -320,7 +312,6 @@ __global__ void __launch_bounds__(CA_THREADS) channel_affine_any_kernel(AffGeom 
     }
 }
 
-inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace
 
@@ -368,7 +359,7 @@ extern "C" int dlwpcs_channel_moments(const dlwpcs_chan_desc *d, const float *sr
     if (!scratch || scratch_bytes < need || (((uintptr_t)scratch) & 7))
         return fail(DLWPCS_E_WORKSPACE, "channel_moments: scratch of %zu bytes, need %zu (8-byte aligned)", scratch_bytes, need);
     double *partial = (double *)scratch;
-    const dim3 grid = grid_of(G.nblk), blk(CM_THREADS);
+    const dim3 grid = launch_grid(G.nblk), blk(CM_THREADS);
 #define CM_LAUNCH(VEC, SKIP) \
     hipLaunchKernelGGL((channel_moments_kernel<VEC, SKIP>), grid, blk, 0, s, G, src, rows, center, partial)
     if (vec) { if (skipna) CM_LAUNCH(true, true); else CM_LAUNCH(true, false); }
@@ -424,6 +415,6 @@ extern "C" int dlwpcs_channel_affine(const dlwpcs_chan_desc *d, const float *src
         kernel = mul ? channel_affine_any_kernel<DLWPCS_AFFINE_MUL_ADD, false> : channel_affine_any_kernel<DLWPCS_AFFINE_SUB_DIV, false>;
     }
     if (G.nblk > MAX_BLOCKS) return fail(DLWPCS_E_UNSUPPORTED, "channel_affine: %lld workgroups is too many", (long long)G.nblk);
-    hipLaunchKernelGGL(kernel, grid_of(G.nblk), dim3(CA_THREADS), 0, (hipStream_t)stream, G, src, a, b, dst);
+    hipLaunchKernelGGL(kernel, launch_grid(G.nblk), dim3(CA_THREADS), 0, (hipStream_t)stream, G, src, a, b, dst);
     return check_launch("channel_affine");
 }

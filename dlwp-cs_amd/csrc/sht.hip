@@ -29,6 +29,7 @@
 // stands below.  The vector forms (dlwpcs_sht_vector_synthesis, dlwpcs_sht_vector_analysis) are the same two products with four
 // accumulators against the derivative and zonal tables, and the barotropic model's two streaming kernels close the file.
 #include "mfma_common.h"
+#include "strided.h"
 
 namespace dlwpcs {
 
@@ -44,7 +45,6 @@ constexpr int SH_KV = 4;                    // stage B: 16-byte loads of a lane 
 constexpr int SH_MC = 8;                    // coefficient kernel: orders per workgroup
 constexpr int SH_JT = 4 * SH_TILE;          // inverse Fourier: longitudes per workgroup (32 per wave)
 constexpr int SH_KU = 4;                    // inverse stages: MFMAs per accumulator whose operands are loaded together
-constexpr int64_t SH_MAX_GRID = 65536ll * 65535ll;
 
 struct ShGeom {
     int32_t nlat, nlp, L, T, n_dims, n_mt, n_nt;
@@ -55,8 +55,6 @@ struct ShGeom {
     int64_t ext[DLWPCS_SCORE_MAX_DIMS];
     int64_t stride[2][DLWPCS_SCORE_MAX_DIMS];
 };
-
-__device__ __forceinline__ bool sh_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
 // the three fp32 products of the pair form (q = 0 alone in the single form), spelled once so that both forms round alike
 __device__ __forceinline__ float sh_product(int q, float cf, float sf, float cv, float sv) {
@@ -83,7 +81,7 @@ __global__ void __launch_bounds__(SH_THREADS) sht_fourier_kernel(ShGeom G, const
     __shared__ int64_t s_flag[SH_ROWS];
     __shared__ int s_valid[SH_ROWS], s_bad[SH_ROWS];
 
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t bid = flat_block();
     if (bid >= G.n_rt * G.n_mt) return;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int mt = (int)(bid % G.n_mt);
@@ -168,7 +166,7 @@ __global__ void __launch_bounds__(SH_THREADS) sht_fourier_kernel(ShGeom G, const
 #pragma unroll
                 for (int e = 0; e < (VEC ? 4 : 1); ++e) {
                     v[e] = regs[op][i][e];              // (zero outside the row: fetch has seen to it)
-                    if (sh_nonfinite(v[e])) bad_mask |= 1u << i;
+                    if (nonfinite(v[e])) bad_mask |= 1u << i;
                 }
                 float *dst = &s_x[op][ld_row[i] * SH_XS + ld_col[i]];
                 if constexpr (VEC) {
@@ -308,7 +306,7 @@ __global__ void __launch_bounds__(64) sht_legendre_kernel(ShGeom G, const float 
                                                           int32_t *__restrict__ skipped) {
     constexpr int NOP = PAIR ? 2 : 1;
     constexpr int NQ = PAIR ? 3 : 1;
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t bid = flat_block();
     if (bid >= G.n_ft * G.n_nt) return;
     const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
     const int nt = (int)(bid % G.n_nt);
@@ -370,7 +368,7 @@ __device__ __forceinline__ float sh_div_l(float v, double L) { return (float)((d
 __global__ void __launch_bounds__(64) sht_coef_kernel(ShGeom G, const float *__restrict__ xs, const int32_t *__restrict__ bad,
                                                       const float *__restrict__ table, float2 *__restrict__ coef,
                                                       int32_t *__restrict__ skipped) {
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t bid = flat_block();
     if (bid >= G.n_ft * G.n_nt * G.n_mc) return;
     const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
     const int mc = (int)(bid % G.n_mc);
@@ -423,7 +421,7 @@ __global__ void __launch_bounds__(64) sht_coef_kernel(ShGeom G, const float *__r
 // The grid is (field tiles) x (latitude tiles) x (orders): no wave walks the orders, the longest chain is T + 1 degrees.
 __global__ void __launch_bounds__(64) sht_ilegendre_kernel(ShGeom G, const float2 *__restrict__ coef, const float *__restrict__ response,
                                                            const float *__restrict__ ptable, float *__restrict__ gs) {
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t bid = flat_block();
     const int T = G.T, K = T + 1, nlat = G.nlat, nlp = G.nlp;
     if (bid >= G.n_ft * G.n_lt * K) return;
     const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
@@ -504,7 +502,7 @@ __global__ void __launch_bounds__(SH_THREADS) sht_ifourier_kernel(ShGeom G, cons
     __shared__ int64_t s_line[SH_ROWS];                 // gs offset of (field, m = 0, re, latitude) of the slot's row
     __shared__ int s_valid[SH_ROWS];
 
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t bid = flat_block();
     if (bid >= G.n_rt * G.n_jt) return;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int jt = (int)(bid % G.n_jt);
@@ -601,7 +599,7 @@ __global__ void __launch_bounds__(64) sht_vilegendre_kernel(ShGeom G, const floa
                                                             const float *__restrict__ rpsi, const float *__restrict__ rchi,
                                                             const float *__restrict__ dtable, const float *__restrict__ qtable,
                                                             float *__restrict__ gs) {
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t bid = flat_block();
     const int T = G.T, K = T + 1, nlat = G.nlat, nlp = G.nlp;
     if (bid >= G.n_ft * G.n_lt * K) return;
     const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
@@ -712,7 +710,7 @@ __global__ void __launch_bounds__(64) sht_vcoef_kernel(ShGeom G, const float *__
                                                        const float *__restrict__ response, const float *__restrict__ wdtable,
                                                        const float *__restrict__ wqtable, float2 *__restrict__ vrt,
                                                        float2 *__restrict__ dvg, int32_t *__restrict__ skipped) {
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t bid = flat_block();
     if (bid >= G.n_ft * G.n_nt * G.n_mc) return;
     const int lane = (int)threadIdx.x, r32 = lane & 31, h = lane >> 5;
     const int mc = (int)(bid % G.n_mc);
@@ -829,7 +827,7 @@ __global__ void __launch_bounds__(256) barotropic_flux_kernel(int64_t n, int32_t
                                                               const float *__restrict__ zeta, const float *__restrict__ u,
                                                               const float *__restrict__ v, float *__restrict__ F, float *__restrict__ Gv) {
 #pragma clang fp contract(off)
-    const int64_t t = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+    const int64_t t = flat_block() * 256 + threadIdx.x;
     const int64_t e = VEC ? 4 * t : t;
     if (e >= n) return;
     const float f = coriolis[(e / L) % nlat];
@@ -872,7 +870,7 @@ template <bool VEC>
 __global__ void __launch_bounds__(256) barotropic_update_kernel(int64_t n, int64_t rows, const float *__restrict__ damp, float dt, float rc,
                                                                 int first, const float *__restrict__ tend, float *__restrict__ zeta,
                                                                 float *__restrict__ zeta_prev) {
-    const int64_t t = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;     // n floats = 2 * fields * rows
+    const int64_t t = flat_block() * 256 + threadIdx.x;     // n floats = 2 * fields * rows
     const int64_t e = VEC ? 4 * t : 2 * t;
     if (e >= n) return;
     if constexpr (VEC) {
@@ -948,15 +946,10 @@ int sh_plan(const dlwpcs_sht_spectrum_desc *d, bool pair, ShPlan &P, const char 
     G.n_mc = (G.T + 1 + SH_MC - 1) / SH_MC;
     G.n_lt = (G.nlat + SH_TILE - 1) / SH_TILE;
     G.n_jt = (G.L + SH_JT - 1) / SH_JT;
-    if (G.n_rt * G.n_mt > SH_MAX_GRID) return fail(DLWPCS_E_UNSUPPORTED, "%s: too many workgroups", who);
+    if (G.n_rt * G.n_mt > MAX_BLOCKS) return fail(DLWPCS_E_UNSUPPORTED, "%s: too many workgroups", who);
     P.xs_bytes = (size_t)G.op_stride * sizeof(float) * (pair ? 2 : 1);
     P.bad_bytes = (size_t)G.rows * sizeof(int32_t);
     return DLWPCS_OK;
-}
-
-dim3 sh_grid(int64_t n) {
-    const int64_t gx = n < 65536 ? n : 65536;
-    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
 }
 
 }  // namespace
@@ -992,7 +985,7 @@ extern "C" int dlwpcs_sht_spectrum(const dlwpcs_sht_spectrum_desc *d, const floa
     int32_t *bad = (int32_t *)((char *)scratch + P.xs_bytes);
     const bool vec = P.vec_ok && !((((uintptr_t)a) | ((uintptr_t)b)) & 15);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid_a = sh_grid(G.n_rt * G.n_mt), grid_b = sh_grid(G.n_ft * G.n_nt);
+    const dim3 grid_a = launch_grid(G.n_rt * G.n_mt), grid_b = launch_grid(G.n_ft * G.n_nt);
     const float2 *tw = (const float2 *)twiddle;
 #define SH_LAUNCH_A(PAIR, VEC) \
     hipLaunchKernelGGL((sht_fourier_kernel<PAIR, VEC>), grid_a, dim3(SH_THREADS), 0, s, G, a, b, tw, xs, bad)
@@ -1016,7 +1009,7 @@ extern "C" int dlwpcs_sht_analysis(const dlwpcs_sht_spectrum_desc *d, const floa
     const int rc = sh_plan(d, false, P, "sht_analysis");
     if (rc != DLWPCS_OK) return rc;
     const ShGeom &G = P.G;
-    if (G.n_ft * G.n_nt * G.n_mc > SH_MAX_GRID) return fail(DLWPCS_E_UNSUPPORTED, "sht_analysis: too many workgroups");
+    if (G.n_ft * G.n_nt * G.n_mc > MAX_BLOCKS) return fail(DLWPCS_E_UNSUPPORTED, "sht_analysis: too many workgroups");
     if (!twiddle || !legendre) return fail(DLWPCS_E_INVALID, "sht_analysis: null twiddle or Legendre table");
     if (((uintptr_t)twiddle) & 7) return fail(DLWPCS_E_INVALID, "sht_analysis: the twiddle table is not aligned to 8 bytes");
     if (((uintptr_t)legendre) & 15) return fail(DLWPCS_E_INVALID, "sht_analysis: the Legendre table is not aligned to 16 bytes");
@@ -1031,7 +1024,7 @@ extern "C" int dlwpcs_sht_analysis(const dlwpcs_sht_spectrum_desc *d, const floa
     int32_t *bad = (int32_t *)((char *)scratch + P.xs_bytes);
     const bool vec = P.vec_ok && !(((uintptr_t)a) & 15);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid_a = sh_grid(G.n_rt * G.n_mt), grid_b = sh_grid(G.n_ft * G.n_nt * G.n_mc);
+    const dim3 grid_a = launch_grid(G.n_rt * G.n_mt), grid_b = launch_grid(G.n_ft * G.n_nt * G.n_mc);
     const float2 *tw = (const float2 *)twiddle;
     const float *none = nullptr;
     if (vec) hipLaunchKernelGGL((sht_fourier_kernel<false, true>), grid_a, dim3(SH_THREADS), 0, s, G, a, none, tw, xs, bad);
@@ -1059,7 +1052,7 @@ int sh_synthesis_plan(const dlwpcs_sht_synthesis_desc *d, ShPlan &P) {
     const int rc = sh_plan(&sd, false, P, "sht_synthesis");
     if (rc != DLWPCS_OK) return rc;
     const ShGeom &G = P.G;
-    if (G.n_ft * G.n_lt * (G.T + 1) > SH_MAX_GRID || G.n_rt * G.n_jt > SH_MAX_GRID)
+    if (G.n_ft * G.n_lt * (G.T + 1) > MAX_BLOCKS || G.n_rt * G.n_jt > MAX_BLOCKS)
         return fail(DLWPCS_E_UNSUPPORTED, "sht_synthesis: too many workgroups");
     return DLWPCS_OK;
 }
@@ -1092,7 +1085,7 @@ extern "C" int dlwpcs_sht_synthesis(const dlwpcs_sht_synthesis_desc *d, const fl
     float *gs = (float *)scratch;
     const bool vec = P.vec_ok && !(((uintptr_t)out) & 15);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid_l = sh_grid(G.n_ft * G.n_lt * (G.T + 1)), grid_f = sh_grid(G.n_rt * G.n_jt);
+    const dim3 grid_l = launch_grid(G.n_ft * G.n_lt * (G.T + 1)), grid_f = launch_grid(G.n_rt * G.n_jt);
     const float2 *tw = (const float2 *)twiddle;
     hipLaunchKernelGGL(sht_ilegendre_kernel, grid_l, dim3(64), 0, s, G, (const float2 *)coef, response, legendre, gs);
     if (vec) hipLaunchKernelGGL((sht_ifourier_kernel<true>), grid_f, dim3(SH_THREADS), 0, s, G, (const float *)gs, tw, out);
@@ -1115,7 +1108,7 @@ extern "C" int dlwpcs_sht_vector_synthesis(const dlwpcs_sht_spectrum_desc *d, co
     const int rc = sh_plan(d, true, P, who);
     if (rc != DLWPCS_OK) return rc;
     const ShGeom &G = P.G;
-    if (G.n_ft * G.n_lt * (G.T + 1) > SH_MAX_GRID || G.n_rt * G.n_jt > SH_MAX_GRID)
+    if (G.n_ft * G.n_lt * (G.T + 1) > MAX_BLOCKS || G.n_rt * G.n_jt > MAX_BLOCKS)
         return fail(DLWPCS_E_UNSUPPORTED, "%s: too many workgroups", who);
     if (!twiddle || !dtable || !qtable) return fail(DLWPCS_E_INVALID, "%s: null twiddle, derivative or zonal table", who);
     if (((uintptr_t)twiddle) & 7) return fail(DLWPCS_E_INVALID, "%s: the twiddle table is not aligned to 8 bytes", who);
@@ -1131,7 +1124,7 @@ extern "C" int dlwpcs_sht_vector_synthesis(const dlwpcs_sht_spectrum_desc *d, co
         return fail(DLWPCS_E_INVALID, "%s: this descriptor needs a 16-byte aligned scratch of %zu bytes", who, P.xs_bytes);
     float *gs = (float *)scratch;
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid_l = sh_grid(G.n_ft * G.n_lt * (G.T + 1)), grid_f = sh_grid(G.n_rt * G.n_jt);
+    const dim3 grid_l = launch_grid(G.n_ft * G.n_lt * (G.T + 1)), grid_f = launch_grid(G.n_rt * G.n_jt);
     const float2 *tw = (const float2 *)twiddle, *ca = (const float2 *)coef_a, *cb = (const float2 *)coef_b;
     if (ca && cb) hipLaunchKernelGGL((sht_vilegendre_kernel<true, true>), grid_l, dim3(64), 0, s, G, ca, cb, rpsi, rchi, dtable, qtable, gs);
     else if (ca) hipLaunchKernelGGL((sht_vilegendre_kernel<true, false>), grid_l, dim3(64), 0, s, G, ca, cb, rpsi, rchi, dtable, qtable, gs);
@@ -1164,7 +1157,7 @@ extern "C" int dlwpcs_sht_vector_analysis(const dlwpcs_sht_spectrum_desc *d, con
     const int rc = sh_plan(d, true, P, who);
     if (rc != DLWPCS_OK) return rc;
     const ShGeom &G = P.G;
-    if (G.n_ft * G.n_nt * G.n_mc > SH_MAX_GRID) return fail(DLWPCS_E_UNSUPPORTED, "%s: too many workgroups", who);
+    if (G.n_ft * G.n_nt * G.n_mc > MAX_BLOCKS) return fail(DLWPCS_E_UNSUPPORTED, "%s: too many workgroups", who);
     if (!twiddle || !wdtable || !wqtable) return fail(DLWPCS_E_INVALID, "%s: null twiddle, derivative or zonal table", who);
     if (((uintptr_t)twiddle) & 7) return fail(DLWPCS_E_INVALID, "%s: the twiddle table is not aligned to 8 bytes", who);
     if ((((uintptr_t)wdtable) | ((uintptr_t)wqtable)) & 15) return fail(DLWPCS_E_INVALID, "%s: a table is not aligned to 16 bytes", who);
@@ -1181,7 +1174,7 @@ extern "C" int dlwpcs_sht_vector_analysis(const dlwpcs_sht_spectrum_desc *d, con
     int32_t *bad = (int32_t *)((char *)scratch + P.xs_bytes);
     const bool vec = P.vec_ok && !((((uintptr_t)u) | ((uintptr_t)v)) & 15);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid_a = sh_grid(G.n_rt * G.n_mt), grid_b = sh_grid(G.n_ft * G.n_nt * G.n_mc);
+    const dim3 grid_a = launch_grid(G.n_rt * G.n_mt), grid_b = launch_grid(G.n_ft * G.n_nt * G.n_mc);
     const float2 *tw = (const float2 *)twiddle;
     if (vec) hipLaunchKernelGGL((sht_fourier_kernel<true, true>), grid_a, dim3(SH_THREADS), 0, s, G, u, v, tw, xs, bad);
     else hipLaunchKernelGGL((sht_fourier_kernel<true, false>), grid_a, dim3(SH_THREADS), 0, s, G, u, v, tw, xs, bad);
@@ -1206,8 +1199,8 @@ extern "C" int dlwpcs_barotropic_flux(int64_t fields, int32_t nlat, int32_t L, c
     const bool vec = L % 4 == 0 && !((((uintptr_t)zeta) | ((uintptr_t)u) | ((uintptr_t)v) | ((uintptr_t)F) | ((uintptr_t)G)) & 15);
     hipStream_t s = (hipStream_t)stream;
     const int64_t threads = vec ? n / 4 : n;
-    if ((threads + 255) / 256 > SH_MAX_GRID) return fail(DLWPCS_E_UNSUPPORTED, "barotropic_flux: too many workgroups");
-    const dim3 grid = sh_grid((threads + 255) / 256);
+    if ((threads + 255) / 256 > MAX_BLOCKS) return fail(DLWPCS_E_UNSUPPORTED, "barotropic_flux: too many workgroups");
+    const dim3 grid = launch_grid((threads + 255) / 256);
     if (vec) hipLaunchKernelGGL((barotropic_flux_kernel<true>), grid, dim3(256), 0, s, n, nlat, L, coriolis, zeta, u, v, F, G);
     else hipLaunchKernelGGL((barotropic_flux_kernel<false>), grid, dim3(256), 0, s, n, nlat, L, coriolis, zeta, u, v, F, G);
     return check_launch("barotropic_flux");
@@ -1229,8 +1222,8 @@ extern "C" int dlwpcs_barotropic_update(int64_t fields, int64_t rows, const floa
     const bool vec = n % 4 == 0 && !(all & 15);
     hipStream_t s = (hipStream_t)stream;
     const int64_t threads = vec ? n / 4 : n / 2;                       // (n < 2^63: both factors are below 2^31)
-    if ((threads + 255) / 256 > SH_MAX_GRID) return fail(DLWPCS_E_UNSUPPORTED, "barotropic_update: too many workgroups");
-    const dim3 grid = sh_grid((threads + 255) / 256);
+    if ((threads + 255) / 256 > MAX_BLOCKS) return fail(DLWPCS_E_UNSUPPORTED, "barotropic_update: too many workgroups");
+    const dim3 grid = launch_grid((threads + 255) / 256);
     if (vec) hipLaunchKernelGGL((barotropic_update_kernel<true>), grid, dim3(256), 0, s, n, rows, damp, dt, robert, (int)first_step, tend, zeta, zeta_prev);
     else hipLaunchKernelGGL((barotropic_update_kernel<false>), grid, dim3(256), 0, s, n, rows, damp, dt, robert, (int)first_step, tend, zeta, zeta_prev);
     return check_launch("barotropic_update");

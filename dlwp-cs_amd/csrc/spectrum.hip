@@ -20,6 +20,7 @@
 // remove_mean: a first pass over the tile's rows sums each row in fp64 (lane j mod 64, then a fixed butterfly), the mean rounded
 // to fp32 is subtracted as the row is staged, and k = 0 reports the fp64 mean squared (pair: the products of the two means).
 #include "mfma_common.h"
+#include "strided.h"
 
 namespace dlwpcs {
 
@@ -47,8 +48,6 @@ struct ZsGeom {
     int64_t keep_ext[DLWPCS_SCORE_MAX_DIMS], avg_ext[DLWPCS_SCORE_MAX_DIMS];
     int64_t keep_stride[3][DLWPCS_SCORE_MAX_DIMS], avg_stride[3][DLWPCS_SCORE_MAX_DIMS];
 };
-
-__device__ __forceinline__ bool zs_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
 // the four fp32 products of the pair form (q = 0 alone in the single form), spelled once so that every instantiation rounds alike
 __device__ __forceinline__ float zs_product(int q, float cf, float sf, float cv, float sv) {
@@ -82,7 +81,7 @@ __global__ void __launch_bounds__(ZS_THREADS) zonal_spectrum_kernel(ZsGeom G, co
     __shared__ float s_w[ZS_ROWS];
     __shared__ int s_valid[ZS_ROWS], s_bad[ZS_ROWS];
 
-    const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t bid = flat_block();
     if (bid >= G.nblk) return;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int kt = (int)(bid % G.n_kt);
@@ -212,7 +211,7 @@ __global__ void __launch_bounds__(ZS_THREADS) zonal_spectrum_kernel(ZsGeom G, co
 #pragma unroll
                     for (int e = 0; e < (VEC ? 4 : 1); ++e) {
                         const float x = regs[op][i][e];
-                        if (zs_nonfinite(x)) bad_mask |= 1u << i;
+                        if (nonfinite(x)) bad_mask |= 1u << i;
                         v[e] = in ? x - ld_mu[op][i] : 0.f;
                     }
                     float *dst = &s_x[op][ld_row[i] * ZS_XS + ld_col[i]];
@@ -353,7 +352,7 @@ __global__ void __launch_bounds__(256) zonal_spectrum_finish_kernel(const double
                                                                     const int32_t *__restrict__ part_skip, int64_t groups, int K,
                                                                     int nq, int slabs, float *__restrict__ out,
                                                                     int32_t *__restrict__ skipped) {
-    const int64_t i = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+    const int64_t i = flat_block() * 256 + threadIdx.x;
     if (i >= (int64_t)nq * groups * K) return;
     const int k = (int)(i % K);
     const int64_t g = (i / K) % groups;
@@ -443,7 +442,7 @@ int zs_plan(const dlwpcs_zonal_spectrum_desc *d, bool pair, ZsPlan &P) {
         }
     }
     G.nblk = G.n_gt * G.slabs * G.n_kt;
-    if (G.nblk > 65536ll * 65535ll) return fail(DLWPCS_E_UNSUPPORTED, "zonal_spectrum: %lld workgroups is too many", (long long)G.nblk);
+    if (G.nblk > MAX_BLOCKS) return fail(DLWPCS_E_UNSUPPORTED, "zonal_spectrum: %lld workgroups is too many", (long long)G.nblk);
     const size_t nq = pair ? 4 : 1;
     P.partial_bytes = P.w_bytes = P.skip_bytes = 0;
     if (G.slabs > 1) {
@@ -452,11 +451,6 @@ int zs_plan(const dlwpcs_zonal_spectrum_desc *d, bool pair, ZsPlan &P) {
         P.skip_bytes = (size_t)G.slabs * (size_t)G.groups * sizeof(int32_t);
     }
     return DLWPCS_OK;
-}
-
-dim3 zs_grid(int64_t n) {
-    const int64_t gx = n < 65536 ? n : 65536;
-    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
 }
 
 }  // namespace
@@ -491,9 +485,9 @@ extern "C" int dlwpcs_zonal_spectrum(const dlwpcs_zonal_spectrum_desc *d, const 
     double *partial = (double *)scratch;
     double *part_w = (double *)((char *)scratch + P.partial_bytes);
     int32_t *part_skip = (int32_t *)((char *)scratch + P.partial_bytes + P.w_bytes);
-    const bool vec = P.vec_ok && !((((uintptr_t)a) | ((uintptr_t)b)) & 15);
+    const bool vec = P.vec_ok && aligned16(a) && aligned16(b);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid = zs_grid(G.nblk), blk(ZS_THREADS);
+    const dim3 grid = launch_grid(G.nblk), blk(ZS_THREADS);
     const float2 *tw = (const float2 *)twiddle;
 #define ZS_LAUNCH(PAIR, VEC) \
     hipLaunchKernelGGL((zonal_spectrum_kernel<PAIR, VEC>), grid, blk, 0, s, G, a, b, w, tw, partial, part_w, part_skip, out, skipped)
@@ -503,7 +497,7 @@ extern "C" int dlwpcs_zonal_spectrum(const dlwpcs_zonal_spectrum_desc *d, const 
     if (G.slabs > 1) {
         const int nq = pair ? 4 : 1;
         const int64_t n = (int64_t)nq * G.groups * G.K;
-        hipLaunchKernelGGL(zonal_spectrum_finish_kernel, zs_grid((n + 255) / 256), dim3(256), 0, s, partial, part_w, part_skip,
+        hipLaunchKernelGGL(zonal_spectrum_finish_kernel, launch_grid((n + 255) / 256), dim3(256), 0, s, partial, part_w, part_skip,
                            G.groups, G.K, nq, G.slabs, out, skipped);
     }
     return check_launch("zonal_spectrum");

@@ -33,7 +33,7 @@
 // No profiler tags: the launch profiler's registry is the convolution family's (tests/test_conv_coverage_tags.py), as for the
 // other verification kernels.
 #include <math.h>
-#include "common.h"
+#include "strided.h"
 
 namespace dlwpcs {
 
@@ -52,46 +52,14 @@ constexpr int TF_GATHER_BLOCK = 8;                  // outputs a lane computes f
 constexpr int64_t TF_GATHER_MIN_SLAB = 8;
 
 struct TfGeom {
-    int32_t n_inner, out_vec;
-    int64_t ext[DLWPCS_SCORE_MAX_DIMS];             // the last extent counts chunks (elements / V)
-    int64_t sst[DLWPCS_SCORE_MAX_DIMS];
-    int64_t ost[DLWPCS_SCORE_MAX_DIMS];
-    int64_t src_row_stride, out_row_stride;
+    RowsAddr A;
+    int32_t out_vec;
     int64_t step_stride;                            // s * src_row_stride
-    int64_t ncol;                                   // chunks per row
-    int64_t tiles;                                  // column tiles of TF_THREADS chunks
-    int64_t nblk;
     int64_t T, o, J, slab_rows;
     int32_t K, s;
     int32_t alo, rem;                               // K = alo * s + rem: row t of a step has a tap for alo + (t < rem) ages
     float min_weight;
 };
-
-__device__ __forceinline__ int64_t tf_flat_block() { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
-
-template <int V>
-__device__ __forceinline__ void tf_offsets(const TfGeom &G, int64_t q, int64_t &soff, int64_t &ooff) {
-    soff = 0;
-    ooff = 0;
-    for (int d = G.n_inner - 1; d >= 0; --d) {
-        const int64_t e = G.ext[d];
-        int64_t c = q % e;
-        q /= e;
-        if (d == G.n_inner - 1) c *= V;
-        soff += c * G.sst[d];
-        ooff += c * G.ost[d];
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void tf_load(const float *__restrict__ p, float x[V]) {
-    if constexpr (V == 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(p);
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    } else {
-        x[0] = *p;
-    }
-}
 
 // source row r of the lane's column, off = r * src_row_stride; a row outside the source, or past the last row the slab needs
 // (r_last), is missing
@@ -99,10 +67,10 @@ template <int V>
 __device__ __forceinline__ void tf_load_row(const TfGeom &G, const float *__restrict__ p, int64_t r, int64_t off, int64_t r_last,
                                             float x[V]) {
     if (r >= 0 && r < G.T && r <= r_last) {
-        tf_load<V>(p + off, x);
+        load_chunk<V>(p + off, x);
     } else {
 #pragma unroll
-        for (int v = 0; v < V; ++v) x[v] = __int_as_float(0x7fc00000);
+        for (int v = 0; v < V; ++v) x[v] = quiet_nan();
     }
 }
 
@@ -113,7 +81,7 @@ __device__ __forceinline__ void tf_store(const TfGeom &G, float *__restrict__ ou
         if (G.out_vec) {
             *reinterpret_cast<float4 *>(out + off) = make_float4(r[0], r[1], r[2], r[3]);
             if (with_count) {
-                if ((reinterpret_cast<uintptr_t>(count) & 15) == 0) {
+                if (aligned16(count)) {
                     *reinterpret_cast<int4 *>(count + off) = make_int4(n[0], n[1], n[2], n[3]);
                 } else {
 #pragma unroll
@@ -121,7 +89,7 @@ __device__ __forceinline__ void tf_store(const TfGeom &G, float *__restrict__ ou
                 }
             }
         } else {
-            const int64_t st = G.ost[G.n_inner - 1];
+            const int64_t st = G.A.ost[G.A.n_inner - 1];
 #pragma unroll
             for (int v = 0; v < V; ++v) {
                 out[off + v * st] = r[v];
@@ -137,7 +105,7 @@ __device__ __forceinline__ void tf_store(const TfGeom &G, float *__restrict__ ou
 template <bool MEAN>
 __device__ __forceinline__ float tf_finish(float acc, float w, float min_weight) {
 #pragma clang fp contract(off)
-    const float nan = __int_as_float(0x7fc00000);
+    const float nan = quiet_nan();
     if constexpr (MEAN) {
         const float q = __fdiv_rn(acc, w);
         return (w >= min_weight && !isnan(q)) ? q : nan;
@@ -242,7 +210,7 @@ __device__ __forceinline__ void tf_step(TfWalk<V, AC, MEAN, CNT, S1, U> &W, TfLi
         float x[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) x[v] = ring[PP % U][v];
-        tf_load_row<V>(G, W.p, m + U - G.o, (m + U - G.o) * G.src_row_stride, W.r_last, ring[PP % U]);
+        tf_load_row<V>(G, W.p, m + U - G.o, (m + U - G.o) * G.A.src_row_stride, W.r_last, ring[PP % U]);
         if (m - G.o <= W.r_last) tf_row<V, AC, MEAN, CNT, true>(G, W.taps, L, PP, 0.f, 0, x);
     } else {
         if (W.r <= W.r_last) {
@@ -256,7 +224,7 @@ __device__ __forceinline__ void tf_step(TfWalk<V, AC, MEAN, CNT, S1, U> &W, TfLi
                         tf_load_row<V>(G, W.p, r, off, W.r_last, x[u]);
                         hv[u] = tf_row_taps(G, W.taps, t0 + u, na[u]);
                         r += 1;
-                        off += G.src_row_stride;
+                        off += G.A.src_row_stride;
                     }
 #pragma unroll
                 for (int u = 0; u < U; ++u)
@@ -267,7 +235,7 @@ __device__ __forceinline__ void tf_step(TfWalk<V, AC, MEAN, CNT, S1, U> &W, TfLi
         W.off += G.step_stride;
     }
     const int64_t j = m - (AC - 1);
-    if (j >= W.j0 && W.live) tf_emit<V, AC, MEAN, CNT>(G, L, (PP + 1) % AC, W.out, W.count, j * G.out_row_stride + W.ooff);
+    if (j >= W.j0 && W.live) tf_emit<V, AC, MEAN, CNT>(G, L, (PP + 1) % AC, W.out, W.count, j * G.A.out_row_stride + W.ooff);
 }
 
 template <int PP, int P, int V, int AC, bool MEAN, bool CNT, bool S1, int U>
@@ -286,17 +254,17 @@ __global__ void __launch_bounds__(TF_THREADS) time_filter_stream_kernel(TfGeom G
     // rows in flight per lane: a ring across the steps (s = 1), else a batch within a step (short where the unrolled code is long)
     constexpr int U = S1 ? (V == 4 ? 4 : 8) : (AC <= 8 ? 4 : 1);
     constexpr int P = S1 && U > AC ? U : AC;            // steps per unrolled period: a multiple of AC and of the ring
-    const int64_t bid = tf_flat_block();
-    if (bid >= G.nblk) return;
-    const int64_t slab = bid / G.tiles;
-    int64_t q = (bid - slab * G.tiles) * TF_THREADS + threadIdx.x;
+    const int64_t bid = flat_block();
+    if (bid >= G.A.nblk) return;
+    const int64_t slab = bid / G.A.tiles;
+    int64_t q = (bid - slab * G.A.tiles) * TF_THREADS + threadIdx.x;
     // a lane past the last column stays (the taps of a row are read lane by lane): it walks the last column and stores nothing
-    const bool live = q < G.ncol;
-    if (!live) q = G.ncol - 1;
+    const bool live = q < G.A.ncol;
+    if (!live) q = G.A.ncol - 1;
     const int64_t j0 = slab * G.slab_rows;
     const int64_t j1 = j0 + G.slab_rows < G.J ? j0 + G.slab_rows : G.J;
     int64_t soff, ooff;
-    tf_offsets<V>(G, q, soff, ooff);
+    rows_offsets<V, false>(G.A, q, soff, ooff);
     const float *p = src + soff;
     const int64_t r_last = (j1 - 1) * (int64_t)G.s + G.K - 1 - G.o;     // the last source row an output of the slab reads
     const int64_t m_last = j1 - 1 + (AC - 1);           // the step at whose end output j1 - 1 is stored
@@ -311,10 +279,10 @@ __global__ void __launch_bounds__(TF_THREADS) time_filter_stream_kernel(TfGeom G
         for (int u = 0; u < U; ++u) {                   // ring[u]: the first row at or after step j0 whose step % U == u
             int64_t m = j0 - j0 % U + u;
             if (m < j0) m += U;
-            tf_load_row<V>(G, p, m - G.o, (m - G.o) * G.src_row_stride, r_last, ring[u]);
+            tf_load_row<V>(G, p, m - G.o, (m - G.o) * G.A.src_row_stride, r_last, ring[u]);
         }
     }
-    TfWalk<V, AC, MEAN, CNT, S1, U> W = {G, p, taps, out, count, ooff, j0, r_last, m_last, live, r, r * G.src_row_stride};
+    TfWalk<V, AC, MEAN, CNT, S1, U> W = {G, p, taps, out, count, ooff, j0, r_last, m_last, live, r, r * G.A.src_row_stride};
     for (int64_t mb = m_first; mb <= m_last; mb += P) tf_period<0, P>(W, L, ring, mb);
 }
 
@@ -324,15 +292,15 @@ __global__ void __launch_bounds__(TF_THREADS) time_filter_gather_kernel(TfGeom G
                                                                        int32_t *__restrict__ count) {
 #pragma clang fp contract(off)
     constexpr int U = TF_GATHER_UNROLL, R = TF_GATHER_BLOCK;
-    const int64_t bid = tf_flat_block();
-    if (bid >= G.nblk) return;
-    const int64_t slab = bid / G.tiles;
-    const int64_t q = (bid - slab * G.tiles) * TF_THREADS + threadIdx.x;
-    if (q >= G.ncol) return;
+    const int64_t bid = flat_block();
+    if (bid >= G.A.nblk) return;
+    const int64_t slab = bid / G.A.tiles;
+    const int64_t q = (bid - slab * G.A.tiles) * TF_THREADS + threadIdx.x;
+    if (q >= G.A.ncol) return;
     const int64_t j0 = slab * G.slab_rows;
     const int64_t j1 = j0 + G.slab_rows < G.J ? j0 + G.slab_rows : G.J;
     int64_t soff, ooff;
-    tf_offsets<V>(G, q, soff, ooff);
+    rows_offsets<V, false>(G.A, q, soff, ooff);
     const float *p = src + soff;
     for (int64_t jb = j0; jb < j1; jb += R) {
         float acc[R][V], w[R][V];
@@ -350,7 +318,7 @@ __global__ void __launch_bounds__(TF_THREADS) time_filter_gather_kernel(TfGeom G
             for (int u = 0; u < U; ++u) {
                 const int64_t rr = rr0 + u;
                 const bool read = rr < nrow && (G.s <= G.K || rr % G.s < G.K);      // (K < s: rows between the windows)
-                tf_load_row<V>(G, p, r0 + rr, (r0 + rr) * G.src_row_stride, read ? G.T : -1, x[u]);
+                tf_load_row<V>(G, p, r0 + rr, (r0 + rr) * G.A.src_row_stride, read ? G.T : -1, x[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -387,15 +355,9 @@ __global__ void __launch_bounds__(TF_THREADS) time_filter_gather_kernel(TfGeom G
                 float r[V];
 #pragma unroll
                 for (int v = 0; v < V; ++v) r[v] = tf_finish<MEAN>(acc[i][v], w[i][v], G.min_weight);
-                tf_store<V>(G, out, count, (jb + i) * G.out_row_stride + ooff, r, n[i], count != nullptr);
+                tf_store<V>(G, out, count, (jb + i) * G.A.out_row_stride + ooff, r, n[i], count != nullptr);
             }
     }
-}
-
-dim3 tf_grid(int64_t n) {
-    if (n <= 0) return dim3(0, 0);
-    const int64_t gx = n < 65536 ? n : 65536;
-    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
 }
 
 struct TfPlan {
@@ -408,8 +370,10 @@ struct TfPlan {
 // The planner (restated in tests/time_filter_ref.py).  src / out: looked at for 16-byte alignment only.
 int tf_plan(const dlwpcs_rows_desc *d, const void *src, const void *out, int64_t n_rows, int n_taps, int64_t step, int64_t origin,
             int64_t n_out, int mode, int form, int64_t slab_rows, TfPlan &P) {
-    if (!d) return fail(DLWPCS_E_INVALID, "time_filter: null descriptor");
-    if (d->n_inner < 0 || d->n_inner > DLWPCS_SCORE_MAX_DIMS) return fail(DLWPCS_E_INVALID, "time_filter: n_inner %d out of range", d->n_inner);
+    TfGeom &G = P.G;
+    memset(&G, 0, sizeof(G));
+    const int rc = rows_addr_init(d, "time_filter", G.A, P.inner);
+    if (rc != DLWPCS_OK) return rc;
     if (n_taps < 1 || n_taps > DLWPCS_TIME_FILTER_MAX_TAPS)
         return fail(DLWPCS_E_INVALID, "time_filter: %d taps (1 .. %d)", n_taps, DLWPCS_TIME_FILTER_MAX_TAPS);
     if (step < 1 || step > (1ll << 30)) return fail(DLWPCS_E_INVALID, "time_filter: step %lld", (long long)step);
@@ -419,19 +383,6 @@ int tf_plan(const dlwpcs_rows_desc *d, const void *src, const void *out, int64_t
     if (mode != DLWPCS_FILTER_SUM && mode != DLWPCS_FILTER_MEAN) return fail(DLWPCS_E_INVALID, "time_filter: mode %d", mode);
     if (form < -1 || form > 1) return fail(DLWPCS_E_INVALID, "time_filter: form %d", form);
     if (slab_rows < 0) return fail(DLWPCS_E_INVALID, "time_filter: slab_rows %lld", (long long)slab_rows);
-    TfGeom &G = P.G;
-    memset(&G, 0, sizeof(G));
-    G.n_inner = d->n_inner;
-    G.src_row_stride = d->src_row_stride;
-    G.out_row_stride = d->out_row_stride;
-    P.inner = 1;
-    for (int i = 0; i < d->n_inner; ++i) {
-        if (d->inner_ext[i] < 0) return fail(DLWPCS_E_INVALID, "time_filter: inner extent %lld", (long long)d->inner_ext[i]);
-        G.ext[i] = d->inner_ext[i];
-        G.sst[i] = d->src_stride[i];
-        G.ost[i] = d->out_stride[i];
-        P.inner *= d->inner_ext[i];
-    }
     G.T = n_rows; G.K = n_taps; G.s = (int32_t)step; G.o = origin; G.J = n_out;
     G.step_stride = step * d->src_row_stride;
     G.alo = (int32_t)(n_taps / step);
@@ -445,24 +396,22 @@ int tf_plan(const dlwpcs_rows_desc *d, const void *src, const void *out, int64_t
     if (P.form == 0)
         for (P.cls = 1; P.cls < A; P.cls *= 2) {}
     // 16-byte chunks along the last dim; every other offset keeps a chunk on 16 bytes
-    const int L = d->n_inner - 1;
-    bool vec = L >= 0 && d->src_stride[L] == 1 && d->inner_ext[L] % 4 == 0 && d->src_row_stride % 4 == 0 && !(((uintptr_t)src) & 15);
-    for (int i = 0; i < L && vec; ++i) vec = d->src_stride[i] % 4 == 0;
-    if (P.form == 0 && P.cls > TF_VEC_MAX_CLASS) vec = false;
-    bool ovec = vec && d->out_stride[L] == 1 && d->out_row_stride % 4 == 0 && !(((uintptr_t)out) & 15);
-    for (int i = 0; i < L && ovec; ++i) ovec = d->out_stride[i] % 4 == 0;
+    bool vec, ovec;
+    rows_vector_ok(d, vec, ovec);
+    vec = vec && aligned16(src) && !(P.form == 0 && P.cls > TF_VEC_MAX_CLASS);
+    ovec = ovec && vec && aligned16(out);
     P.vec = vec;
     G.out_vec = ovec;
-    if (vec) G.ext[L] /= 4;
-    G.ncol = P.inner / (vec ? 4 : 1);
-    G.tiles = (G.ncol + TF_THREADS - 1) / TF_THREADS;
+    if (vec) G.A.ext[d->n_inner - 1] /= 4;
+    G.A.ncol = P.inner / (vec ? 4 : 1);
+    G.A.tiles = (G.A.ncol + TF_THREADS - 1) / TF_THREADS;
     if (slab_rows > 0) {
         G.slab_rows = slab_rows;
     } else {
         // enough slabs to fill the chip, none so short that the rows it shares with its neighbour (and, streaming, the steps in
         // which its pipeline fills) are more than an eighth of its own
         const int64_t lmin = P.form == 0 ? 8 * (int64_t)P.cls : TF_GATHER_MIN_SLAB;
-        const int64_t want = G.tiles > 0 ? (TF_TARGET_BLOCKS + G.tiles - 1) / G.tiles : 1;
+        const int64_t want = G.A.tiles > 0 ? (TF_TARGET_BLOCKS + G.A.tiles - 1) / G.A.tiles : 1;
         int64_t nsl = n_out / lmin < want ? n_out / lmin : want;
         if (nsl < 1) nsl = 1;
         G.slab_rows = (n_out + nsl - 1) / nsl;
@@ -470,14 +419,14 @@ int tf_plan(const dlwpcs_rows_desc *d, const void *src, const void *out, int64_t
     if (G.slab_rows < 1) G.slab_rows = 1;
     if (G.slab_rows > n_out && n_out > 0) G.slab_rows = n_out;
     const int64_t slabs = (n_out + G.slab_rows - 1) / G.slab_rows;
-    G.nblk = G.tiles * slabs;
-    if (G.nblk > 65536ll * 65535ll) return fail(DLWPCS_E_INVALID, "time_filter: %lld workgroups is too many", (long long)G.nblk);
+    G.A.nblk = G.A.tiles * slabs;
+    if (G.A.nblk > MAX_BLOCKS) return fail(DLWPCS_E_INVALID, "time_filter: %lld workgroups is too many", (long long)G.A.nblk);
     return DLWPCS_OK;
 }
 
 template <int V, int AC, bool MEAN, bool CNT>
 void tf_launch_stream(const TfPlan &P, const float *src, const float *taps, float *out, int32_t *count, hipStream_t s) {
-    const dim3 grid = tf_grid(P.G.nblk), blk(TF_THREADS);
+    const dim3 grid = launch_grid(P.G.A.nblk), blk(TF_THREADS);
     if (P.G.s == 1) hipLaunchKernelGGL((time_filter_stream_kernel<V, AC, MEAN, CNT, true>), grid, blk, 0, s, P.G, src, taps, out, count);
     else hipLaunchKernelGGL((time_filter_stream_kernel<V, AC, MEAN, CNT, false>), grid, blk, 0, s, P.G, src, taps, out, count);
 }
@@ -496,7 +445,7 @@ void tf_launch_class(const TfPlan &P, bool mean, const float *src, const float *
 template <int V>
 void tf_launch(const TfPlan &P, bool mean, const float *src, const float *taps, float *out, int32_t *count, hipStream_t s) {
     if (P.form == 1) {
-        const dim3 grid = tf_grid(P.G.nblk), blk(TF_THREADS);
+        const dim3 grid = launch_grid(P.G.A.nblk), blk(TF_THREADS);
         if (mean) hipLaunchKernelGGL((time_filter_gather_kernel<V, true>), grid, blk, 0, s, P.G, src, taps, out, count);
         else hipLaunchKernelGGL((time_filter_gather_kernel<V, false>), grid, blk, 0, s, P.G, src, taps, out, count);
         return;
@@ -546,7 +495,7 @@ extern "C" int dlwpcs_time_filter_plan_info(const dlwpcs_rows_desc *d, const voi
     if (rc != DLWPCS_OK) return rc;
     const bool empty = n_out == 0 || P.inner == 0;
     if (!empty && (!src || !out)) return fail(DLWPCS_E_INVALID, "time_filter: null operand");
-    const dim3 grid = tf_grid(empty ? 0 : P.G.nblk);
+    const dim3 grid = launch_grid(empty ? 0 : P.G.A.nblk);
     info[0] = P.form;
     info[1] = P.cls;
     info[2] = P.vec ? 1 : 0;

@@ -16,7 +16,7 @@
 // is row_tab[f * t_len + t] -- one load where a row's offsets are computed, nothing else differs, so the plan, the slabs
 // and the order of every sum are those of the materialised operand.  Which operand it is follows from the method (idx_operand).
 #include <string.h>
-#include "common.h"
+#include "strided.h"
 
 namespace dlwpcs {
 
@@ -47,9 +47,6 @@ struct ScoreGeom {
 constexpr int AUX_ELEM = 0;                     // one load per element (any strides)
 constexpr int AUX_VEC = 1;                      // one float4: contiguous along (row, channel) like a and b
 constexpr int AUX_CELL = 2;                     // one load: kc = 4 and constant along the channels (a per-cell field)
-
-// flat workgroup index of a launch that may use a second grid dimension (grid x * block size must stay below 2^32)
-__device__ __forceinline__ int64_t flat_block() { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
 
 template <int V>
 __device__ __forceinline__ void load_aux(const float *__restrict__ p, bool has, int mode, int64_t off, int64_t e0, int shift,
@@ -371,12 +368,6 @@ struct Plan {
     bool vec, column;
 };
 
-// grid of n workgroups: x below 2^16 (so x * 256 work-items fits in 32 bits), the rest in y
-static dim3 grid_of(int64_t n) {
-    const int64_t gx = n < 65536 ? n : 65536;
-    return dim3((unsigned)gx, (unsigned)((n + gx - 1) / gx));
-}
-
 static int aux_mode(const ScoreGeom &G, int op) {
     bool v4 = (G.kc == 1 || G.kc_stride[op] == 1) && G.row_stride[op] == G.kc && G.lead_stride[op] % 4 == 0 &&
               G.t_stride[op] % 4 == 0 && (op != G.idx_op || G.idx_stride % 4 == 0);
@@ -471,14 +462,14 @@ int make_plan(const dlwpcs_score_desc *d, Plan &P, int idx_op = -1, int64_t idx_
     if (P.column) slabs = 1;
     G.slabs = (int32_t)slabs;
     G.nblk = P.column ? (P.n_out + 255) / 256 : P.groups * slabs;
-    if (G.nblk > 65536ll * 65535ll) return fail(DLWPCS_E_INVALID, "score: %lld outputs is too many", (long long)P.n_out);
+    if (G.nblk > MAX_BLOCKS) return fail(DLWPCS_E_INVALID, "score: %lld outputs is too many", (long long)P.n_out);
     return DLWPCS_OK;
 }
 
 template <int M, bool IDX>
 void launch(const Plan &P, const float *a, const float *b, const float *c, const float *w, double *partial, void *out,
             const int32_t *row_tab, hipStream_t s) {
-    const dim3 grid = grid_of(P.G.nblk);
+    const dim3 grid = launch_grid(P.G.nblk);
     if (P.column) {
         hipLaunchKernelGGL((score_column_kernel<M, IDX>), grid, dim3(256), 0, s, P.G, P.n_out, a, b, c, w, out, row_tab);
         return;
@@ -490,7 +481,7 @@ void launch(const Plan &P, const float *a, const float *b, const float *c, const
         hipLaunchKernelGGL((score_partial_kernel<M, false, IDX>), grid, dim3(SC_THREADS), 0, s, P.G, a, b, c, w, partial, out,
                            row_tab);
     if (P.G.slabs > 1)
-        hipLaunchKernelGGL((score_finalize_kernel<M>), grid_of((P.n_out + 255) / 256), dim3(256), 0, s, partial, P.n_out,
+        hipLaunchKernelGGL((score_finalize_kernel<M>), launch_grid((P.n_out + 255) / 256), dim3(256), 0, s, partial, P.n_out,
                            P.G.kc, P.G.slabs, P.G.out_f32, out);
 }
 
@@ -511,9 +502,9 @@ int settle(const dlwpcs_score_desc *d, Plan &P, const float *&a, const float *b,
     if (!b || (d->method != DLWPCS_SCORE_MEAN && !a)) return fail(DLWPCS_E_INVALID, "score: null operand");
     if (P.G.idx_op >= 0 && !(P.G.idx_op == 0 ? a : c)) return fail(DLWPCS_E_INVALID, "score_indexed: null table");
     if (d->method == DLWPCS_SCORE_MEAN) a = b;
-    if (P.vec && ((((uintptr_t)a) & 15) || (((uintptr_t)b) & 15))) P.vec = false;
-    if (P.G.cmode == AUX_VEC && (((uintptr_t)c) & 15)) P.G.cmode = AUX_ELEM;
-    if (P.G.wmode == AUX_VEC && (((uintptr_t)w) & 15)) P.G.wmode = AUX_ELEM;
+    if (P.vec && !(aligned16(a) && aligned16(b))) P.vec = false;
+    if (P.G.cmode == AUX_VEC && !aligned16(c)) P.G.cmode = AUX_ELEM;
+    if (P.G.wmode == AUX_VEC && !aligned16(w)) P.G.wmode = AUX_ELEM;
     P.G.has_c = c != nullptr;
     P.G.has_w = w != nullptr;
     return DLWPCS_OK;
@@ -585,7 +576,7 @@ extern "C" int dlwpcs_score_plan_info(const dlwpcs_score_desc *d, const void *a,
     const float *pa = (const float *)a;
     rc = settle(d, P, pa, (const float *)b, (const float *)c, (const float *)w);
     if (rc != DLWPCS_OK) return rc;
-    const dim3 grid = grid_of(P.G.nblk);
+    const dim3 grid = launch_grid(P.G.nblk);
     info[0] = P.column ? 2 : P.vec ? 1 : 0;
     info[1] = P.G.slabs;
     info[2] = P.G.has_c ? P.G.cmode : -1;
