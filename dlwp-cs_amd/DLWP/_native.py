@@ -174,6 +174,8 @@ class EnsembleDesc(ctypes.Structure):
 
 QUANTILE_MAX_PROBS = 16
 TIME_FILTER_MAX_TAPS = 4096
+REGRESSION_MAX_TERMS = 16
+REGRESSION_SLAB_ROWS = 512
 CATEGORY_MAX_M = 1024
 CATEGORY_MAX_Q = 16
 
@@ -284,6 +286,13 @@ PROTOTYPES = {
                                    c_int, c_float, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_time_filter_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, ctypes.c_int64, c_int,
                                              c_int, ctypes.c_int64, c_void_p]),
+    'dlwpcs_time_regression_scratch_bytes': (c_size_t, [c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, c_int]),
+    'dlwpcs_time_regression': (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_int, ctypes.c_int64, ctypes.c_double,
+                                       ctypes.c_int64, c_int, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_time_regression_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_int, ctypes.c_int64,
+                                                 ctypes.c_int64, c_int, c_int, ctypes.c_int64, c_void_p]),
+    'dlwpcs_time_regression_apply': (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p,
+                                             c_int, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),

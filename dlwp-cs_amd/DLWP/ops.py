@@ -2991,6 +2991,185 @@ def time_filter(src, taps, row_axis=0, step=1, origin=0, n_out=None, mode='sum',
     return (out, cnt) if counts else out
 
 
+REGRESSION_MAX_TERMS = nat.REGRESSION_MAX_TERMS
+_FIT_MODES = {'skip': 0, 'propagate': 1}
+_FIT_FORMS = {None: -1, False: 0, True: 1}
+
+
+def _fit_basis(basis, n_rows, dev, who):
+    """(device tensor or None, float32 host array or None, K) of a (T, K) basis: numpy values are checked and rounded to float32,
+    a device tensor is trusted"""
+    if isinstance(basis, torch.Tensor):
+        if basis.dtype != torch.float32 or basis.device != dev or basis.dim() != 2 or not basis.is_contiguous():
+            raise TypeError('%s: a device basis must be a contiguous (T, K) float32 tensor on the device of the data' % who)
+        b, b32, shape = basis, None, tuple(basis.shape)
+    else:
+        bh = np.asarray(basis, dtype=np.float64)
+        if bh.ndim != 2:
+            raise ValueError('%s: the basis must be (T, K), got %d dims' % (who, bh.ndim))
+        with np.errstate(over='ignore'):
+            b32 = np.ascontiguousarray(bh, dtype=np.float32)
+        if not np.all(np.isfinite(b32)):
+            raise ValueError('%s: the basis must be finite in float32' % who)
+        b, shape = None, b32.shape
+    if not 1 <= shape[1] <= REGRESSION_MAX_TERMS:
+        raise ValueError('%s: %d terms (1 .. %d)' % (who, shape[1], REGRESSION_MAX_TERMS))
+    if shape[0] != n_rows:
+        raise ValueError('%s: the basis has %d rows, the data %d' % (who, shape[0], n_rows))
+    return b, b32, int(shape[1])
+
+
+def _fit_args(n_terms, missing, min_count, pivot_tol, slab_rows, split, gram):
+    if missing not in _FIT_MODES:
+        raise ValueError("time_regression: missing must be 'skip' or 'propagate', got %r" % (missing,))
+    if split not in _FIT_FORMS or gram not in _FIT_FORMS:
+        raise ValueError('time_regression: split and gram must be None, False or True')
+    mc = n_terms if min_count is None else int(min_count)
+    if mc < n_terms:
+        raise ValueError('time_regression: min_count %d below the %d terms' % (mc, n_terms))
+    tol = 0. if pivot_tol is None else float(pivot_tol)
+    if not 0. <= tol < 1.:
+        raise ValueError('time_regression: pivot_tol %r outside [0, 1)' % (pivot_tol,))
+    slab = 0 if slab_rows is None else int(slab_rows)
+    if slab < 0 or (slab_rows is not None and slab == 0):
+        raise ValueError('time_regression: slab_rows %r' % (slab_rows,))
+    return _FIT_MODES[missing], mc, tol, slab, _FIT_FORMS[split], _FIT_FORMS[gram]
+
+
+def time_regression_plan(shape, strides, n_terms, row_axis=0, out_perm=None, slab_rows=None, split=None, gram=None, aligned=True):
+    """
+    Which code time_regression would run for a source of this shape and these element strides (host only, no device is touched):
+    dict(split, gram = every column its own G, k_class = the term class, chunk = elements per lane, grid, lds_bytes, slab_rows).
+    aligned=False: as for pointers that are not on 16 bytes.  Raises what time_regression would raise.
+    """
+    n_terms = int(n_terms)
+    if not 1 <= n_terms <= REGRESSION_MAX_TERMS:
+        raise ValueError('time_regression: %d terms (1 .. %d)' % (n_terms, REGRESSION_MAX_TERMS))
+    m, mc, _, slab, sp, gr = _fit_args(n_terms, 'skip', None, None, slab_rows, split, gram)
+    d, _ = rows_layout(shape, strides, row_axis, out_perm, n_terms)
+    info = (ctypes.c_int32 * 8)()
+    p = (1 << 20) if aligned else (1 << 20) + 4
+    check(lib().dlwpcs_time_regression_plan_info(ctypes.byref(d), p, p, int(shape[row_axis]), n_terms, m, mc, slab, sp, gr,
+                                                 d.out_row_stride, info), 'dlwpcs_time_regression_plan_info')
+    return dict(split=bool(info[0]), gram=bool(info[1]), k_class=info[2], chunk=info[3], grid=(info[4], info[5]), lds_bytes=info[6],
+                slab_rows=info[7])
+
+
+def time_regression(src, basis, row_axis=0, missing='skip', min_count=None, pivot_tol=None, out_perm=None, slab_rows=None, split=None,
+                    gram=None, counts=False):
+    """
+    The least-squares coefficients of the (T, K) `basis` along `row_axis` of the fp32 device tensor `src` (any strides), per
+    element, over the rows that are not NaN: fp64 normal equations in a fixed order, factorised without a square root
+    (include/dlwpcs.h states the operations).  missing='skip': fitted to the rows present; 'propagate': an element with a missing
+    row is NaN.  An element with fewer than `min_count` rows present (None: K), a singular system (a pivot below `pivot_tol` times
+    its diagonal entry, None: 2^-40) or a coefficient that is not finite is NaN in all K terms.  `basis`: a numpy array (checked,
+    rounded to float32 once: the coefficients belong to the rounded basis) or an fp32 device tensor (trusted: finite).  The result
+    has src's dims in the order `out_perm` (default: unchanged) with K terms where the row axis stood, contiguous.  split / gram:
+    None = the library chooses, True / False forces the two-launch slab form / an own normal matrix for every column;
+    slab_rows: rows per slab of the summation order (None: 512, part of the definition).  The same bits whatever split and gram
+    are.  counts=True also returns the int32 number of rows present, without the row axis.  Four launches on the current stream
+    (two of them one small workgroup or one per slab), no host synchronisation.
+    """
+    require_device(src, 'time_regression')
+    dev = src.device
+    n_rows = int(src.shape[row_axis])
+    b, b32, K = _fit_basis(basis, n_rows, dev, 'time_regression')
+    m, mc, tol, slab, sp, gr = _fit_args(K, missing, min_count, pivot_tol, slab_rows, split, gram)
+    d, out = _rows_desc(src, row_axis, out_perm, K)
+    at = (tuple(range(src.dim())) if out_perm is None else tuple(int(a) % src.dim() for a in out_perm)).index(row_axis % src.dim())
+    # the counts have the layout of one term: term 0 of an array of the coefficients' shape
+    cnt = torch.empty(out.shape, dtype=torch.int32, device=dev) if counts else None
+    if out.numel():
+        with torch.cuda.device(dev):
+            if b is None:
+                b = torch.from_numpy(b32).pin_memory().to(dev, non_blocking=True)
+            nbytes = int(lib().dlwpcs_time_regression_scratch_bytes(ctypes.byref(d), n_rows, K, slab, sp))
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            check(lib().dlwpcs_time_regression(ctypes.byref(d), src.data_ptr(), n_rows, b.data_ptr(), K, m, mc, tol, slab, sp, gr,
+                                               out.data_ptr(), d.out_row_stride, ptr(cnt), ptr(scratch), nbytes, stream_ptr()),
+                  'dlwpcs_time_regression')
+    return (out, cnt.select(at, 0)) if counts else out
+
+
+def time_regression_apply(coef, basis, src=None, term_axis=0, row_axis=None, out_perm=None):
+    """
+    The fitted values sum_k basis[r, k] * coef[k] for every row r of the (R, K) `basis` (src=None), or the residuals src - fitted,
+    in fp64 rounded to fp32 once.  `coef`: an fp32 device tensor with K terms along `term_axis` (any strides); `src`: an fp32 device
+    tensor with R rows along `row_axis` (None: term_axis) and coef's other dims in coef's order.  NaN where a coefficient of the
+    element or the source is NaN.  R need not be the length of the fit.  The result has the dims of `src` (of coef, with R rows
+    where the terms stood) in the order `out_perm`, contiguous.  One launch on the current stream.
+    """
+    require_device(coef, 'time_regression_apply')
+    if coef.dtype != torch.float32:
+        raise TypeError('time_regression_apply: the coefficients must be float32, got %s' % coef.dtype)
+    dev = coef.device
+    nd = coef.dim()
+    term_axis = term_axis % nd
+    row_axis = term_axis if row_axis is None else row_axis % nd
+    n_rows = int(src.shape[row_axis]) if src is not None else int(np.shape(basis)[0])
+    b, b32, K = _fit_basis(basis, n_rows, dev, 'time_regression_apply')
+    if int(coef.shape[term_axis]) != K:
+        raise ValueError('time_regression_apply: %d coefficients along axis %d, the basis has %d terms' % (coef.shape[term_axis], term_axis, K))
+    crest = [a for a in range(nd) if a != term_axis]
+    if src is not None:
+        require_device(src, 'time_regression_apply')
+        if src.dtype != torch.float32 or src.device != dev:
+            raise TypeError('time_regression_apply: the source must be float32 on the device of the coefficients')
+        srest = [a for a in range(nd) if a != row_axis]
+        if src.dim() != nd or [src.shape[a] for a in srest] != [coef.shape[a] for a in crest] or int(src.shape[row_axis]) != n_rows:
+            raise ValueError('time_regression_apply: the source %s does not match the coefficients %s' % (tuple(src.shape), tuple(coef.shape)))
+        shape, sstr = tuple(src.shape), tuple(src.stride())
+    else:
+        srest = crest
+        row_axis = term_axis
+        shape = tuple(n_rows if a == term_axis else int(coef.shape[a]) for a in range(nd))
+        sstr = (0,) * nd
+    cstr = [0] * nd
+    for sa, ca in zip(srest, crest):
+        cstr[sa] = int(coef.stride(ca))
+    d, cst, oshape = _apply_layout(shape, sstr, cstr, row_axis, out_perm, n_rows, src is not None)
+    out = torch.empty(oshape, dtype=torch.float32, device=dev)
+    if out.numel():
+        cs = (ctypes.c_int64 * nat.SCORE_MAX_DIMS)(*cst)
+        with torch.cuda.device(dev):
+            if b is None:
+                b = torch.from_numpy(b32).pin_memory().to(dev, non_blocking=True)
+            check(lib().dlwpcs_time_regression_apply(ctypes.byref(d), ptr(src), n_rows, b.data_ptr(), K, coef.data_ptr(),
+                                                     int(coef.stride(term_axis)), cs, 0 if src is None else 1, out.data_ptr(), stream_ptr()),
+                  'dlwpcs_time_regression_apply')
+    return out
+
+
+def _apply_layout(shape, sstr, cstr, row_axis, out_perm, n_out, has_src):
+    """rows_layout with a third operand: (descriptor of source and output, the coefficients' stride per inner dim, output shape).
+    Neighbours merge where source, coefficients and output all allow it; the dim that is contiguous in the source (without one:
+    in the output) goes last."""
+    nd = len(shape)
+    perm = tuple(range(nd)) if out_perm is None else tuple(int(a) % nd for a in out_perm)
+    if sorted(perm) != list(range(nd)):
+        raise ValueError('rows: out_perm %s is not a permutation of %d dims' % (out_perm, nd))
+    oshape = [n_out if a == row_axis else int(shape[a]) for a in perm]
+    ostride, run = [0] * nd, 1
+    for pos in range(nd - 1, -1, -1):
+        ostride[pos] = run
+        run *= max(oshape[pos], 1)
+    at = perm.index(row_axis)
+    dims = [(e, st) for e, st, _ in
+            merge_dims((int(shape[a]), (int(sstr[a]), int(cstr[a]), ostride[pos]), pos > at) for pos, a in enumerate(perm) if a != row_axis)]
+    unit = [i for i, x in enumerate(dims) if x[1][0 if has_src else 2] == 1]
+    if unit:
+        dims.append(dims.pop(unit[-1]))
+    if len(dims) > nat.SCORE_MAX_DIMS:
+        raise NotImplementedError('rows: more than %d inner dims after merging' % nat.SCORE_MAX_DIMS)
+    d = nat.RowsDesc()
+    d.n_inner = len(dims)
+    d.src_row_stride, d.out_row_stride = int(sstr[row_axis]), ostride[at]
+    cst = [0] * nat.SCORE_MAX_DIMS
+    for i, (e, st) in enumerate(dims):
+        d.inner_ext[i], d.src_stride[i], cst[i], d.out_stride[i] = e, st[0], st[1], st[2]
+    return d, cst, oshape
+
+
 QUANTILE_MAX_PROBS = nat.QUANTILE_MAX_PROBS
 
 

@@ -2274,3 +2274,344 @@ def lead_window_mean(x, windows, axis=None, min_count=None):
                 out[i] = np.where(n >= mc[i], np.where(ok, h[a:b], 0.).sum(axis=0) / np.maximum(n, 1), np.nan)
         out = np.moveaxis(out, 0, axis)
     return _filter_label(x, axis, win[:, 1] - 1, out, 'lead_window_mean')
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# Least-squares fits along time: trends, harmonic climatologies, regression maps
+# --------------------------------------------------------------------------------------------------------------------- #
+
+REGRESSION_MAX_TERMS = 16
+_TROPICAL_YEAR_S = 365.24219 * 86400.
+_FIT_SLAB = 512
+_FIT_PIVOT_TOL = 2.0 ** -40
+
+
+def _centred(t):
+    """t mapped linearly onto [-1, 1] (one time: 0)"""
+    t = np.asarray(t, dtype=np.float64)
+    lo, hi = (t.min(), t.max()) if t.size else (0., 0.)
+    return (2. * t - (hi + lo)) / (hi - lo) if hi > lo else np.zeros_like(t)
+
+
+def _times_seconds(times):
+    t = np.asarray(getattr(times, 'values', times))
+    if t.dtype.kind == 'M':
+        return (t.astype('datetime64[ms]') - np.datetime64('2000-01-01T00', 'ms')).astype(np.float64) / 1000., True
+    return t.astype(np.float64), False
+
+
+def harmonic_basis(times, n_harmonics=4, trend=False, period=None, trend_span=None):
+    """
+    The (T, K) float64 basis of a harmonic fit at `times`: a column of ones, with `trend` a linear trend centred and scaled to
+    [-1, 1] over the times (over `trend_span` = (first, last) when given, so that other times continue the same line), then
+    cos and sin of the harmonics 1 .. n_harmonics of `period`.  datetime64 times: the period is the tropical year (365.24219
+    days) and the phase is counted from 2000-01-01; numbers: `period` must be given, in the unit of the times.  Host only.
+    """
+    t, is_date = _times_seconds(times)
+    if t.ndim != 1:
+        raise ValueError('harmonic_basis: the times must be one-dimensional')
+    H = int(n_harmonics)
+    if H < 0:
+        raise ValueError('harmonic_basis: n_harmonics %d' % H)
+    if period is None:
+        if not is_date:
+            raise ValueError('harmonic_basis: numeric times need a period')
+        p = _TROPICAL_YEAR_S
+    else:
+        p = float(period / np.timedelta64(1, 's')) if isinstance(period, np.timedelta64) else float(period)
+        if not p > 0.:
+            raise ValueError('harmonic_basis: period %r' % (period,))
+    cols = [np.ones(t.shape)]
+    if trend:
+        if trend_span is None:
+            cols.append(_centred(t))
+        else:
+            lo, hi = _times_seconds(np.asarray(trend_span))[0]
+            cols.append((2. * t - (hi + lo)) / (hi - lo) if hi > lo else np.zeros_like(t))
+    for h in range(1, H + 1):
+        ang = 2. * np.pi * h * (t / p)
+        cols += [np.cos(ang), np.sin(ang)]
+    if len(cols) > REGRESSION_MAX_TERMS:
+        raise ValueError('harmonic_basis: %d terms (1 .. %d)' % (len(cols), REGRESSION_MAX_TERMS))
+    return np.stack(cols, axis=1)
+
+
+def _fit_basis32(basis, n_rows, name):
+    """the basis as the device sees it: float32, checked"""
+    b = np.asarray(getattr(basis, 'values', basis), dtype=np.float64)
+    if b.ndim != 2:
+        raise ValueError('%s: the basis must be (T, K), got %d dims' % (name, b.ndim))
+    if not 1 <= b.shape[1] <= REGRESSION_MAX_TERMS:
+        raise ValueError('%s: %d terms (1 .. %d)' % (name, b.shape[1], REGRESSION_MAX_TERMS))
+    if n_rows is not None and b.shape[0] != n_rows:
+        raise ValueError('%s: the basis has %d rows, the data %d' % (name, b.shape[0], n_rows))
+    with np.errstate(over='ignore'):
+        b32 = np.ascontiguousarray(b, dtype=np.float32)
+    if not np.all(np.isfinite(b32)):
+        raise ValueError('%s: the basis must be finite in float32' % name)
+    return b32
+
+
+def _time_regression_host(x, b32, axis, propagate, min_count):
+    """the definition of dlwpcs_time_regression in float64 on the host: (float32 coefficients, int32 counts), the term axis where
+    `axis` stood.  The same operations on the same rounded basis; the sums are numpy's, not the slab order: no claim to the bits."""
+    v = np.moveaxis(np.asarray(x, dtype=np.float64), axis, 0)
+    T, K = b32.shape
+    rest = v.shape[1:]
+    v = v.reshape(T, -1)
+    E = v.shape[1]
+    b = b32.astype(np.float64)
+    present = ~np.isnan(v)
+    n = present.sum(axis=0).astype(np.int32)
+    with np.errstate(all='ignore'):
+        xz = np.where(present, v, 0.)
+        c = b.T @ xz                                                    # (K, E); an infinity stays one (0 * inf: NaN, as on the device)
+        pm = present.astype(np.float64)
+        G = np.zeros((K, K, E))
+        for i in range(K):
+            for j in range(i + 1):
+                G[i, j] = (b[:, i] * b[:, j]) @ pm
+        L, d = np.zeros((K, K, E)), np.zeros((K, E))
+        singular = np.zeros(E, dtype=bool)
+        for j in range(K):
+            s = np.zeros(E)
+            for p in range(j):
+                s = s + (L[j, p] * L[j, p]) * d[p]
+            dj = G[j, j] - s
+            singular |= ~(dj > _FIT_PIVOT_TOL * G[j, j])
+            d[j] = np.where(singular, np.nan, dj)
+            for i in range(j + 1, K):
+                s = np.zeros(E)
+                for p in range(j):
+                    s = s + (L[i, p] * L[j, p]) * d[p]
+                L[i, j] = (G[i, j] - s) / d[j]
+        z = np.zeros((K, E))
+        for i in range(K):
+            s = np.zeros(E)
+            for p in range(i):
+                s = s + L[i, p] * z[p]
+            z[i] = c[i] - s
+        w = z / d
+        a = np.zeros((K, E))
+        for i in range(K - 1, -1, -1):
+            s = np.zeros(E)
+            for p in range(i + 1, K):
+                s = s + L[p, i] * a[p]
+            a[i] = w[i] - s
+        coef = a.astype(np.float32)
+    bad = (n < min_count) | singular | ~np.all(np.isfinite(coef), axis=0)
+    if propagate:
+        bad |= n < T
+    coef[:, bad] = np.nan
+    return np.moveaxis(coef.reshape((K,) + rest), 0, axis), n.reshape(rest)
+
+
+def _fit_label(x, axis, values, name, term=True):
+    """`values` labelled like x with a 'term' dim where `axis` stood (term=False: without that dim)"""
+    if not hasattr(x, 'dims'):
+        return values
+    dims = tuple(x.dims)
+    coords = {d: _coord(x, d) for i, d in enumerate(dims) if i != axis and d in getattr(x, 'coords', {})}
+    if term:
+        coords['term'] = np.arange(values.shape[axis])
+        out_dims = dims[:axis] + ('term',) + dims[axis + 1:]
+    else:
+        out_dims = dims[:axis] + dims[axis + 1:]
+    out = Forecast(values, out_dims, coords, name=name)
+    if hasattr(x, 'lat'):
+        out.lat = x.lat
+    return out
+
+
+def _fit(x, b32, axis, missing, min_count, return_count, name):
+    if missing not in ('propagate', 'skip'):
+        raise ValueError("'missing' must be 'propagate' or 'skip'")
+    K = b32.shape[1]
+    mc = K if min_count is None else int(min_count)
+    if mc < K:
+        raise ValueError('%s: min_count %d below the %d terms' % (name, mc, K))
+    v = _raw(x)
+    if _is_tensor(v) and v.is_cuda:
+        import torch
+        from . import ops as dops
+        with torch.cuda.device(v.device):
+            src = v if v.dtype == torch.float32 else v.to(torch.float32)
+            res = dops.time_regression(src, b32, row_axis=axis, missing=missing, min_count=mc, counts=return_count)
+        coef, cnt = res if return_count else (res, None)
+    else:
+        coef, cnt = _time_regression_host(_host(v), b32, axis, missing == 'propagate', mc)
+    out = _fit_label(x, axis, coef, name)
+    return (out, _fit_label(x, axis, cnt, name + '_count', term=False)) if return_count else out
+
+
+def time_regression(x, basis, axis=None, missing='skip', min_count=None, return_count=False):
+    """
+    The least-squares coefficients of `basis` (T, K; K at most 16) fitted along time, per grid point, to the rows that are not
+    NaN: a trend, a harmonic climatology (`harmonic_basis`), or the regression of a field on an index (basis = ones and the
+    index: coefficient 1 is the regression map).
+
+    :param x: a `Forecast` (or anything with `.dims`, `.coords`, `.values`), a numpy array or a torch tensor.  Values on a HIP
+        device are fitted there (dlwpcs_time_regression: fp64 normal equations in a fixed order) and the result stays there;
+        numpy values are fitted on the host in float64 by the same rules, without a claim to the same bits.
+    :param basis: host values, (T, K).  It is rounded to float32 ONCE, on both paths: the coefficients belong to the rounded
+        basis, which is also what `regression_fitted` and `regression_residual` evaluate.
+    :param axis: the axis to fit along, a position or a dim name; None: the 'time' dim of a labelled input, else axis 0
+    :param missing: 'skip': fit the rows present.  'propagate': a grid point with a missing row is NaN.
+    :param min_count: a grid point with fewer rows present is NaN (None: K).  So is one whose system is singular.
+    :param return_count: also return the int32 number of rows present (no term dim)
+    :return: float32 coefficients labelled like the input, a 'term' dim where the time axis stood
+    """
+    axis = _filter_axis(x, axis, 'time')
+    b32 = _fit_basis32(basis, int(_raw(x).shape[axis]), 'time_regression')
+    return _fit(x, b32, axis, missing, min_count, return_count, 'time_regression')
+
+
+def _evaluate(coef, b32, term_axis, x, axis, name, rows_coord=None, row_dim='time'):
+    """fitted values (x None) or residuals x - fitted, labelled"""
+    c = _raw(coef)
+    on_dev = _is_tensor(c) and c.is_cuda
+    xv = None if x is None else _raw(x)
+    if xv is not None and (_is_tensor(xv) and xv.is_cuda) != on_dev:
+        raise ValueError('%s: the data and the coefficients must both be on the device or both on the host' % name)
+    if on_dev:
+        import torch
+        from . import ops as dops
+        with torch.cuda.device(c.device):
+            cf = c if c.dtype == torch.float32 else c.to(torch.float32)
+            src = None if xv is None else (xv if xv.dtype == torch.float32 else xv.to(torch.float32))
+            out = dops.time_regression_apply(cf, b32, src=src, term_axis=term_axis, row_axis=axis)
+    else:
+        ch = np.moveaxis(np.asarray(_host(c), dtype=np.float64), term_axis, 0)
+        with np.errstate(all='ignore'):
+            f = np.tensordot(b32.astype(np.float64), ch, axes=(1, 0))
+            bad = np.isnan(ch).any(axis=0)[None]
+            if xv is None:
+                y = np.moveaxis(np.where(bad, np.nan, f), 0, term_axis).astype(np.float32)
+            else:
+                xh = np.moveaxis(np.asarray(_host(xv), dtype=np.float64), axis, 0)
+                y = np.moveaxis(np.where(bad, np.nan, xh - f), 0, axis).astype(np.float32)
+    if x is not None:
+        if not hasattr(x, 'dims'):
+            return out if on_dev else y
+        res = Forecast(out if on_dev else y, tuple(x.dims), {d: _coord(x, d) for d in x.dims if d in getattr(x, 'coords', {})}, name=name)
+        if hasattr(x, 'lat'):
+            res.lat = x.lat
+        return res
+    if not hasattr(coef, 'dims'):
+        return out if on_dev else y
+    dims = tuple(coef.dims)
+    coords = {d: _coord(coef, d) for i, d in enumerate(dims) if i != term_axis and d in getattr(coef, 'coords', {})}
+    if rows_coord is not None:
+        coords[row_dim] = rows_coord
+    res = Forecast(out if on_dev else y, dims[:term_axis] + (row_dim,) + dims[term_axis + 1:], coords, name=name)
+    if hasattr(coef, 'lat'):
+        res.lat = coef.lat
+    return res
+
+
+def regression_fitted(coef, basis, term_axis=None, times=None):
+    """
+    The fitted values sum_k basis[r, k] coef[k] of the coefficients of `time_regression` at the rows of `basis` (R, K; R need not
+    be the length of the fit), in fp64 rounded to float32 once; NaN where the grid point's coefficients are.  A 'time' dim of R
+    rows stands where the 'term' dim stood (its coordinate: `times`, when given).  Device coefficients are evaluated there.
+    """
+    term_axis = _filter_axis(coef, term_axis, 'term')
+    b32 = _fit_basis32(basis, None, 'regression_fitted')
+    if b32.shape[1] != int(_raw(coef).shape[term_axis]):
+        raise ValueError('regression_fitted: %d coefficients, the basis has %d terms' % (_raw(coef).shape[term_axis], b32.shape[1]))
+    return _evaluate(coef, b32, term_axis, None, term_axis, 'regression_fitted', None if times is None else np.asarray(times))
+
+
+def regression_residual(x, coef, basis, axis=None, term_axis=None):
+    """x minus the fitted values of `regression_fitted`, labelled like x: NaN where x or the grid point's coefficients are."""
+    axis = _filter_axis(x, axis, 'time')
+    term_axis = axis if term_axis is None and not hasattr(coef, 'dims') else _filter_axis(coef, term_axis, 'term')
+    b32 = _fit_basis32(basis, int(_raw(x).shape[axis]), 'regression_residual')
+    if b32.shape[1] != int(_raw(coef).shape[term_axis]):
+        raise ValueError('regression_residual: %d coefficients, the basis has %d terms' % (_raw(coef).shape[term_axis], b32.shape[1]))
+    return _evaluate(coef, b32, term_axis, x, axis, 'regression_residual')
+
+
+def detrend(x, axis=None, order=1, missing='skip'):
+    """
+    x minus its least-squares polynomial of degree `order` (0 .. 3) along time, per grid point: powers of the row number centred
+    and scaled to [-1, 1].  order 0 removes the mean of the rows present.  NaN where x is, and at a grid point with fewer than
+    order + 1 rows present (with missing='propagate': with any row missing).
+    """
+    order = int(order)
+    if not 0 <= order <= 3:
+        raise ValueError('detrend: order %d outside 0 .. 3' % order)
+    axis = _filter_axis(x, axis, 'time')
+    T = int(_raw(x).shape[axis])
+    t = _centred(np.arange(T))
+    b32 = _fit_basis32(np.stack([t ** p for p in range(order + 1)], axis=1), T, 'detrend')
+    coef = _fit(x, b32, axis, missing, None, False, 'detrend')
+    return _evaluate(coef, b32, axis, x, axis, 'detrend')
+
+
+class HarmonicClimatology(object):
+    """
+    A climatology as a mean, optionally a linear trend, and the first annual harmonics, fitted per grid point over a whole series
+    (`harmonic_climatology`).  `.coefficients`: float32, a 'term' dim where the time dim stood, on the device when the data was.
+    `.series(times)`: the climatology at any times, a 'time' dim in that place: what `daily_climo_time_series` returns, and
+    accepted wherever that is.  `.anomalies(ds)`: ds minus the climatology at its own times.
+    """
+
+    def __init__(self, coefficients, n_harmonics, trend, span):
+        self.coefficients = coefficients
+        self.n_harmonics = int(n_harmonics)
+        self.trend = bool(trend)
+        self.span = span
+
+    def basis(self, times):
+        return harmonic_basis(times, self.n_harmonics, self.trend, trend_span=self.span)
+
+    def series(self, times, f_hour=None):
+        """the climatology at `times`; with `f_hour` at times + f_hour, behind a leading 'f_hour' dim, as daily_climo_time_series"""
+        t = np.asarray(getattr(times, 'values', times))
+        axis = _filter_axis(self.coefficients, None, 'term')
+        if f_hour is None:
+            b32 = _fit_basis32(self.basis(t), None, 'harmonic_climatology')
+            return _evaluate(self.coefficients, b32, axis, None, axis, 'climatology', t)
+        when = t.astype('datetime64[s]')[None, :] + _lead_hours(f_hour).astype('timedelta64[s]')[:, None]
+        b32 = _fit_basis32(self.basis(when.reshape(-1)), None, 'harmonic_climatology')
+        flat = _evaluate(self.coefficients, b32, axis, None, axis, 'climatology', when.reshape(-1))
+        v = _raw(flat)
+        v = v.reshape(tuple(v.shape[:axis]) + when.shape + tuple(v.shape[axis + 1:]))
+        v = v.movedim(axis, 0) if _is_tensor(v) else np.moveaxis(v, axis, 0)
+        if not hasattr(flat, 'dims'):
+            return v
+        coords = {d: c for d, c in flat.coords.items() if d != 'time'}
+        coords['time'] = t
+        coords['f_hour'] = np.asarray(getattr(f_hour, 'values', f_hour))
+        out = Forecast(v, ('f_hour',) + tuple(flat.dims), coords, name='climatology')
+        if hasattr(flat, 'lat'):
+            out.lat = flat.lat
+        return out
+
+    def anomalies(self, ds):
+        axis = _filter_axis(ds, None, 'time')
+        if not (hasattr(ds, 'coords') and 'time' in ds.coords):
+            raise ValueError("harmonic_climatology: the data has no 'time' coordinate")
+        b32 = _fit_basis32(self.basis(_coord(ds, 'time')), int(_raw(ds).shape[axis]), 'harmonic_climatology')
+        return _evaluate(self.coefficients, b32, _filter_axis(self.coefficients, None, 'term'), ds, axis, 'anomaly')
+
+
+def harmonic_climatology(ds, n_harmonics=4, trend=False, min_count=None):
+    """
+    The harmonic climatology of a labelled series with a datetime64 'time' coordinate: a mean, with `trend` a linear trend, and
+    `n_harmonics` harmonics of the tropical year, fitted per grid point to the rows that are not NaN (`time_regression`).  Where
+    `daily_climatology` averages the thirty-odd values a day of the year has, this fits 1 + 2 n_harmonics numbers to all of them.
+    Returns a `HarmonicClimatology`.
+    """
+    if not (hasattr(ds, 'dims') and 'time' in tuple(ds.dims) and 'time' in getattr(ds, 'coords', {})):
+        raise ValueError("harmonic_climatology: the data needs a 'time' dimension with a coordinate")
+    t = _coord(ds, 'time')
+    if t.dtype.kind != 'M':
+        raise ValueError("harmonic_climatology: the 'time' coordinate must be datetime64")
+    span = (t.min(), t.max()) if t.size else None
+    basis = harmonic_basis(t, n_harmonics, trend, trend_span=span)
+    axis = tuple(ds.dims).index('time')
+    coef = _fit(ds, _fit_basis32(basis, int(_raw(ds).shape[axis]), 'harmonic_climatology'), axis, 'skip', min_count, False,
+                'harmonic_climatology')
+    return HarmonicClimatology(coef, n_harmonics, trend, span)

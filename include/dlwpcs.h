@@ -728,6 +728,75 @@ int dlwpcs_time_filter_plan_info(const dlwpcs_rows_desc *d, const void *src, con
                                  int64_t step, int64_t n_out, int mode, int form, int64_t slab_rows, int32_t info[8]);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Least-squares fits along the row axis (DLWP/verify.py time_regression, detrend, harmonic_climatology): per element of a row set
+ * (dlwpcs_rows_desc: strides in elements, lanes along the last inner dim) the K coefficients of the basis that fit the rows
+ * present best.  x: T = n_rows fp32 rows.  basis: a contiguous (T, K) fp32 DEVICE array, finite, trusted, 1 <= K <=
+ * DLWPCS_REGRESSION_MAX_TERMS.  S = slab_rows > 0 (0: DLWPCS_REGRESSION_SLAB_ROWS), min_count >= K, pivot_tol a double in [0, 1)
+ * (0: 2^-40), mode DLWPCS_FIT_SKIP or DLWPCS_FIT_PROPAGATE; anything else is DLWPCS_E_INVALID before any launch.
+ *
+ * Definition (the tests compare bits against it).  Every operation at element e is fp64, rounded once, no contraction in 4 and 5:
+ *  1. row r is present when x[r, e] is not NaN; an infinity is a value.
+ *  2. rows are cut into slabs of S; a slab starts from zero and takes its present rows in row order:
+ *         c[k] += b[r,k] * x[r,e];   G[i][j] += b[r,i] * b[r,j] for j <= i;   n += 1
+ *     (the factors are fp32, so the products are exact and a fused multiply-add has the same bits)
+ *  3. the slab sums are added to totals that start from zero, in slab order.
+ *  4. L D L^T without a square root.  For j = 0 .. K-1:
+ *         s = 0; for p < j in order: s = s + (L[j][p] * L[j][p]) * d[p];        d[j] = G[j][j] - s
+ *         the column is SINGULAR unless d[j] > pivot_tol * G[j][j]   (nothing after it is computed)
+ *         for i > j:  s = 0; for p < j in order: s = s + (L[i][p] * L[j][p]) * d[p];   L[i][j] = (G[i][j] - s) / d[j]
+ *  5. for i ascending:  s = 0; for p < i in order: s = s + L[i][p] * z[p];   z[i] = c[i] - s
+ *     w[i] = z[i] / d[i]
+ *     for i descending: s = 0; for p = i+1 .. K-1 in order: s = s + L[p][i] * a[p];   a[i] = w[i] - s
+ *  6. coef[k, e] = (float)a[k].  All K coefficients of the element are QNAN (0x7fc00000) when n < min_count, the column is
+ *     singular, any (float)a[k] is not finite, or mode is PROPAGATE and n < T.
+ *  7. count (may be NULL): int32, n.
+ * coef[k] lies at k * coef_term_stride elements; below that the layout is dlwpcs_group_mean's output layout (out_stride[] of the
+ * descriptor; out_row_stride is not used), and count has the layout of one term.
+ *
+ * split follows dlwpcs_group_mean.  0: a lane walks its slabs and adds their sums.  1: every (column tile, slab) has its own
+ * workgroups and the slab sums of c and n go to scratch.  < 0: split when there are fewer than 512 column tiles and more than one
+ * slab.  Either way a finishing launch, one element per lane, adds what the first stored in slab order and solves.  gram = 0: a
+ * column with no missing row has the G of every other such column, so that G, its L and d are computed once per call into scratch
+ * (two small launches) and the column only does the two solves; a column with gaps re-reads its rows in the finishing launch for
+ * a G of its own (not in PROPAGATE mode, which answers QNAN).  gram = 1: every column its own G.  gram < 0: the library's choice
+ * (0).  Every combination gives the same bits.  K is served in classes of 1, 2, 4, 8, 16 terms; a chunk of the first launch is
+ * four elements (16-byte loads) up to class 8 where the layout and the pointers allow it, else one.  scratch >=
+ * dlwpcs_time_regression_scratch_bytes(...) of the same arguments, 8-byte aligned: the shared factor, the slab sums of its G
+ * (136 doubles a slab) and the sums of c and n (K doubles and an int32 per element, times the slabs when split).  No atomics, no
+ * allocation, no host synchronisation (capturable); a zero extent launches nothing; n_rows = 0 (src and basis may then be NULL)
+ * answers QNAN and a count of 0.
+ *
+ * dlwpcs_time_regression_plan_info (host only; src and coef are looked at for NULL and for 16-byte alignment, never dereferenced):
+ * info[0] = split, info[1] = gram, info[2] = the term class, info[3] = elements per chunk, info[4] / info[5] = the grid of the
+ * first launch over the rows, info[6] = LDS bytes of a workgroup of it (0), info[7] = rows per slab.
+ *
+ * dlwpcs_time_regression_apply: out[r, e] for r < n_rows from the coefficients and a basis of n_rows rows (which need not be the
+ * rows of the fit: a climatology is evaluated at forecast valid times this way).  f = 0; for k in order: f = f + b[r,k] *
+ * coef[k,e] in fp64 (exact products, fma allowed).  DLWPCS_FIT_FITTED: out = (float)f, src may be NULL.  DLWPCS_FIT_RESIDUAL:
+ * out = (float)((double)x[r,e] - f).  The output is QNAN where a coefficient of the element is NaN or the value is NaN (a NaN x
+ * among them).  src and out are addressed through d; coef[k] of an element lies at k * coef_term_stride + sum of coordinate *
+ * coef_stride[i] (a HOST array of n_inner strides, read during the call; NULL: out_stride[]).  One launch over column tiles x
+ * row slabs: every row is read once, the coefficients of a lane stay in registers.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_REGRESSION_MAX_TERMS 16
+#define DLWPCS_REGRESSION_SLAB_ROWS 512
+#define DLWPCS_FIT_SKIP 0
+#define DLWPCS_FIT_PROPAGATE 1
+#define DLWPCS_FIT_FITTED 0
+#define DLWPCS_FIT_RESIDUAL 1
+size_t dlwpcs_time_regression_scratch_bytes(const dlwpcs_rows_desc *d, int64_t n_rows, int n_terms, int64_t slab_rows, int split);
+int dlwpcs_time_regression(const dlwpcs_rows_desc *d, const float *src, int64_t n_rows, const float *basis /* device */, int n_terms,
+                           int mode, int64_t min_count, double pivot_tol, int64_t slab_rows, int split, int gram, float *coef,
+                           int64_t coef_term_stride, int32_t *count /* may be NULL */, void *scratch, size_t scratch_bytes,
+                           dlwpcs_stream_t stream);
+int dlwpcs_time_regression_plan_info(const dlwpcs_rows_desc *d, const void *src, const void *coef, int64_t n_rows, int n_terms,
+                                     int mode, int64_t min_count, int64_t slab_rows, int split, int gram, int64_t coef_term_stride,
+                                     int32_t info[8]);
+int dlwpcs_time_regression_apply(const dlwpcs_rows_desc *d, const float *src /* may be NULL */, int64_t n_rows,
+                                 const float *basis /* device */, int n_terms, const float *coef, int64_t coef_term_stride,
+                                 const int64_t *coef_stride /* host, may be NULL */, int mode, float *out, dlwpcs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Offline-map remapping (cubed sphere <-> lat-lon, DLWP/remap): one sparse matrix in CSR form applied to a stack of fields,
  *   y[o, r, k] = sum_{j in [row_ptr[r], row_ptr[r+1])} val[j] * x[o, col[j], k]      for r < n_b,
  * the terms of each output added in CSR order with fp32 fma (no atomics, no split rows: bitwise repeatable, and eager and
