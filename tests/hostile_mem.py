@@ -1,6 +1,8 @@
 """
-Exact-size, poisoned, guarded memory for the tests of the convolution family (test_hostile_mem.py, test_gpu_hostile_mem.py).
-Not a test module: imported by the tests that share it.
+Exact-size, poisoned, guarded memory for the GPU tests: written for the convolution family (test_hostile_mem.py,
+test_gpu_hostile_mem.py, whose workspaces hostile_workspaces() replaces), and shared by the tests of the analysis families
+(ensemble, category, quantile, spectrum, the spherical transforms, the time filters and regressions, the score plans), which
+place their operands and results in an Arena.  Not a test module: imported by the tests that share it.
 
 Arena: one uint8 buffer (device or CPU), every byte 0xFF -- NaN as fp32 and as bf16, -1 as int32.  carve() hands out views
 whose first and last byte are exactly the object's; a guard band lies in front of and behind each.  The guard is as large
