@@ -176,6 +176,8 @@ QUANTILE_MAX_PROBS = 16
 TIME_FILTER_MAX_TAPS = 4096
 REGRESSION_MAX_TERMS = 16
 REGRESSION_SLAB_ROWS = 512
+TIME_SPECTRUM_MAX_M = 1728
+TIME_SPECTRUM_SLAB_SEGMENTS = 8
 CATEGORY_MAX_M = 1024
 CATEGORY_MAX_Q = 16
 
@@ -293,6 +295,12 @@ PROTOTYPES = {
                                                  ctypes.c_int64, c_int, c_int, ctypes.c_int64, c_void_p]),
     'dlwpcs_time_regression_apply': (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p,
                                              c_int, c_void_p, c_void_p]),
+    'dlwpcs_time_spectrum_scratch_bytes': (c_size_t, [c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, c_int, c_int, c_int]),
+    'dlwpcs_time_spectrum': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, c_void_p, c_void_p,
+                                     ctypes.c_double, c_int, c_int, c_int, c_int, c_int, ctypes.c_int64, ctypes.c_int64, c_void_p,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_time_spectrum_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, c_int, c_int,
+                                               c_int, c_void_p]),
     'dlwpcs_sparse_map_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),

@@ -2991,8 +2991,157 @@ def time_filter(src, taps, row_axis=0, step=1, origin=0, n_out=None, mode='sum',
     return (out, cnt) if counts else out
 
 
+TIME_SPECTRUM_MAX_M = nat.TIME_SPECTRUM_MAX_M
+TIME_SPECTRUM_SLAB_SEGMENTS = nat.TIME_SPECTRUM_SLAB_SEGMENTS
+_windows = {}               # (window bytes, device) -> float32 device vector
+
+
+def _spectrum_args(n_rows, n_segment, hop, n_freq, min_count, split, who):
+    M = int(n_segment)
+    if M < 2:
+        raise ValueError('%s: segments of %d rows (at least 2)' % (who, M))
+    if M > TIME_SPECTRUM_MAX_M:
+        raise NotImplementedError('%s: segments of %d rows, the device serves 2 .. %d' % (who, M, TIME_SPECTRUM_MAX_M))
+    hop = max(1, M // 2) if hop is None else int(hop)
+    if hop < 1:
+        raise ValueError('%s: hop %d' % (who, hop))
+    K = M // 2 + 1 if n_freq is None else int(n_freq)
+    if not 1 <= K <= M // 2 + 1:
+        raise ValueError('%s: n_freq = %s outside 1 .. M // 2 + 1 = %d' % (who, n_freq, M // 2 + 1))
+    if int(min_count) < 1:
+        raise ValueError('%s: min_count %d (at least 1)' % (who, min_count))
+    if split not in (None, False, True):
+        raise ValueError('%s: split must be None, False or True' % who)
+    n_seg = (n_rows - M) // hop + 1 if n_rows >= M else 0
+    return M, hop, K, int(min_count), -1 if split is None else int(bool(split)), n_seg
+
+
+def spectrum_window_host(window, M):
+    """(M float32 weights, their sum of squares in float64) of a window given as None (ones) or M host values: evaluated in
+    float64 by the caller, rounded to float32 once here"""
+    if window is None:
+        w32 = np.ones(int(M), dtype=np.float32)
+    else:
+        w32 = np.ascontiguousarray(np.asarray(window, dtype=np.float64).reshape(-1), dtype=np.float32)
+    if w32.size != int(M):
+        raise ValueError('time_spectrum: the window has %d weights, the segment %d rows' % (w32.size, M))
+    sw = float((w32.astype(np.float64) ** 2).sum())
+    if not np.all(np.isfinite(w32)) or not sw > 0.:
+        raise ValueError('time_spectrum: the window must be finite in float32 with a positive sum of squares')
+    return w32, sw
+
+
+def _spectrum_window(window, M, dev):
+    w32, sw = spectrum_window_host(window, M)
+    key = (w32.tobytes(), str(torch.device(dev)))
+    hit = _windows.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise nat.NativeError('time_spectrum: first use of a window inside a graph capture (run it once eagerly first)')
+        if len(_windows) >= 64:
+            _windows.clear()
+        hit = torch.from_numpy(w32).to(dev)
+        _windows[key] = hit
+    return hit, sw
+
+
+def time_spectrum_plan(shape, strides, n_segment, hop=None, row_axis=0, n_freq=None, pair=False, coefficients=False, out_perm=None,
+                       split=None, aligned=True):
+    """
+    Which launch time_spectrum (coefficients=True: time_fourier) would make for a source of this shape and these element strides
+    (host only, no device is touched): dict(n_seg, col_tiles, freq_tiles, slabs, tiles = tiles of the launch, grid = persistent
+    workgroups, split, vec = 16-byte loads, lds_bytes).  aligned=False: as for pointers that are not on 16 bytes.  Raises what
+    the call would raise.
+    """
+    n_rows = int(shape[row_axis])
+    M, hop, K, _, sp, n_seg = _spectrum_args(n_rows, n_segment, hop, n_freq, 1, split, 'time_spectrum')
+    d, _ = rows_layout(shape, strides, row_axis, out_perm, 2 * K if coefficients else K)
+    info = (ctypes.c_int64 * 8)()
+    p = (1 << 20) if aligned else (1 << 20) + 4
+    check(lib().dlwpcs_time_spectrum_plan_info(ctypes.byref(d), p, p if pair else None, n_rows, M, hop, K, 1 if coefficients else 0,
+                                               sp, info), 'dlwpcs_time_spectrum_plan_info')
+    return dict(n_seg=n_seg, col_tiles=info[0], freq_tiles=info[1], slabs=info[2], tiles=info[3], grid=info[4], split=bool(info[5]),
+                vec=bool(info[6]), lds_bytes=info[7])
+
+
+def time_spectrum(src, b=None, n_segment=None, hop=None, window=None, row_axis=0, detrend=False, n_freq=None, min_count=1,
+                  out_perm=None, split=None, counts=False):
+    """
+    Welch's power spectrum along `row_axis` of the fp32 device tensor `src` (any strides): the mean over the segments of
+    `n_segment` rows, `hop` rows apart (None: n_segment // 2), of P_f = c_f |X_f|^2 / (M S_w) for the first `n_freq` frequencies
+    (None: all M // 2 + 1), X_f the transform of w_t (x_t - mean) (include/dlwpcs.h states the operations).  window: None (ones)
+    or M host values; detrend: subtract the segment's mean per column.  A segment counts where all its values are finite; the
+    result is NaN where fewer than `min_count` count.  With `b` (same shape) the pair form: a leading axis of four holds P_aa,
+    P_bb, the co-spectrum and the quadrature spectrum, and a segment counts where it is finite in both.  The result has src's dims
+    in the order `out_perm` (default: unchanged) with the frequencies where the row axis stood, contiguous.  split: None = the
+    library chooses, True / False forces slabs of segments to have workgroups of their own (the same bits).  counts=True also
+    returns the int32 number of segments that counted, without the row axis.  At most two launches on the current stream, no host
+    synchronisation.
+    """
+    require_device(src, 'time_spectrum')
+    if src.dtype != torch.float32:
+        raise TypeError('time_spectrum: the source must be float32, got %s' % src.dtype)
+    dev = src.device
+    if b is not None:
+        require_device(b, 'time_spectrum')
+        if b.dtype != torch.float32 or b.device != dev or tuple(b.shape) != tuple(src.shape):
+            raise TypeError('time_spectrum: the second operand must be float32 of the same shape on the same device')
+        if b.stride() != src.stride():
+            src, b = src.contiguous(), b.contiguous()
+    n_rows = int(src.shape[row_axis])
+    M, hop, K, mc, sp, n_seg = _spectrum_args(n_rows, n_rows if n_segment is None else n_segment, hop, n_freq, min_count, split,
+                                              'time_spectrum')
+    d, oshape = rows_layout(src.shape, src.stride(), row_axis, out_perm, K)
+    nd = src.dim()
+    at = (tuple(range(nd)) if out_perm is None else tuple(int(a) % nd for a in out_perm)).index(row_axis % nd)
+    outer = int(np.prod(oshape))
+    out = torch.empty(([4] if b is not None else []) + list(oshape), dtype=torch.float32, device=dev)
+    # the counts have the layout of one frequency row: frequency 0 of an array of the result's shape
+    cnt = torch.empty(oshape, dtype=torch.int32, device=dev) if counts else None
+    if out.numel():
+        with torch.cuda.device(dev):
+            w, sw = _spectrum_window(window, M, dev)
+            tw = spectrum_twiddle(M, dev)
+            nbytes = int(lib().dlwpcs_time_spectrum_scratch_bytes(ctypes.byref(d), n_rows, M, hop, K, 1 if b is not None else 0, sp))
+            scratch = _workspace(nbytes, dev, 'spectrum') if nbytes else None
+            check(lib().dlwpcs_time_spectrum(ctypes.byref(d), src.data_ptr(), ptr(b) or None, n_rows, M, hop, w.data_ptr(),
+                                             tw.data_ptr(), sw, 1 if detrend else 0, K, mc, 0, sp, outer, 0, out.data_ptr(),
+                                             ptr(cnt) or None, ptr(scratch) or None, nbytes, stream_ptr()), 'dlwpcs_time_spectrum')
+    return (out, cnt.select(at, 0)) if counts else out
+
+
+def time_fourier(src, n_segment=None, hop=None, window=None, row_axis=0, detrend=False, n_freq=None, out_perm=None):
+    """
+    The transform of time_spectrum without the averaging: X_f = sum_t w_t (x_t - mean) exp(-2 pi i f t / M) per segment, unscaled.
+    The result is float32 with a leading segment axis, then src's dims in the order `out_perm` with the row axis replaced by
+    (frequency, 2 = Re | Im), contiguous; a segment that holds a value that is not finite is NaN in its column.  n_segment=None:
+    one segment over the whole axis.  One launch on the current stream.
+    """
+    require_device(src, 'time_fourier')
+    if src.dtype != torch.float32:
+        raise TypeError('time_fourier: the source must be float32, got %s' % src.dtype)
+    dev = src.device
+    n_rows = int(src.shape[row_axis])
+    M, hop, K, _, _, n_seg = _spectrum_args(n_rows, n_rows if n_segment is None else n_segment, hop, n_freq, 1, None, 'time_fourier')
+    d, oshape = rows_layout(src.shape, src.stride(), row_axis, out_perm, 2 * K)
+    nd = src.dim()
+    at = (tuple(range(nd)) if out_perm is None else tuple(int(a) % nd for a in out_perm)).index(row_axis % nd)
+    outer = int(np.prod(oshape))
+    part = int(d.out_row_stride)
+    d.out_row_stride = 2 * part
+    out = torch.empty([n_seg] + list(oshape), dtype=torch.float32, device=dev)
+    if out.numel():
+        with torch.cuda.device(dev):
+            w, sw = _spectrum_window(window, M, dev)
+            tw = spectrum_twiddle(M, dev)
+            check(lib().dlwpcs_time_spectrum(ctypes.byref(d), src.data_ptr(), None, n_rows, M, hop, w.data_ptr(), tw.data_ptr(), sw,
+                                             1 if detrend else 0, K, 1, 1, -1, outer, part, out.data_ptr(), None, None, 0,
+                                             stream_ptr()), 'dlwpcs_time_spectrum')
+    return out.view([n_seg] + list(oshape[:at]) + [K, 2] + list(oshape[at + 1:]))
+
+
 REGRESSION_MAX_TERMS = nat.REGRESSION_MAX_TERMS
-_FIT_MODES = {'skip': 0, 'propagate': 1}
+_FIT_MODES ={'skip': 0, 'propagate': 1}
 _FIT_FORMS = {None: -1, False: 0, True: 1}
 
 

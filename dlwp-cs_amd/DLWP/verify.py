@@ -2615,3 +2615,346 @@ def harmonic_climatology(ds, n_harmonics=4, trend=False, min_count=None):
     coef = _fit(ds, _fit_basis32(basis, int(_raw(ds).shape[axis]), 'harmonic_climatology'), axis, 'skip', min_count, False,
                 'harmonic_climatology')
     return HarmonicClimatology(coef, n_harmonics, trend, span)
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# Spectra along time: Welch's power spectrum, cross-spectra and coherence, wavenumber-frequency diagrams
+# --------------------------------------------------------------------------------------------------------------------- #
+#
+# A series is cut into segments of n_segment rows, `hop` rows apart; a segment is (optionally) freed of its mean, multiplied by
+# a window w and transformed: X_f = sum_t w_t x_t exp(-2 pi i f t / M).  P_f = c_f |X_f|^2 / (M S_w), S_w = sum w_t^2, c_f = 1 at
+# f = 0 and at the Nyquist frequency of an even M, else 2, so that sum_f P_f is the window-weighted mean square of the segment;
+# the result is the mean over the segments whose values are all finite.  numpy values are transformed on the host in float64
+# with np.fft.rfft, device tensors by dlwpcs_time_spectrum (fp32 on the matrix cores, fp64 segment sums in a fixed order) and
+# stay there as float32; neither path falls back to the other.  Both use the window rounded to float32.  The new dim is
+# 'frequency', in cycles per row.
+
+TimeCrossSpectrum = namedtuple('TimeCrossSpectrum', ['power_a', 'power_b', 'co', 'quad'])
+WavenumberFrequencySpectrum = namedtuple('WavenumberFrequencySpectrum', ['eastward', 'westward'])
+
+
+def spectral_window(window, n):
+    """
+    n float64 window weights: 'boxcar' (ones), 'hann' (periodic: 0.5 - 0.5 cos(2 pi t / n), the form that overlaps to a constant
+    at hop n / 2), or an array of n weights, returned as it is.  Host only.
+    """
+    n = int(n)
+    if n < 1:
+        raise ValueError('spectral_window: %d weights' % n)
+    if isinstance(window, str):
+        if window == 'boxcar':
+            return np.ones(n, dtype=np.float64)
+        if window == 'hann':
+            return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n, dtype=np.float64) / n)
+        raise ValueError("spectral_window: 'window' must be 'boxcar', 'hann' or an array of weights, got %r" % (window,))
+    w = np.asarray(_host(window), dtype=np.float64).reshape(-1)
+    if w.size != n:
+        raise ValueError('spectral_window: %d weights for segments of %d rows' % (w.size, n))
+    return w
+
+
+def _welch_args(x, n_segment, axis, hop, window, detrend, n_freq, min_count, name, whole=False):
+    """(axis, M, hop, float64 window rounded to float32, its sum of squares, detrend flag, K, min_count)"""
+    ax = _filter_axis(x, axis, 'time')
+    T = int(_raw(x).shape[ax])
+    if n_segment is None and not whole:
+        raise ValueError('%s: n_segment is needed' % name)
+    M = T if n_segment is None else int(n_segment)
+    if M < 2:
+        raise ValueError('%s: segments of %d rows (at least 2)' % (name, M))
+    hop = max(1, M // 2) if hop is None else int(hop)
+    if hop < 1:
+        raise ValueError('%s: hop must be at least 1, got %d' % (name, hop))
+    if detrend not in (None, 'constant'):
+        raise ValueError("%s: 'detrend' must be None or 'constant' (remove a linear trend from the whole series with detrend())" % name)
+    K = M // 2 + 1 if n_freq is None else int(n_freq)
+    if not 1 <= K <= M // 2 + 1:
+        raise ValueError('%s: n_freq = %s outside 1 .. n_segment // 2 + 1 = %d' % (name, n_freq, M // 2 + 1))
+    if int(min_count) < 1:
+        raise ValueError('%s: min_count must be at least 1, got %d' % (name, min_count))
+    with np.errstate(over='ignore'):
+        w = spectral_window(window, M).astype(np.float32).astype(np.float64)
+    sw = float((w ** 2).sum())
+    if not np.all(np.isfinite(w)) or not sw > 0.:
+        raise ValueError('%s: the window must be finite in float32 with a positive sum of squares' % name)
+    return ax, M, hop, w, sw, detrend == 'constant', K, int(min_count)
+
+
+def _segment_count(T, M, hop):
+    return (T - M) // hop + 1 if T >= M else 0
+
+
+def _fourier_host(v, M, hop, w, detrend, K):
+    """(coefficients (n_seg, K, ...) complex128, counted (n_seg, ...) bool) of v (T, ...) float64"""
+    n_seg = _segment_count(v.shape[0], M, hop)
+    X = np.full((n_seg, K) + v.shape[1:], complex(np.nan, np.nan), dtype=np.complex128)
+    ok = np.zeros((n_seg,) + v.shape[1:], dtype=bool)
+    ws = w.reshape((M,) + (1,) * (v.ndim - 1))
+    for s in range(n_seg):
+        seg = v[s * hop:s * hop + M]
+        ok[s] = np.isfinite(seg).all(axis=0)
+        z = np.where(ok[s], seg, 0.0)
+        if detrend:
+            z = z - z.mean(axis=0)
+        X[s] = np.where(ok[s], np.fft.rfft(z * ws, axis=0)[:K], complex(np.nan, np.nan))
+    return X, ok
+
+
+def _spectral_scale(M, K, sw):
+    c = np.full(K, 2.0)
+    c[0] = 1.0
+    if M % 2 == 0 and K == M // 2 + 1:
+        c[-1] = 1.0
+    return c / (M * sw)
+
+
+def _welch_host(a, b, ax, M, hop, w, sw, detrend, K, min_count):
+    """numpy twin of dlwpcs_time_spectrum: (quantities (nq, ...) float64 with K frequencies at `ax`, counts int32 without it)"""
+    A, ok = _fourier_host(np.moveaxis(np.asarray(a, dtype=np.float64), ax, 0), M, hop, w, detrend, K)
+    if b is not None:
+        B, okb = _fourier_host(np.moveaxis(np.asarray(b, dtype=np.float64), ax, 0), M, hop, w, detrend, K)
+        ok = ok & okb
+    q = [A.real ** 2 + A.imag ** 2]
+    if b is not None:
+        cross = A * np.conj(B)
+        q += [B.real ** 2 + B.imag ** 2, cross.real, cross.imag]
+    n = ok.sum(axis=0).astype(np.int32)
+    scale = _spectral_scale(M, K, sw).reshape((K,) + (1,) * (A.ndim - 2))
+    with np.errstate(invalid='ignore', divide='ignore'):
+        out = np.stack([np.where(n >= min_count, np.where(ok[:, None], x, 0.0).sum(axis=0) * scale / np.maximum(n, 1), np.nan)
+                        for x in q])
+    return np.moveaxis(out, 1, ax + 1), n
+
+
+def _device_f32(x):
+    import torch
+    v = _raw(x)
+    return v if v.dtype == torch.float32 else v.to(torch.float32)
+
+
+def _welch(a, b, n_segment, axis, hop, window, detrend, n_freq, min_count, name):
+    """(quantities (nq, ...), counts, axis, M): numpy float64 for host values, float32 device tensors for device values"""
+    if b is not None:
+        _check_labels(a, b)
+        if tuple(_raw(a).shape) != tuple(_raw(b).shape):
+            raise ValueError('%s: the two series %s and %s must have one shape' % (name, tuple(_raw(a).shape), tuple(_raw(b).shape)))
+    ax, M, hop, w, sw, dt, K, mc = _welch_args(a, n_segment, axis, hop, window, detrend, n_freq, min_count, name)
+    if _on_device(a, b):
+        import torch
+        from . import ops as dops
+        dev = next(_raw(x).device for x in (a, b) if x is not None and _is_tensor(_raw(x)) and _raw(x).is_cuda)
+        with torch.cuda.device(dev):
+            at = _dev_operand(a, dev)
+            bt = _dev_operand(b, dev) if b is not None else None
+            out, cnt = dops.time_spectrum(at, bt, n_segment=M, hop=hop, window=w, row_axis=ax, detrend=dt, n_freq=K, min_count=mc,
+                                          counts=True)
+        return (out if b is not None else out[None]), cnt, ax, M
+    out, cnt = _welch_host(_host(a), None if b is None else _host(b), ax, M, hop, w, sw, dt, K, mc)
+    return out, cnt, ax, M
+
+
+def _freq_label(x, axis, values, M, name, renamed=None, lead=()):
+    """`values` labelled like x with 'frequency' (cycles per row) where `axis` stood; renamed: {axis: (dim, coordinate)} for
+    further axes that changed their meaning; lead: names of leading dims of `values` that x does not have"""
+    if not hasattr(x, 'dims'):
+        return values
+    renamed = dict(renamed or {})
+    renamed[axis] = ('frequency', np.arange(values.shape[len(lead) + axis]) / float(M))
+    dims, coords = [], {}
+    for i, d in enumerate(tuple(x.dims)):
+        if i in renamed:
+            d, c = renamed[i]
+            if c is not None:
+                coords[d] = c
+        elif d in getattr(x, 'coords', {}):
+            coords[d] = _coord(x, d)
+        dims.append(d)
+    out = Forecast(values, tuple(lead) + tuple(dims), coords, name=name)
+    if hasattr(x, 'lat'):
+        out.lat = x.lat
+    return out
+
+
+def _drop_label(x, axis, values, name):
+    """`values` (x's shape without `axis`) labelled like x without that dim"""
+    if not hasattr(x, 'dims'):
+        return values
+    dims = tuple(d for i, d in enumerate(x.dims) if i != axis)
+    coords = {d: _coord(x, d) for d in dims if d in getattr(x, 'coords', {})}
+    return Forecast(values, dims, coords, name=name)
+
+
+def time_spectrum(x, n_segment, axis=None, hop=None, window='hann', detrend='constant', n_freq=None, min_count=1, return_count=False):
+    """
+    Welch's power spectrum of a series along time: the mean over segments of `n_segment` rows of P_f = c_f |X_f|^2 / (M S_w),
+    whose sum over all frequencies is the window-weighted mean square of a segment (its variance with detrend='constant').
+
+    :param x: a `Forecast` (or anything with `.dims`, `.coords`, `.values`), a numpy array or a torch tensor.  Values on a HIP
+        device are transformed there (dlwpcs_time_spectrum) and the float32 result stays there; numpy values are transformed on
+        the host in float64
+    :param n_segment: rows per segment, M (on the device at most 1728)
+    :param axis: the axis to transform, a position or a dim name; None: the 'time' dim of a labelled input, else axis 0
+    :param hop: rows between the starts of neighbouring segments; None: n_segment // 2, the half overlap that suits 'hann'
+    :param window: 'hann' (periodic), 'boxcar' or an array of n_segment weights (`spectral_window`); used rounded to float32
+    :param detrend: 'constant': every segment loses its own mean; None: nothing.  A linear trend is removed from the whole series
+        with the existing `detrend()` first
+    :param n_freq: return the first n_freq frequencies only (1 .. n_segment // 2 + 1)
+    :param min_count: a segment counts where all its values are finite; NaN where fewer than min_count segments count (also where
+        the series is shorter than one segment)
+    :param return_count: also return the int32 number of segments that counted (the input's shape without the time axis)
+    :return: labelled like the input with the dim 'frequency' (cycles per row) where the time axis stood
+    """
+    out, cnt, ax, M = _welch(x, None, n_segment, axis, hop, window, detrend, n_freq, min_count, 'time_spectrum')
+    res = _freq_label(x, ax, out[0], M, 'time_spectrum')
+    return (res, _drop_label(x, ax, cnt, 'time_spectrum_count')) if return_count else res
+
+
+def time_cross_spectrum(a, b, n_segment, axis=None, hop=None, window='hann', detrend='constant', n_freq=None, min_count=1,
+                        return_count=False):
+    """
+    The power spectra of two series of one shape and their cross-spectrum along time, averaged over the segments that are finite
+    in both: TimeCrossSpectrum(power_a, power_b, co, quad) with co + i quad = c_f A_f conj(B_f) / (M S_w).  Arguments as for
+    `time_spectrum`.
+    """
+    out, cnt, ax, M = _welch(a, b, n_segment, axis, hop, window, detrend, n_freq, min_count, 'time_cross_spectrum')
+    res = TimeCrossSpectrum(*[_freq_label(a, ax, out[i], M, n) for i, n in enumerate(TimeCrossSpectrum._fields)])
+    return (res, _drop_label(a, ax, cnt, 'time_cross_spectrum_count')) if return_count else res
+
+
+def time_coherence(a, b, n_segment, axis=None, hop=None, window='hann', detrend='constant', n_freq=None, min_count=1,
+                   return_count=False):
+    """
+    Squared coherence (co^2 + quad^2) / (power_a power_b) per frequency, formed from the segment-AVERAGED spectra of
+    `time_cross_spectrum` (per segment it would be identically 1): 1 where the forecast holds the verification's phase over the
+    segments, near 1 / segments where the two are unrelated.  NaN where either power is 0.  Arguments as for `time_spectrum`.
+    """
+    out, cnt, ax, M = _welch(a, b, n_segment, axis, hop, window, detrend, n_freq, min_count, 'time_coherence')
+    if _is_tensor(out):
+        den = out[0] * out[1]
+        coh = (out[2] ** 2 + out[3] ** 2) / den
+        coh = coh.masked_fill(den == 0, float('nan'))
+    else:
+        with np.errstate(invalid='ignore', divide='ignore'):
+            coh = np.where(out[0] * out[1] == 0, np.nan, (out[2] ** 2 + out[3] ** 2) / (out[0] * out[1]))
+    res = _freq_label(a, ax, coh, M, 'time_coherence')
+    return (res, _drop_label(a, ax, cnt, 'time_coherence_count')) if return_count else res
+
+
+def time_fourier(x, axis=None, n_segment=None, hop=None, window='boxcar', detrend=None, n_freq=None):
+    """
+    The complex coefficients X_f = sum_t w_t x_t exp(-2 pi i f t / M) per segment, unscaled: what `time_spectrum` averages the
+    squares of, and what a transform along one axis feeds to a second transform along another.  n_segment=None: one segment over
+    the whole axis (on the device at most 1728 rows) and no segment axis; else a leading 'segment' axis.  A segment that holds a
+    value that is not finite is NaN.  complex128 for host values; complex64 on the device for device values.  Other arguments as
+    for `time_spectrum`.
+    """
+    ax, M, hop, w, sw, dt, K, _ = _welch_args(x, n_segment, axis, hop, window, detrend, n_freq, 1, 'time_fourier', whole=True)
+    v = _raw(x)
+    if _is_tensor(v) and v.is_cuda:
+        import torch
+        from . import ops as dops
+        with torch.cuda.device(v.device):
+            z = dops.time_fourier(_device_f32(x), n_segment=M, hop=hop, window=w, row_axis=ax, detrend=dt, n_freq=K)
+            out = torch.view_as_complex(z.movedim(ax + 2, -1).contiguous())
+    else:
+        X, _ = _fourier_host(np.moveaxis(np.asarray(_host(v), dtype=np.float64), ax, 0), M, hop, w, dt, K)
+        out = np.moveaxis(X, 1, ax + 1)
+    if n_segment is None:
+        return _freq_label(x, ax, out[0], M, 'time_fourier')
+    return _freq_label(x, ax, out, M, 'time_fourier', lead=('segment',))
+
+
+def _mirror(x, lat_axis, component, name):
+    """(x + flip) / 2 or (x - flip) / 2 along lat_axis: the part symmetric or antisymmetric about the equator"""
+    if component not in ('symmetric', 'antisymmetric'):
+        raise ValueError("%s: 'component' must be None, 'symmetric' or 'antisymmetric'" % name)
+    if lat_axis is None:
+        raise ValueError('%s: a component needs a latitude axis' % name)
+    if hasattr(x, 'coords') and hasattr(x, 'dims') and x.dims[lat_axis] in x.coords:
+        lat = np.asarray(_coord(x, x.dims[lat_axis]), dtype=np.float64)
+        if not np.allclose(lat, -lat[::-1], rtol=0., atol=1e-6 * max(1., float(np.abs(lat).max()))):
+            raise ValueError('%s: the latitudes do not mirror about the equator' % name)
+    v = _raw(x)
+    f = v.flip(lat_axis) if _is_tensor(v) else np.flip(v, lat_axis)
+    return (v + f) * 0.5 if component == 'symmetric' else (v - f) * 0.5
+
+
+def wavenumber_frequency_spectrum(x, n_segment, axis=None, lon_axis=-1, lat_axis=None, component=None, hop=None, window='hann',
+                                  detrend='constant', n_wave=None, n_freq=None, min_count=1, return_count=False):
+    """
+    The wavenumber-frequency power of a series of fields (Wheeler and Kiladis 1999): per zonal wavenumber k and frequency f the
+    variance that travels eastward and westward, WavenumberFrequencySpectrum(eastward, westward), each with 'frequency' where the
+    time axis stood and 'wavenumber' where longitude stood; every other axis (latitude) is kept: reducing it is the caller's.
+
+    Stage 1 is the zonal transform X_k(t) of every row (`time_fourier` along longitude: one boxcar segment); stage 2 the pair form
+    of `time_spectrum` along time on its real and imaginary planes a, b (window, detrend, hop and the missing-value rule as there),
+    and with c_k the factor of `zonal_spectrum`
+        westward = (P_aa + P_bb + 2 Q) / 2 * c_k / L^2,      eastward = (P_aa + P_bb - 2 Q) / 2 * c_k / L^2,
+    Q the quadrature spectrum.  A wave cos(k lon - 2 pi f t / M) lands in eastward[f, k] alone; eastward.sum() + westward.sum()
+    over all k and f is the window-weighted mean square of the segments; f = 0 and the Nyquist frequency hold half in each.
+
+    :param lon_axis: the longitude axis (the dim 'lon' of a labelled input); on the device at most 1728 longitudes
+    :param lat_axis: the latitude axis, needed for `component` only (None: the dim 'lat' of a labelled input, if any)
+    :param component: None, or 'symmetric' / 'antisymmetric': (x +- x mirrored about the equator) / 2 is analysed; the latitudes
+        must mirror
+    :param n_wave: the first n_wave zonal wavenumbers only (1 .. L // 2 + 1)
+    Other arguments as for `time_spectrum`.  The same pair form serves any complex series c(t): for `spherical_analysis`
+    coefficients `coef` (..., 2) interleaved, time_cross_spectrum(coef[..., 0], coef[..., 1], n_segment) reads the two planes in
+    place (inner stride 2) and (power_a + power_b -+ 2 quad) / 2 are the powers of the two directions of rotation.
+    """
+    name = 'wavenumber_frequency_spectrum'
+    ax = _filter_axis(x, axis, 'time')
+    lon = _lon_axis(x, lon_axis)
+    nd = len(_raw(x).shape)
+    if lon == ax:
+        raise ValueError('%s: time and longitude are one axis' % name)
+    if lat_axis is None and hasattr(x, 'dims') and 'lat' in tuple(x.dims):
+        lat_axis = tuple(x.dims).index('lat')
+    if lat_axis is not None:
+        lat_axis = _axes(lat_axis, nd)[0]
+        if lat_axis in (ax, lon):
+            raise ValueError('%s: the latitude axis is the time or the longitude axis' % name)
+    L = int(_raw(x).shape[lon])
+    if L < 2:
+        raise ValueError('%s: %d longitudes (at least 2)' % (name, L))
+    Kw = L // 2 + 1 if n_wave is None else int(n_wave)
+    if not 1 <= Kw <= L // 2 + 1:
+        raise ValueError('%s: n_wave = %s outside 1 .. L // 2 + 1 = %d' % (name, n_wave, L // 2 + 1))
+    _, M, hop, w, sw, dt, K, mc = _welch_args(x, n_segment, ax, hop, window, detrend, n_freq, min_count, name)
+    v = _raw(x) if component is None else _mirror(x, lat_axis, component, name)
+    ck = np.full(Kw, 2.0)
+    ck[0] = 1.0
+    if L % 2 == 0 and Kw == L // 2 + 1:
+        ck[-1] = 1.0
+    shape = [1] * nd
+    shape[lon] = Kw
+    ck = (ck / (2.0 * float(L) ** 2)).reshape(shape)
+    if _is_tensor(v) and v.is_cuda:
+        import torch
+        from . import ops as dops
+        with torch.cuda.device(v.device):
+            src = v if v.dtype == torch.float32 else v.to(torch.float32)
+            z = dops.time_fourier(src, row_axis=lon, n_freq=Kw)[0].movedim(lon + 1, -1)     # (..., wavenumber, ..., 2)
+            p, cnt = dops.time_spectrum(z[..., 0], z[..., 1], n_segment=M, hop=hop, window=w, row_axis=ax, detrend=dt, n_freq=K,
+                                        min_count=mc, counts=True)
+            ckt = torch.from_numpy(ck.astype(np.float32)).to(v.device)
+            both = (p[0] + p[1]) * ckt
+            twoq = (2.0 * p[3]) * ckt
+            east, west = both - twoq, both + twoq
+    else:
+        h = np.asarray(_host(v), dtype=np.float64)
+        rows_ok = np.isfinite(h).all(axis=lon, keepdims=True)
+        z = np.fft.rfft(np.where(rows_ok, h, 0.0), axis=lon)
+        z = np.where(rows_ok, np.take(z, np.arange(Kw), axis=lon), complex(np.nan, np.nan))
+        p, cnt = _welch_host(z.real, z.imag, ax, M, hop, w, sw, dt, K, mc)
+        east, west = (p[0] + p[1] - 2.0 * p[3]) * ck, (p[0] + p[1] + 2.0 * p[3]) * ck
+    ren = {lon: ('wavenumber', np.arange(Kw))}
+    res = WavenumberFrequencySpectrum(_freq_label(x, ax, east, M, 'eastward', ren), _freq_label(x, ax, west, M, 'westward', ren))
+    if not return_count:
+        return res
+    if hasattr(x, 'dims'):
+        dims = tuple('wavenumber' if i == lon else d for i, d in enumerate(x.dims) if i != ax)
+        coords = {d: _coord(x, d) for d in dims if d in getattr(x, 'coords', {})}
+        coords['wavenumber'] = np.arange(Kw)
+        cnt = Forecast(cnt, dims, coords, name=name + '_count')
+    return res, cnt

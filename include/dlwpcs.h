@@ -728,6 +728,64 @@ int dlwpcs_time_filter_plan_info(const dlwpcs_rows_desc *d, const void *src, con
                                  int64_t step, int64_t n_out, int mode, int form, int64_t slab_rows, int32_t info[8]);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Spectra along the row axis (DLWP/verify.py time_spectrum, time_cross_spectrum, time_coherence, time_fourier,
+ * wavenumber_frequency_spectrum): Welch's segment-averaged spectrum over the T = n_rows rows of a row set (dlwpcs_rows_desc:
+ * strides in elements, lanes along the last inner dim).  Segment s holds the rows s * hop .. s * hop + M - 1, M = n_segment,
+ * 2 <= M <= DLWPCS_TIME_SPECTRUM_MAX_M (more: DLWPCS_E_UNSUPPORTED), hop >= 1; there are n_seg = T >= M ? (T - M) / hop + 1 : 0
+ * of them.  window: M fp32 on the DEVICE, finite, trusted; window_power = S_w = sum w_t^2 > 0, taken in fp64 from the fp32 table
+ * by the caller.  twiddle: the table of dlwpcs_zonal_spectrum for L = M, {cos, -sin}(2 pi m / M), 8-byte aligned.
+ *
+ * Definition.  Per column and segment, in fp32, every operation rounded once, no contraction:
+ *     detrend = 1:  mean = (float)(sum / (double)M), sum the fp64 sum of the segment's rows in row order;  detrend = 0: mean = 0.f
+ *     y_t = w_t * (x_t - mean)
+ *     Re X_f = fma chain over t = 0 .. M - 1 of y_t * cos(2 pi ft / M),  Im X_f = ... of y_t * (-sin(2 pi ft / M)), from zero, the
+ *     twiddles read from the table at (f t) mod M (v_mfma_f32_32x32x2_f32)
+ * for the K = n_freq frequencies f = 0 .. K - 1 (n_freq = 0: all M / 2 + 1).  P_f = c_f |X_f|^2 / (M S_w) with c_f = 1 at f = 0
+ * and at f = M / 2 for even M, else 2: sum_f P_f = sum_t y_t^2 / S_w, and with a window of ones and detrend = 0 it is the
+ * convention of dlwpcs_zonal_spectrum.  A segment COUNTS for a column when all its M values are finite (pair form: in both
+ * operands); an infinity makes it missing.
+ *
+ * mode DLWPCS_SPECTRUM_POWER, b == NULL: out[f * out_row_stride + column] (the descriptor's out strides) is the mean of P_f over
+ * the segments that count, NaN (0x7fc00000) where fewer than min_count >= 1 count.  b != NULL (same descriptor, own pointer), the
+ * pair form: quantity q lies at q * out_outer_stride: P_aa, P_bb, the co-spectrum c_f Re(A conj B) / (M S_w) and the quadrature
+ * spectrum c_f Im(A conj B) / (M S_w); quantity 0 has the bits of the single form on a.  count (may be NULL): int32 per column
+ * in the layout of one frequency row, the segments that counted.
+ * Summation order, whatever the plan: per (column, frequency, quantity) the fp32 products Re^2 + Im^2 (fma(Im, Im, Re * Re), and
+ * likewise the other three) are widened to fp64 and added one by one in segment order from zero inside slabs of
+ * DLWPCS_TIME_SPECTRUM_SLAB_SEGMENTS segments, the slab sums are added in slab order from zero, and the stored value is
+ * (float)((total * (c_f / (M S_w))) / n), n the segments that counted.  split = 0: a workgroup walks the slabs of its tile.
+ * split = 1: slabs get workgroups of their own and write their sums to scratch, a second launch adds them -- the same additions,
+ * the same bits; for few columns under many segments.  split < 0: chosen.  scratch >= dlwpcs_time_spectrum_scratch_bytes(...) of the
+ * same arguments (pair = 1 for the pair form), 8-byte aligned (0 bytes: may be NULL).
+ *
+ * mode DLWPCS_SPECTRUM_COEFFICIENTS (b must be NULL): no averaging; Re X_f of segment s lies at s * out_outer_stride +
+ * f * out_row_stride + column, Im X_f out_part_stride further, unscaled; a segment that does not count gives NaN.  min_count,
+ * split, count and scratch are not used.
+ *
+ * A launch of a fixed number of persistent workgroups strides over the list of tiles (32 columns x 128 frequencies x slab); which
+ * workgroup computes a tile influences no bit.  No atomics, no host synchronisation, no allocation, at most two launches
+ * (capturable).  n_seg = 0: the averaged forms store NaN and count 0, the coefficient form launches nothing.
+ *
+ * dlwpcs_time_spectrum_plan_info (host only; a and b are looked at for NULL and 16-byte alignment, never dereferenced):
+ * info[0] = column tiles, info[1] = frequency tiles, info[2] = slabs, info[3] = tiles of the launch, info[4] = workgroups,
+ * info[5] = split, info[6] = 1 for 16-byte loads, info[7] = LDS bytes of a workgroup.  Returns what the entry point would return
+ * for the same arguments.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_TIME_SPECTRUM_MAX_M 1728
+#define DLWPCS_TIME_SPECTRUM_SLAB_SEGMENTS 8
+#define DLWPCS_SPECTRUM_POWER 0
+#define DLWPCS_SPECTRUM_COEFFICIENTS 1
+size_t dlwpcs_time_spectrum_scratch_bytes(const dlwpcs_rows_desc *d, int64_t n_rows, int n_segment, int64_t hop, int n_freq,
+                                          int pair, int split);
+int dlwpcs_time_spectrum(const dlwpcs_rows_desc *d, const float *a, const float *b /* NULL: single form */, int64_t n_rows,
+                         int n_segment, int64_t hop, const float *window /* device */, const float *twiddle /* device */,
+                         double window_power, int detrend, int n_freq, int min_count, int mode, int split,
+                         int64_t out_outer_stride, int64_t out_part_stride, float *out, int32_t *count /* may be NULL */,
+                         void *scratch, size_t scratch_bytes, dlwpcs_stream_t stream);
+int dlwpcs_time_spectrum_plan_info(const dlwpcs_rows_desc *d, const void *a, const void *b, int64_t n_rows, int n_segment,
+                                   int64_t hop, int n_freq, int mode, int split, int64_t info[8]);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Least-squares fits along the row axis (DLWP/verify.py time_regression, detrend, harmonic_climatology): per element of a row set
  * (dlwpcs_rows_desc: strides in elements, lanes along the last inner dim) the K coefficients of the basis that fit the rows
  * present best.  x: T = n_rows fp32 rows.  basis: a contiguous (T, K) fp32 DEVICE array, finite, trusted, 1 <= K <=
