@@ -17,39 +17,9 @@ Not built (raises NotImplementedError): imputation, generators whose inputs are 
 """
 import numpy as np
 
+from ..labelled import Forecast
 from .models import DLWPFunctional
 from .packing import PackedSeries
-
-
-class Forecast(object):
-    """values + named dims + coordinate arrays (the subset of xarray.DataArray the verification code reads)."""
-
-    def __init__(self, values, dims, coords, name='forecast'):
-        self.values = values
-        self.dims = tuple(dims)
-        self.coords = dict(coords)
-        self.name = name
-
-    @property
-    def shape(self):
-        return self.values.shape
-
-    def __array__(self, dtype=None, copy=None):
-        v = self.values
-        if hasattr(v, 'detach'):                                  # device-resident values (predict(keep_on_device=True))
-            v = v.detach().cpu().numpy()
-        return np.asarray(v, dtype=dtype)
-
-    def isel(self, **indexers):
-        idx = [slice(None)] * self.values.ndim
-        coords = dict(self.coords)
-        for k, v in indexers.items():
-            ax = self.dims.index(k)
-            idx[ax] = v
-            coords[k] = np.asarray(self.coords[k])[v]
-        vals = self.values[tuple(idx)]
-        dims = tuple(d for d, i in zip(self.dims, idx) if not isinstance(i, (int, np.integer)))
-        return Forecast(vals, dims, {d: coords[d] for d in dims if d in coords}, self.name)
 
 
 def _values(x):
@@ -308,7 +278,7 @@ class TimeSeriesEstimator(object):
         A generator over a DLWP.model.PackedSeries: the output variables are first decoded into an fp32 temporary of
         (rows, output variables, *space) -- beside the codes in HBM with a device-resident generator -- and that is reduced.
         """
-        from ..verify import _climatology
+        from ..verify.climatology import _climatology
         g = self.generator
         if self._sample_times is None:
             raise ValueError('TimeSeriesEstimator.climatology: the generator has no dates; pass sample_times')

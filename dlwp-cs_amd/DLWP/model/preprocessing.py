@@ -11,37 +11,13 @@ Differences from the reference: the statistics file is not read (the tables are 
 of this stack), the sums are fp64 where the reference adds float32 batch sums, and `Preprocessor`, `get_constants` and
 `prepare_data_array` (xarray / netCDF4 file handling) are not built.
 """
-import sys
-
 import numpy as np
 
-from .extensions import Forecast
-
-
-# DLWP.verify has the same three helpers; it imports DLWP.model (for Forecast) before it defines them, so this module, which
-# DLWP.model imports, cannot take them from there: `import DLWP.verify` as a process's first import would find a cycle
-def _is_tensor(x):
-    torch = sys.modules.get('torch')
-    return torch is not None and isinstance(x, torch.Tensor)
-
-
-def _raw(x):
-    """the array behind a wrapped input (a Forecast / DataArray: `.values`), else x itself"""
-    if isinstance(x, np.ndarray) or _is_tensor(x):
-        return x
-    return getattr(x, 'values', x)
-
-
-def _host(x):
-    r = _raw(x)
-    if hasattr(r, 'detach'):
-        r = r.detach().cpu().numpy()
-    return np.asarray(r)
+from ..labelled import Forecast, host as _host, is_tensor as _is_tensor, on_device, raw as _raw
 
 
 def _device_values(x):
-    v = _raw(x)
-    return v if _is_tensor(v) and v.is_cuda else None
+    return _raw(x) if on_device(x) else None
 
 
 def _as_rows(v):

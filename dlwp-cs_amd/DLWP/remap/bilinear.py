@@ -21,10 +21,9 @@ quadrilateral of kind (a).  Outside, the rungs decide: they are not coordinate l
 from the cell the along-edge coordinate names, by the sign of P . (V_in x V_out), until P lies between two rungs; a point
 beyond the last rung of both strips it could belong to lies in the corner's triangle.
 """
-import sys
-
 import numpy as np
 
+from ..labelled import is_tensor as _is_tensor
 from .grid import CubeSphereGrid, LatLonGrid, default_frames
 
 SIDES = ('west', 'east', 'south', 'north')       # side 0: width index 0, 1: width N - 1, 2: height 0, 3: height N - 1
@@ -314,8 +313,3 @@ def bilinear_map(cube, lat=None, lon=None, *, latlon=None, device=None):
     return OfflineMap(row, col.ravel().astype(np.int64) + 1, w.ravel(), cube.n_cells, n,
                       src_grid_dims=np.array([cube.n_cells], np.int32), dst_grid_dims=dims, yc_a=cube.lat.ravel(),
                       xc_a=cube.lon.ravel(), yc_b=yc, xc_b=xc, dst_cells=as_cells)
-
-
-def _is_tensor(x):
-    torch = sys.modules.get('torch')
-    return torch is not None and isinstance(x, torch.Tensor)

@@ -5,10 +5,10 @@ them into CSR form and applies the matrix to stacks of fields: on the host in fp
 the dlwpcs_sparse_map_apply kernel (device tensors).
 """
 import os
-import sys
 
 import numpy as np
 
+from ..labelled import is_tensor as _is_tensor
 from .netcdf_classic import NetCDFClassic, write_netcdf
 
 _REQUIRED = ('row', 'col', 'S')
@@ -321,11 +321,6 @@ class OfflineMap(object):
             setattr(out, a, getattr(self, a))
         out.frac_b = frac.astype(np.float64)
         return out, frac.reshape(self.dst_shape)
-
-
-def _is_tensor(x):
-    torch = sys.modules.get('torch')
-    return torch is not None and isinstance(x, torch.Tensor)
 
 
 def read_offline_map(path):

@@ -196,8 +196,9 @@ def test_scaler_fit_sel_and_errors():
 
 @pytest.mark.parametrize('first', ['DLWP.verify', 'DLWP.model.preprocessing', 'DLWP.model.extensions'])
 def test_each_module_can_be_a_process_first_import(first):
-    """DLWP.verify imports DLWP.model (Forecast) and DLWP.model imports preprocessing: whichever a fresh process imports first,
-    no module may need a name of one that is only half initialised"""
+    """DLWP.verify and DLWP.model.preprocessing both take the labelled-array helpers from the leaf DLWP.labelled, and neither
+    imports the other at module level: whichever a fresh process imports first, no module may need a name of one that is only
+    half initialised"""
     import subprocess
     import sys
     pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'dlwp-cs_amd')
