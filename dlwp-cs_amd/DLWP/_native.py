@@ -178,6 +178,8 @@ REGRESSION_MAX_TERMS = 16
 REGRESSION_SLAB_ROWS = 512
 TIME_SPECTRUM_MAX_M = 1728
 TIME_SPECTRUM_SLAB_SEGMENTS = 8
+ROW_GRAM_SLAB_COLS = 512
+ROW_GRAM_GROUP_SLABS = 16
 CATEGORY_MAX_M = 1024
 CATEGORY_MAX_Q = 16
 
@@ -301,7 +303,11 @@ PROTOTYPES = {
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     'dlwpcs_time_spectrum_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, ctypes.c_int64, c_int, c_int,
                                                c_int, c_void_p]),
-    'dlwpcs_sparse_map_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_row_gram_scratch_bytes': (c_size_t, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_int]),
+    'dlwpcs_row_gram': (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p,
+                                c_int, c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_row_gram_plan_info': (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p]),
+    'dlwpcs_sparse_map_apply':(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),
     'dlwpcs_missing_count': (c_int, [c_void_p, c_int, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p]),

@@ -3140,6 +3140,109 @@ def time_fourier(src, n_segment=None, hop=None, window=None, row_axis=0, detrend
     return out.view([n_seg] + list(oshape[:at]) + [K, 2] + list(oshape[at + 1:]))
 
 
+ROW_GRAM_SLAB_COLS = nat.ROW_GRAM_SLAB_COLS
+ROW_GRAM_GROUP_SLABS = nat.ROW_GRAM_GROUP_SLABS
+
+
+def _gram_split(split):
+    if split not in (None, False, True):
+        raise ValueError('row_gram: split must be None, False or True')
+    return -1 if split is None else int(bool(split))
+
+
+def _gram_same_columns(da, db):
+    n = da.n_inner
+    return db.n_inner == n and all(da.inner_ext[i] == db.inner_ext[i] and da.out_stride[i] == db.out_stride[i] for i in range(n))
+
+
+def row_gram_plan(shape, strides, n_rows_b=None, row_axis=0, split=None, aligned=True):
+    """
+    Which launch row_gram would make for a source of this shape and these element strides (host only, no device is touched);
+    n_rows_b: the cross form against that many rows laid out like the source.  dict(row_tiles_a, row_tiles_b, tile_pairs, slabs,
+    groups, split, vec = 16-byte loads, grid = workgroups of the product launch).  aligned=False: as for pointers that are not
+    on 16 bytes.  Raises what the call would raise.
+    """
+    sp = _gram_split(split)
+    d, _ = rows_layout(shape, strides, row_axis, None, 1)
+    info = (ctypes.c_int64 * 8)()
+    p = (1 << 20) if aligned else (1 << 20) + 4
+    cross = n_rows_b is not None
+    check(lib().dlwpcs_row_gram_plan_info(ctypes.byref(d), p, int(shape[row_axis]), ctypes.byref(d) if cross else None,
+                                          p if cross else None, int(n_rows_b) if cross else 0, sp, info), 'dlwpcs_row_gram_plan_info')
+    return dict(row_tiles_a=info[0], row_tiles_b=info[1], tile_pairs=info[2], slabs=info[3], groups=info[4], split=bool(info[5]),
+                vec=bool(info[6]), grid=info[7])
+
+
+def _gram_center(center, cshape, dev, who):
+    """(mode, given mean or None) of a centring argument: False, True or an fp32 device tensor that broadcasts to the columns"""
+    if center is False or center is None:
+        return 0, None
+    if center is True:
+        return 1, None
+    if not isinstance(center, torch.Tensor) or center.dtype != torch.float32 or center.device != dev:
+        raise TypeError('%s: a given mean must be a float32 tensor on the device of the data' % who)
+    return 2, center.expand(cshape).contiguous()
+
+
+def row_gram(a, b=None, weight_root=None, row_axis=0, center=True, center_b=None, split=None, counts=False, mean=False):
+    """
+    The Gram matrix between the rows along `row_axis` of the fp32 device tensor `a` (any strides) and those of `b` (None: of `a`
+    itself, the symmetric form): out[s, t] = sum over the columns of y_a[s] y_b[t], y = r (x - mean), as a (Ta, Tb) float64
+    device tensor (include/dlwpcs.h states the operations and the summation order).  `b` has a's shape but for the row axis and
+    a's order of dims in memory.  weight_root: None (ones) or an fp32 device tensor that broadcasts to a's shape without the row
+    axis: the root of the weights, it goes on both operands.  center / center_b (None: as center): True = the operand's own mean
+    over its rows, False = none, or a tensor = that mean.  A column with a value that is not finite in either operand or in the
+    weight root, or a NaN in a given mean, is excluded.  split: None = the library chooses, True / False forces the groups of
+    columns to have workgroups of their own (the same bits).  counts=True also returns the number of columns kept (an int64 device
+    scalar), mean=True the fp32 mean subtracted from `a` per column (NaN at an excluded column).  At most three launches on the
+    current stream, no host synchronisation.
+    """
+    require_device(a, 'row_gram')
+    if a.dtype != torch.float32:
+        raise TypeError('row_gram: the source must be float32, got %s' % a.dtype)
+    dev = a.device
+    nd = a.dim()
+    if nd < 1:
+        raise ValueError('row_gram: the source has no row axis')
+    row_axis = row_axis % nd
+    sp = _gram_split(split)
+    cshape = tuple(a.shape[:row_axis]) + tuple(a.shape[row_axis + 1:])
+    Ta = int(a.shape[row_axis])
+    da, _ = rows_layout(a.shape, a.stride(), row_axis, None, 1)
+    db, Tb = None, Ta
+    if b is not None:
+        require_device(b, 'row_gram')
+        if b.dtype != torch.float32 or b.device != dev or b.dim() != nd or \
+                tuple(b.shape[:row_axis]) + tuple(b.shape[row_axis + 1:]) != cshape:
+            raise ValueError('row_gram: b %s must be float32 on the device of a with the shape of a %s but for axis %d'
+                             % (tuple(b.shape), tuple(a.shape), row_axis))
+        Tb = int(b.shape[row_axis])
+        db, _ = rows_layout(b.shape, b.stride(), row_axis, None, 1)
+        if not _gram_same_columns(da, db):
+            raise ValueError('row_gram: a and b walk their columns differently (strides %s and %s): lay b out in memory like a'
+                             % (tuple(a.stride()), tuple(b.stride())))
+    ca, ga = _gram_center(center, cshape, dev, 'row_gram')
+    cb, gb = (ca, ga) if center_b is None else _gram_center(center_b, cshape, dev, 'row_gram')
+    if weight_root is not None:
+        if not isinstance(weight_root, torch.Tensor) or weight_root.dtype != torch.float32 or weight_root.device != dev:
+            raise TypeError('row_gram: weight_root must be a float32 tensor on the device of the data')
+        weight_root = weight_root.expand(cshape).contiguous()
+    out = torch.empty((Ta, Tb), dtype=torch.float64, device=dev)
+    nv = torch.zeros((), dtype=torch.int64, device=dev) if counts else None
+    mu = torch.full(cshape, float('nan'), dtype=torch.float32, device=dev) if mean else None
+    if out.numel():
+        with torch.cuda.device(dev):
+            nbytes = int(lib().dlwpcs_row_gram_scratch_bytes(ctypes.byref(da), Ta, ctypes.byref(db) if db is not None else None, Tb, sp))
+            scratch = _workspace(nbytes, dev, 'row_gram')
+            # (b == NULL means the symmetric form: a b without columns, whose pointer torch leaves null, still reads as the cross form)
+            check(lib().dlwpcs_row_gram(ctypes.byref(da), a.data_ptr() or None, Ta, ctypes.byref(db) if db is not None else None,
+                                        None if b is None else (b.data_ptr() or 4), Tb, ptr(weight_root) or None, ca, ptr(ga) or None,
+                                        cb, ptr(gb) or None, sp, out.data_ptr(), Tb, ptr(mu) or None, ptr(nv) or None,
+                                        scratch.data_ptr(), nbytes, stream_ptr()), 'dlwpcs_row_gram')
+    res = (out,) + ((nv,) if counts else ()) + ((mu,) if mean else ())
+    return res if len(res) > 1 else out
+
+
 REGRESSION_MAX_TERMS = nat.REGRESSION_MAX_TERMS
 _FIT_MODES ={'skip': 0, 'propagate': 1}
 _FIT_FORMS = {None: -1, False: 0, True: 1}

@@ -786,6 +786,58 @@ int dlwpcs_time_spectrum_plan_info(const dlwpcs_rows_desc *d, const void *a, con
                                    int64_t hop, int n_freq, int mode, int split, int64_t info[8]);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * The Gram matrix of a row set (DLWP/verify/eof.py pattern_covariance, eof_analysis, EOFAnalysis.project): the weighted,
+ * centred inner products between the Ta = n_rows_a rows of a and the Tb = n_rows_b rows of b over the columns of a row set
+ * (dlwpcs_rows_desc: strides in elements).  b == NULL is the symmetric form, b = a (db and n_rows_b are not looked at).
+ * db has da's n_inner, inner extents and out strides, and its own source strides.  A COLUMN is one element of the inner dims;
+ * columns are numbered q = 0 .. E - 1 in the row-major order of inner_ext.  The descriptor's OUT strides address what exists once
+ * per column: weight_root (fp32, device, NULL = ones), the given means mean_a / mean_b and the output mean_out (may be NULL).
+ *
+ * Definition.  Per column, in fp32, every operation rounded once, no contraction:
+ *     centring mode 0 (DLWPCS_ROW_GRAM_CENTER_NONE): mean = 0.f;  1 (_OWN): mean = (float)(sum / (double)T), sum the fp64 sum of
+ *     the operand's T rows in row order (the rule of dlwpcs_time_spectrum's segment mean);  2 (_GIVEN): mean = mean_x[column]
+ *     y[s] = r * (x[s] - mean),  r = weight_root[column]: the weight root goes on both operands
+ * A column is EXCLUDED when any of its values in a or in b is not finite (exponent all ones), when its weight root is not
+ * finite, or when a given mean is NaN; it contributes nothing.  n_valid (int64, device, may be NULL) is the number of columns
+ * kept; mean_out is operand a's mean, NaN (0x7fc00000) at an excluded column.
+ * Summation order, whatever the plan: the columns are cut into slabs of DLWPCS_ROW_GRAM_SLAB_COLS consecutive q; within a slab
+ * the value of (s, t) is the fp32 fmaf chain from zero over the slab's columns in q order of y_a[s] * y_b[t]
+ * (v_mfma_f32_32x32x2_f32), an excluded column entering as 0 * 0.  The slab sums are widened to fp64 and added in slab order from
+ * zero within a group of DLWPCS_ROW_GRAM_GROUP_SLABS slabs, the group sums are added in group order from zero, and out[s * ld_out
+ * + t] (double, ld_out >= Tb) is that fp64 total, not rounded again.  The symmetric form computes the tile pairs on or below the
+ * diagonal and stores every element s >= t at (s, t) and at (t, s): out == out^T bit for bit, and it has the bits of the cross
+ * form on (a, a).
+ * split = 0: a workgroup walks all the groups of its tile pair.  split = 1: each (tile pair, group) is a tile of its own and
+ * writes its fp64 group sums to scratch, a finishing launch adds them in group order -- the same additions, the same bits; for
+ * few tile pairs over many columns.  split < 0: chosen.  scratch >= dlwpcs_row_gram_scratch_bytes(...) of the same arguments
+ * (db == NULL for the symmetric form), 8-byte aligned; it also holds the per-column means.
+ *
+ * At most three launches: the column pass (one read of the data: means, exclusion, kept-column counts per workgroup), the
+ * products on persistent workgroups that stride over the list of 128 x 128 tiles (which workgroup computes a tile influences no
+ * bit), the finish.  No atomics, no host synchronisation, no allocation (capturable).  E = 0 stores zeros and n_valid = 0;
+ * Ta = 0 or Tb = 0 is an empty output: nothing is launched and nothing stored.
+ *
+ * dlwpcs_row_gram_plan_info (host only; a and b are looked at for NULL and 16-byte alignment, never dereferenced):
+ * info[0] = row tiles of a, info[1] = row tiles of b, info[2] = tile pairs, info[3] = slabs, info[4] = groups, info[5] = split,
+ * info[6] = 1 for 16-byte loads, info[7] = workgroups of the product launch.  Returns what the entry point would return for the
+ * same arguments.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_ROW_GRAM_SLAB_COLS 512
+#define DLWPCS_ROW_GRAM_GROUP_SLABS 16
+#define DLWPCS_ROW_GRAM_CENTER_NONE 0
+#define DLWPCS_ROW_GRAM_CENTER_OWN 1
+#define DLWPCS_ROW_GRAM_CENTER_GIVEN 2
+size_t dlwpcs_row_gram_scratch_bytes(const dlwpcs_rows_desc *da, int64_t n_rows_a, const dlwpcs_rows_desc *db /* NULL: symmetric */,
+                                     int64_t n_rows_b, int split);
+int dlwpcs_row_gram(const dlwpcs_rows_desc *da, const float *a, int64_t n_rows_a, const dlwpcs_rows_desc *db,
+                    const float *b /* NULL: symmetric form */, int64_t n_rows_b, const float *weight_root /* may be NULL */,
+                    int center_a, const float *mean_a, int center_b, const float *mean_b, int split, double *out, int64_t ld_out,
+                    float *mean_out /* may be NULL */, int64_t *n_valid /* may be NULL */, void *scratch, size_t scratch_bytes,
+                    dlwpcs_stream_t stream);
+int dlwpcs_row_gram_plan_info(const dlwpcs_rows_desc *da, const void *a, int64_t n_rows_a, const dlwpcs_rows_desc *db, const void *b,
+                              int64_t n_rows_b, int split, int64_t info[8]);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Least-squares fits along the row axis (DLWP/verify.py time_regression, detrend, harmonic_climatology): per element of a row set
  * (dlwpcs_rows_desc: strides in elements, lanes along the last inner dim) the K coefficients of the basis that fit the rows
  * present best.  x: T = n_rows fp32 rows.  basis: a contiguous (T, K) fp32 DEVICE array, finite, trusted, 1 <= K <=
