@@ -180,6 +180,9 @@ TIME_SPECTRUM_MAX_M = 1728
 TIME_SPECTRUM_SLAB_SEGMENTS = 8
 ROW_GRAM_SLAB_COLS = 512
 ROW_GRAM_GROUP_SLABS = 16
+TIME_LAG_MAX_LAGS = 1024
+TIME_LAG_SLAB_ROWS = 512
+LAG_AUTO, LAG_PAIR, LAG_INDEX = 0, 1, 2
 CATEGORY_MAX_M = 1024
 CATEGORY_MAX_Q = 16
 
@@ -307,6 +310,11 @@ PROTOTYPES = {
     'dlwpcs_row_gram': (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p,
                                 c_int, c_void_p, c_int, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'dlwpcs_row_gram_plan_info': (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p]),
+    'dlwpcs_time_lag_scratch_bytes': (c_size_t, [c_void_p, c_int, ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int]),
+    'dlwpcs_time_lag': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_int, c_void_p,
+                                c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_time_lag_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int,
+                                          c_void_p]),
     'dlwpcs_sparse_map_apply':(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),

@@ -3140,6 +3140,149 @@ def time_fourier(src, n_segment=None, hop=None, window=None, row_axis=0, detrend
     return out.view([n_seg] + list(oshape[:at]) + [K, 2] + list(oshape[at + 1:]))
 
 
+TIME_LAG_MAX_LAGS = nat.TIME_LAG_MAX_LAGS
+TIME_LAG_SLAB_ROWS = nat.TIME_LAG_SLAB_ROWS
+_LAG_FORMS = {'auto': nat.LAG_AUTO, 'pair': nat.LAG_PAIR, 'index': nat.LAG_INDEX}
+_LAG_MODES = {'skip': 0, 'propagate': 1}
+_LAG_MAX_BLOCK = 16
+
+
+def lag_progression(lags, who='time_lag'):
+    """(lag0, lag_step, n_lags) of an int sequence that is an ascending arithmetic progression; anything else: ValueError"""
+    lg = np.asarray(lags)
+    if lg.ndim != 1 or lg.size < 1 or lg.dtype.kind not in 'iu':
+        raise ValueError('%s: lags must be a non-empty sequence of ints, got %r' % (who, lags))
+    lg = lg.astype(np.int64)
+    if lg.size > TIME_LAG_MAX_LAGS:
+        raise ValueError('%s: %d lags (1 .. %d)' % (who, lg.size, TIME_LAG_MAX_LAGS))
+    step = int(lg[1] - lg[0]) if lg.size > 1 else 1
+    if step < 1 or np.any(np.diff(lg) != step):
+        raise ValueError('%s: lags must be an ascending arithmetic progression, got %r' % (who, lags))
+    return int(lg[0]), step, int(lg.size)
+
+
+def _lag_plan_args(split, lag_block, who='time_lag'):
+    if split not in (None, False, True):
+        raise ValueError('%s: split must be None, False or True' % who)
+    lb = 0 if lag_block is None else int(lag_block)
+    if lag_block is not None and not 1 <= lb <= _LAG_MAX_BLOCK:
+        raise ValueError('%s: lag_block %r outside 1 .. %d' % (who, lag_block, _LAG_MAX_BLOCK))
+    return -1 if split is None else int(bool(split)), lb
+
+
+def time_lag_plan(shape, strides, n_lags, lag_step=1, row_axis=0, form='auto', out_perm=None, split=None, lag_block=None, aligned=True):
+    """
+    Which launch time_lag would make for a source of this shape and these element strides (host only, no device is touched):
+    dict(lag_block = lags per pass, passes, vec = 16-byte chunks, slabs, split, tiles = tiles of the launch, grid = persistent
+    workgroups, scratch_bytes).  form: 'auto', 'pair' or 'index'.  aligned=False: as for pointers that are not on 16 bytes.
+    Raises what the call would raise.
+    """
+    if form not in _LAG_FORMS:
+        raise ValueError("time_lag: form must be 'auto', 'pair' or 'index', got %r" % (form,))
+    n_lags, lag_step = int(n_lags), int(lag_step)
+    if not 1 <= n_lags <= TIME_LAG_MAX_LAGS:
+        raise ValueError('time_lag: %d lags (1 .. %d)' % (n_lags, TIME_LAG_MAX_LAGS))
+    if lag_step < 1:
+        raise ValueError('time_lag: lag_step %d' % lag_step)
+    sp, lb = _lag_plan_args(split, lag_block)
+    d, _ = rows_layout(shape, strides, row_axis, out_perm, n_lags)
+    info = (ctypes.c_int64 * 8)()
+    p = (1 << 20) if aligned else (1 << 20) + 4
+    check(lib().dlwpcs_time_lag_plan_info(ctypes.byref(d), p, None if form == 'auto' else p, _LAG_FORMS[form], int(shape[row_axis]),
+                                          lag_step, n_lags, sp, lb, info), 'dlwpcs_time_lag_plan_info')
+    return dict(lag_block=info[0], passes=info[1], vec=info[2] == 4, slabs=info[3], split=bool(info[4]), tiles=info[5], grid=info[6],
+                scratch_bytes=info[7])
+
+
+def _lag_center(center, cshape, dev, what):
+    if center is None:
+        return None
+    if not isinstance(center, torch.Tensor) or center.dtype != torch.float32 or center.device != dev or tuple(center.shape) != tuple(cshape):
+        raise TypeError('time_lag: %s must be a float32 tensor of shape %s on the device of the data' % (what, tuple(cshape)))
+    return center
+
+
+def time_lag(a, b=None, lags=(0,), center_a=None, center_b=None, row_axis=0, missing='skip', min_count=1, out_perm=None, split=None,
+             lag_block=None, counts=False):
+    """
+    Lagged covariances along `row_axis` of the fp32 device tensor `a` (any strides), per column and lag l: the mean over the pairs
+    present of (a[t] - center_a) * (b[t + l] - center_b), a positive lag meaning that a leads (include/dlwpcs.h states the
+    operations: fp32 deviations, exact fp64 products added in row order inside slabs of 512 rows, one division, one rounding).
+    b: None (the auto form, b = a), a tensor of a's shape (the pair form; both are made contiguous where their strides differ) or a
+    1-d tensor of T values shared by every column (the index form).  lags: ints in an ascending arithmetic progression, at most
+    1024; they may be negative, and a lag beyond the series has no pairs.  center_a / center_b: None (subtract nothing) or the fp32
+    one-row result of group_mean with one group and the same `out_perm`; in the index form center_b is one value; in the auto form
+    center_b = None means center_a.  A NaN entry is missing.  missing='skip': NaN where fewer than max(min_count, 1) pairs are
+    present; 'propagate': NaN where any pair in range has a missing entry.  The result has a's dims in the order `out_perm`
+    (default: unchanged) with the lags where the row axis stood, contiguous; counts=True also returns the int32 pair counts of
+    the same shape.  split: None = the library chooses, True / False forces the slabs to have workgroups of their own;
+    lag_block: the lags per pass (None = chosen, at most 16): the same bits whatever they are.  At most two launches on the
+    current stream, no host synchronisation.
+    """
+    require_device(a, 'time_lag')
+    if a.dtype != torch.float32:
+        raise TypeError('time_lag: the source must be float32, got %s' % a.dtype)
+    if missing not in _LAG_MODES:
+        raise ValueError("time_lag: missing must be 'skip' or 'propagate', got %r" % (missing,))
+    if int(min_count) < 0:
+        raise ValueError('time_lag: min_count %d' % min_count)
+    lag0, lag_step, n_lags = lag_progression(lags)
+    sp, lb = _lag_plan_args(split, lag_block)
+    dev = a.device
+    nd = a.dim()
+    if nd < 1:
+        raise ValueError('time_lag: the source has no row axis')
+    row_axis = row_axis % nd
+    T = int(a.shape[row_axis])
+    form = 'auto'
+    if b is not None:
+        require_device(b, 'time_lag')
+        if b.dtype != torch.float32 or b.device != dev:
+            raise TypeError('time_lag: the second operand must be float32 on the device of the first')
+        if tuple(b.shape) == tuple(a.shape):
+            form = 'pair'
+            if b.stride() != a.stride():
+                a, b = a.contiguous(), b.contiguous()
+        elif b.dim() == 1 and int(b.shape[0]) == T:
+            form = 'index'
+            b = b.contiguous()
+        else:
+            raise ValueError('time_lag: b %s must have the shape of a %s or be a vector of its %d rows' % (tuple(b.shape), tuple(a.shape), T))
+    perm = tuple(range(nd)) if out_perm is None else tuple(int(x) % nd for x in out_perm)
+    if sorted(perm) != list(range(nd)):
+        raise ValueError('time_lag: out_perm %s is not a permutation of %d dims' % (out_perm, nd))
+    cshape = [1 if ax == row_axis else int(a.shape[ax]) for ax in perm]
+    center_a = _lag_center(center_a, cshape, dev, 'center_a')
+    if form == 'index':
+        if center_b is not None:
+            if not isinstance(center_b, torch.Tensor):
+                center_b = torch.tensor([float(center_b)], dtype=torch.float32).to(dev)
+            if center_b.dtype != torch.float32 or center_b.device != dev or center_b.numel() != 1:
+                raise TypeError('time_lag: in the index form center_b is one float32 value')
+    else:
+        center_b = _lag_center(center_b, cshape, dev, 'center_b')
+        if center_a is not None and center_b is not None and center_a.stride() != center_b.stride():
+            center_a, center_b = center_a.contiguous(), center_b.contiguous()
+    one = center_a if center_a is not None else (center_b if form != 'index' else None)
+    cstr = [0] * nd
+    if one is not None:
+        for pos, ax in enumerate(perm):
+            cstr[ax] = int(one.stride(pos))
+    d, cst, oshape = _apply_layout(tuple(a.shape), tuple(a.stride()), cstr, row_axis, out_perm, n_lags, True)
+    out = torch.empty(oshape, dtype=torch.float32, device=dev)
+    cnt = torch.empty(oshape, dtype=torch.int32, device=dev) if counts else None
+    if out.numel():
+        cs = (ctypes.c_int64 * nat.SCORE_MAX_DIMS)(*cst)
+        with torch.cuda.device(dev):
+            nbytes = int(lib().dlwpcs_time_lag_scratch_bytes(ctypes.byref(d), _LAG_FORMS[form], T, lag_step, n_lags, sp, lb))
+            scratch = _workspace(nbytes, dev, 'time_lag') if nbytes else None
+            check(lib().dlwpcs_time_lag(ctypes.byref(d), a.data_ptr() or None, ptr(b) or None, _LAG_FORMS[form], T, lag0, lag_step,
+                                        n_lags, ptr(center_a) or None, ptr(center_b) or None, cs, _LAG_MODES[missing], int(min_count),
+                                        sp, lb, out.data_ptr(), ptr(cnt) or None, ptr(scratch) or None, nbytes, stream_ptr()),
+                  'dlwpcs_time_lag')
+    return (out, cnt) if counts else out
+
+
 ROW_GRAM_SLAB_COLS = nat.ROW_GRAM_SLAB_COLS
 ROW_GRAM_GROUP_SLABS = nat.ROW_GRAM_GROUP_SLABS
 

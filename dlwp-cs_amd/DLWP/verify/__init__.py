@@ -36,9 +36,10 @@ from .ensemble import (ensemble_crps, ensemble_error, ensemble_mean, ensemble_sp
                        stack_forecasts, _ENS_METHODS, _ensemble_fields)
 from .category import (brier_score, categorical_error, ensemble_probability, ranked_probability_score,  # noqa: F401
                        reliability_counts, _CAT_METHODS, _category_fields)
-from .timeseries import (detrend, harmonic_basis, harmonic_climatology, HarmonicClimatology, lanczos_weights,  # noqa: F401
-                         lead_window_mean, regression_fitted, REGRESSION_MAX_TERMS, regression_residual,
+from .timeseries import (autocorrelation, decorrelation_time, detrend, effective_sample_size, harmonic_basis,  # noqa: F401
+                         harmonic_climatology, HarmonicClimatology, lag_correlation, lag_covariance, lag_regression,
+                         lanczos_weights, lead_window_mean, regression_fitted, REGRESSION_MAX_TERMS, regression_residual,
                          running_mean, spectral_window, time_coherence, time_cross_spectrum, time_filter,
                          time_fourier, time_regression, time_spectrum, TimeCrossSpectrum,
-                         wavenumber_frequency_spectrum, WavenumberFrequencySpectrum)
+                         wavenumber_frequency_spectrum, WavenumberFrequencySpectrum, _time_lag_host)
 from .eof import eof_analysis, EOFAnalysis, EOF_MAX_ROWS, pattern_covariance, _gram_host  # noqa: F401

@@ -1,6 +1,6 @@
 """
 Analysis along time in DLWP.verify: running means and Lanczos filters, least-squares fits (trends, harmonic climatologies),
-Welch spectra and wavenumber-frequency diagrams.
+Welch spectra and wavenumber-frequency diagrams, lagged covariances (autocorrelation, lead-lag maps, effective sample size).
 """
 from collections import namedtuple
 
@@ -808,3 +808,372 @@ def wavenumber_frequency_spectrum(x, n_segment, axis=None, lon_axis=-1, lat_axis
     ren = {**wave, **_frequency(ax, K, M)}
     res = WavenumberFrequencySpectrum(label(x, east, 'eastward', replace=ren, lat=True), label(x, west, 'westward', replace=ren, lat=True))
     return (res, label(x, cnt, name + '_count', drop=(ax,), replace=wave)) if return_count else res
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# Lagged covariances along time: lead-lag maps, autocorrelation, decorrelation time, effective sample size
+# --------------------------------------------------------------------------------------------------------------------- #
+#
+# Lag l pairs a[t] with b[t + l]: a positive lag means that a leads.  c_l is the mean over the pairs present (neither entry NaN) of
+# (a[t] - mean a) (b[t + l] - mean b), the means taken once over the rows present of each series.  numpy values go through
+# _time_lag_host in float64, device tensors through dlwpcs_time_lag (fp32 deviations, exact fp64 products in a fixed order) after
+# one group_mean pass per operand for the means, and stay on the device as float32; neither path falls back to the other.  The
+# new dim is 'lag', in rows.
+
+_LAG_MAX = 1024
+
+
+def _lag_list(lags, auto, name):
+    """the lags as int64: an int L means 0 .. L (auto) or -L .. L; a sequence must be an ascending arithmetic progression"""
+    if isinstance(lags, (int, np.integer)) and not isinstance(lags, bool):
+        if int(lags) < 0:
+            raise ValueError('%s: a largest lag of %d' % (name, lags))
+        lg = np.arange(0 if auto else -int(lags), int(lags) + 1, dtype=np.int64)
+    else:
+        lg = np.asarray(lags)
+        if lg.ndim != 1 or lg.size < 1 or lg.dtype.kind not in 'iu':
+            raise ValueError('%s: lags must be an int or a non-empty sequence of ints, got %r' % (name, lags))
+        lg = lg.astype(np.int64)
+        if lg.size > 1 and (lg[1] - lg[0] < 1 or np.any(np.diff(lg) != lg[1] - lg[0])):
+            raise ValueError('%s: lags must be an ascending arithmetic progression, got %r' % (name, lags))
+    if lg.size > _LAG_MAX:
+        raise ValueError('%s: %d lags (1 .. %d)' % (name, lg.size, _LAG_MAX))
+    return lg
+
+
+def _lag_form(a, b, ax, name):
+    if b is None:
+        return 'auto'
+    sa, sb = tuple(_raw(a).shape), tuple(_raw(b).shape)
+    if sa == sb:
+        if hasattr(b, 'dims'):
+            _check_labels(a, b)
+        return 'pair'
+    if len(sb) == 1 and sb[0] == sa[ax]:
+        return 'index'
+    raise ValueError('%s: the second series %s must have the shape of the first %s or be a vector of its %d rows' % (name, sb, sa, sa[ax]))
+
+
+def _lag_checks(center, missing, min_count, name):
+    if center not in ('mean', None):
+        raise ValueError("%s: 'center' must be 'mean' or None" % name)
+    if missing not in ('propagate', 'skip'):
+        raise ValueError("%s: 'missing' must be 'propagate' or 'skip'" % name)
+    if int(min_count) < 1:
+        raise ValueError('%s: min_count must be at least 1, got %d' % (name, min_count))
+
+
+def _time_lag_host(a, b, lags, axis, center_a=None, center_b=None, propagate=False, min_count=1):
+    """the definition of dlwpcs_time_lag in float64 on the host: (values float64, int32 counts), the lags where `axis` stood.  b:
+    None, an array of a's shape or a vector of its rows; the centres broadcast against the operands moved to rows first."""
+    va = np.moveaxis(np.asarray(a, dtype=np.float64), axis, 0)
+    T, tail = va.shape[0], (None,) * (va.ndim - 1)
+    if b is None:
+        vb, center_b = va, center_a if center_b is None else center_b
+    else:
+        vb = np.asarray(b, dtype=np.float64)
+        vb = vb[(slice(None),) + tail] if vb.ndim == 1 and va.ndim > 1 else np.moveaxis(vb, axis, 0)
+    pa, pb = ~np.isnan(va), ~np.isnan(vb)
+    with np.errstate(all='ignore'):
+        da = np.where(pa, va - (0. if center_a is None else center_a), 0.)
+        db = np.where(pb, vb - (0. if center_b is None else center_b), 0.)
+        out = np.full((len(lags),) + va.shape[1:], np.nan)
+        cnt = np.zeros(out.shape, dtype=np.int32)
+        for i, l in enumerate(int(x) for x in lags):
+            t0, t1 = max(0, -l), min(T, T - l)
+            if t1 <= t0:
+                continue
+            s = (da[t0:t1] * db[t0 + l:t1 + l]).sum(axis=0)
+            n = (pa[t0:t1] & pb[t0 + l:t1 + l]).sum(axis=0)
+            need = max(T - abs(l), 1) if propagate else max(int(min_count), 1)
+            cnt[i] = n
+            out[i] = np.where(n >= need, s / np.maximum(n, 1), np.nan)
+    return np.moveaxis(out, 0, axis), np.moveaxis(cnt, 0, axis)
+
+
+def _host_mean(v, axis):
+    """the mean over the rows present, axis kept: float64"""
+    ok = ~np.isnan(v)
+    n = ok.sum(axis=axis, keepdims=True)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(n > 0, np.where(ok, v, 0.).sum(axis=axis, keepdims=True) / np.maximum(n, 1), np.nan)
+
+
+def _dev_mean(t, axis):
+    """the mean over the rows present on the device, axis kept: ops.group_mean with one group, the fp64 sum rounded to fp32 once"""
+    from .. import ops as dops
+    T = int(t.shape[axis])
+    if T == 0:
+        return None
+    return dops.group_mean(t, [0, T], np.arange(T), row_axis=axis)
+
+
+def _lag_run(a, b, form, lags, ax, center, missing, min_count):
+    """(values, counts) with the lags at `ax`: float32 / int32 device tensors for device values, float64 / int32 numpy otherwise"""
+    if _on_device(a, b):
+        from .. import ops as dops
+        with device_scope(a, b) as dev:
+            at = _dev_operand(a, dev)
+            bt = None if b is None else _dev_operand(b, dev)
+            ca = _dev_mean(at, ax) if center else None
+            cb = None
+            if center and bt is not None:
+                cb = _dev_mean(bt, 0 if form == 'index' else ax)
+            return dops.time_lag(at, bt, lags=lags, center_a=ca, center_b=cb, row_axis=ax, missing=missing, min_count=min_count,
+                                 counts=True)
+    ha = np.asarray(_host(a), dtype=np.float64)
+    hb = None if b is None else np.asarray(_host(b), dtype=np.float64)
+    ca = cb = None
+    if center:
+        ca = np.moveaxis(_host_mean(ha, ax), ax, 0)
+        if hb is not None:
+            cb = _host_mean(hb, 0) if form == 'index' else np.moveaxis(_host_mean(hb, ax), ax, 0)
+    return _time_lag_host(ha, hb, lags, ax, ca, cb, missing == 'propagate', min_count)
+
+
+def _lag_operands(a, b):
+    """the values of the two series where they are reduced: both on the device when either is there, else both on the host"""
+    if _on_device(a, b):
+        with device_scope(a, b) as dev:
+            return _dev_operand(a, dev), None if b is None else _dev_operand(b, dev)
+    return _host(a), None if b is None else _host(b)
+
+
+def _take(v, ax, i):
+    """row i of axis ax, the axis kept"""
+    return v.narrow(ax, i, 1) if _is_tensor(v) else np.take(v, [i], axis=ax)
+
+
+def _where_nan(cond, v):
+    """v with NaN where cond"""
+    if _is_tensor(v):
+        return v.masked_fill(cond, float('nan'))
+    return np.where(cond, np.nan, v)
+
+
+def _sqrt(v):
+    if _is_tensor(v):
+        return v.sqrt()
+    with np.errstate(invalid='ignore'):
+        return np.sqrt(v)
+
+
+def _ratio(num, den):
+    """num / den, NaN where den is not positive"""
+    if _is_tensor(num):
+        return _where_nan(~(den > 0), num / den)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(den > 0, num / den, np.nan)
+
+
+def _lag_label(src, values, name, ax, lags):
+    return label(src, values, name, replace={ax: ('lag', np.asarray(lags, dtype=np.int64))}, lat=True)
+
+
+def _variance0(x, ax, center, missing, min_count):
+    """the lag-0 autocovariance of x, the lag axis kept: one one-lag auto call"""
+    return _lag_run(x, None, 'auto', np.zeros(1, np.int64), ax, center, missing, min_count)[0]
+
+
+def lag_covariance(a, b=None, lags=0, axis=None, center='mean', missing='skip', min_count=1, norm='pairs', return_count=False):
+    """
+    The lagged covariance along time, per grid point and lag l: the mean over the pairs present of (a[t] - mean a)
+    (b[t + l] - mean b).  A positive lag means that a leads.
+
+    :param a: a `Forecast` (or anything with `.dims`, `.coords`, `.values`), a numpy array or a torch tensor.  Values on a HIP
+        device are reduced there (dlwpcs_time_lag: fp32 deviations, exact fp64 products in a fixed order) and the float32 result
+        stays there; numpy values are reduced on the host in float64 by the same rules
+    :param b: None (the autocovariance of a), a series of a's shape, or a vector of T values shared by every grid point (an index)
+    :param lags: an int L: the lags 0 .. L (b=None) or -L .. L; or ints in an ascending arithmetic progression (at most 1024).
+        A lag beyond the series has no pairs
+    :param axis: the time axis, a position or a dim name; None: the 'time' dim of a labelled input, else axis 0
+    :param center: 'mean': each series loses its mean over the rows present, taken once over the whole series (on the device the
+        fp64 sum rounded to float32 once); None: nothing is subtracted
+    :param missing: a NaN entry is missing.  'skip': a lag is NaN where fewer than `min_count` pairs are present; 'propagate':
+        where any pair inside the series has a missing entry
+    :param norm: 'pairs': the sum over the n_l pairs present divided by n_l.  'biased': divided by n_0 instead (the estimator
+        whose autocovariance matrix is positive semi-definite); it needs lag 0 among the lags
+    :param return_count: also return the int32 number of pairs present per lag
+    :return: labelled like the input with the dim 'lag' (rows) where the time axis stood
+    """
+    name = 'lag_covariance'
+    ax = axis_of(a, 'time', explicit=axis)
+    _lag_checks(center, missing, min_count, name)
+    if norm not in ('pairs', 'biased'):
+        raise ValueError("%s: 'norm' must be 'pairs' or 'biased'" % name)
+    form = _lag_form(a, b, ax, name)
+    lg = _lag_list(lags, form == 'auto', name)
+    if norm == 'biased' and 0 not in lg:
+        raise ValueError("%s: norm='biased' needs lag 0 among the lags" % name)
+    out, cnt = _lag_run(a, b, form, lg, ax, center, missing, int(min_count))
+    if norm == 'biased':
+        n0 = _take(cnt, ax, int(np.flatnonzero(lg == 0)[0]))
+        if _is_tensor(out):
+            out = out * (cnt.to(out.dtype) / n0.to(out.dtype))
+        else:
+            with np.errstate(invalid='ignore', divide='ignore'):
+                out = out * (cnt / n0.astype(np.float64))
+    res = _lag_label(a, out, name, ax, lg)
+    return (res, _lag_label(a, cnt, name + '_count', ax, lg)) if return_count else res
+
+
+def _correlation(a, b, lags, axis, center, missing, min_count, name):
+    """(correlations, counts, axis, lags) of lag_correlation"""
+    ax = axis_of(a, 'time', explicit=axis)
+    _lag_checks(center, missing, min_count, name)
+    form = _lag_form(a, b, ax, name)
+    lg = _lag_list(lags, form == 'auto', name)
+    mc = int(min_count)
+    va_, vb_ = _lag_operands(a, b)
+    out, cnt = _lag_run(va_, vb_, form, lg, ax, center, missing, mc)
+    if form == 'auto':
+        at0 = np.flatnonzero(lg == 0)
+        v0 = _take(out, ax, int(at0[0])) if at0.size else _variance0(va_, ax, center, missing, mc)
+        return _ratio(out, v0), cnt, ax, lg
+    var_a = _variance0(va_, ax, center, missing, mc)
+    var_b = _variance0(vb_, 0, center, missing, mc).reshape(()) if form == 'index' else _variance0(vb_, ax, center, missing, mc)
+    return _ratio(out, _sqrt(var_a) * _sqrt(var_b)), cnt, ax, lg
+
+
+def lag_correlation(a, b=None, lags=0, axis=None, center='mean', missing='skip', min_count=1, return_count=False):
+    """
+    The lagged correlation c_l / sqrt(c_aa(0) c_bb(0)) along time, c_l the covariance of `lag_covariance` (norm='pairs') and
+    c_aa(0), c_bb(0) the lag-0 autocovariances of the two series over their own rows present.  b=None: the autocorrelation, c_l
+    divided by lag 0 of the same call (where lag 0 is not among the lags it is computed by one more one-lag call and not
+    returned).  With a second series the two variances are two more one-lag calls, each with its own pass for the mean: on the
+    device that is four extra passes over the data.  NaN where a variance is not positive.  Arguments as for `lag_covariance`.
+    """
+    out, cnt, ax, lg = _correlation(a, b, lags, axis, center, missing, min_count, 'lag_correlation')
+    res = _lag_label(a, out, 'lag_correlation', ax, lg)
+    return (res, _lag_label(a, cnt, 'lag_correlation_count', ax, lg)) if return_count else res
+
+
+def autocorrelation(x, max_lag, axis=None, center='mean', missing='skip', min_count=1, return_count=False):
+    """The autocorrelation function r_0 .. r_max_lag of a series along time: `lag_correlation` of x with itself (r_0 = 1 where
+    the variance is positive)."""
+    if not isinstance(max_lag, (int, np.integer)) or isinstance(max_lag, bool) or int(max_lag) < 0:
+        raise ValueError('autocorrelation: max_lag must be an int of at least 0, got %r' % (max_lag,))
+    out, cnt, ax, lg = _correlation(x, None, int(max_lag), axis, center, missing, min_count, 'autocorrelation')
+    res = _lag_label(x, out, 'autocorrelation', ax, lg)
+    return (res, _lag_label(x, cnt, 'autocorrelation_count', ax, lg)) if return_count else res
+
+
+def lag_regression(index, x, lags=0, axis=None, center='mean', missing='skip', min_count=1, return_correlation=False):
+    """
+    Lead-lag regression maps of a field onto an index: per grid point and lag l the slope cov(index[t], x[t + l]) / var(index),
+    what the field looks like l rows after (l < 0: before) the index peaks by one unit.
+
+    :param index: a (T,) series on the host or the device, e.g. one principal component of `eof_analysis`
+    :param x: the field, T rows along time; device values are reduced there (the index is uploaded where it is not)
+    :param lags: an int L: -L .. L; or ints in an ascending arithmetic progression
+    :param return_correlation: also return the correlation maps cov / sqrt(var(index) var(x)), var(x) by one more one-lag call
+    Other arguments as for `lag_covariance`.  Labelled like x with the dim 'lag' where the time axis stood.
+    """
+    name = 'lag_regression'
+    ax = axis_of(x, 'time', explicit=axis)
+    _lag_checks(center, missing, min_count, name)
+    iv = _raw(index)
+    T = int(_raw(x).shape[ax])
+    if len(iv.shape) != 1 or int(iv.shape[0]) != T:
+        raise ValueError('%s: the index %s must be a vector of the %d rows of the data' % (name, tuple(iv.shape), T))
+    lg = _lag_list(lags, False, name)
+    mc = int(min_count)
+    # the kernel pairs x[s] with index[s + k]: k = -l, so the lags run backwards and the result is turned round
+    xv, iv = _lag_operands(x, iv)
+    out, _ = _lag_run(xv, iv, 'index', -lg[::-1], ax, center, missing, mc)
+    out = out.flip(ax) if _is_tensor(out) else np.flip(out, ax)
+    vi = _variance0(iv, 0, center, missing, mc).reshape(())
+    slope = _lag_label(x, _ratio(out, vi), name, ax, lg)
+    if not return_correlation:
+        return slope
+    vx = _variance0(xv, ax, center, missing, mc)
+    corr = _lag_label(x, _ratio(out, _sqrt(vi) * _sqrt(vx)), name + '_correlation', ax, lg)
+    return slope, corr
+
+
+def decorrelation_time(x, max_lag, threshold=float(np.exp(-1.)), axis=None, center='mean', missing='skip', min_count=1):
+    """
+    The e-folding time of a series along time, in rows: the first crossing of the autocorrelation r_0 .. r_max_lag below
+    `threshold`, linearly interpolated between the two lags around it; inf where it never crosses within max_lag, NaN where the
+    autocorrelation is NaN before it crosses.  The time axis is dropped.
+    """
+    name = 'decorrelation_time'
+    if not isinstance(max_lag, (int, np.integer)) or isinstance(max_lag, bool) or int(max_lag) < 1:
+        raise ValueError('%s: max_lag must be an int of at least 1, got %r' % (name, max_lag))
+    if not 0. < float(threshold) < 1.:
+        raise ValueError('%s: a threshold of %r is outside (0, 1)' % (name, threshold))
+    r, _, ax, lg = _correlation(x, None, int(max_lag), axis, center, missing, min_count, name)
+    thr = float(threshold)
+    if _is_tensor(r):
+        import torch
+        r = r.movedim(ax, 0)
+        below = r[1:] < thr
+        bad = torch.isnan(r).cumsum(0)[1:] > 0                               # a NaN at or before this lag
+        k = (below | bad).to(torch.int8).argmax(0, keepdim=True)              # the first such lag is k + 1
+        hi, lo = r[:-1].gather(0, k)[0], r[1:].gather(0, k)[0]
+        tau = k[0].to(r.dtype) + (hi - thr) / (hi - lo)
+        tau = torch.where(below.any(0) | bad.any(0), tau, torch.full_like(tau, float('inf')))
+        tau = _where_nan(bad.gather(0, k)[0] | torch.isnan(r[0]), tau)
+    else:
+        r = np.moveaxis(r, ax, 0)
+        below = r[1:] < thr
+        bad = np.cumsum(np.isnan(r), axis=0)[1:] > 0
+        k = np.argmax(below | bad, axis=0)[None]
+        hi, lo = np.take_along_axis(r[:-1], k, 0)[0], np.take_along_axis(r[1:], k, 0)[0]
+        with np.errstate(invalid='ignore', divide='ignore'):
+            tau = k[0] + (hi - thr) / (hi - lo)
+        tau = np.where(below.any(0) | bad.any(0), tau, np.inf)
+        tau = np.where(np.take_along_axis(bad, k, 0)[0] | np.isnan(r[0]), np.nan, tau)
+    return label(x, tau, name, drop=(ax,), lat=True)
+
+
+def effective_sample_size(x, b=None, method='ar1', max_lag=None, axis=None, center='mean', missing='skip', min_count=1):
+    """
+    The effective number of independent samples of a series along time (of the pair x, b for the significance of their
+    correlation), with n the rows present (pair: present in both) and r_k the autocorrelations (pair: the products r_k(x) r_k(b)):
+    method='ar1': n (1 - r_1) / (1 + r_1) (Bretherton et al. 1999); method='sum': n / (1 + 2 sum_{k=1..max_lag} (1 - k / n) r_k).
+    Clipped to [1, n]; NaN where an autocorrelation is.  The time axis is dropped.
+    """
+    name = 'effective_sample_size'
+    if method not in ('ar1', 'sum'):
+        raise ValueError("%s: 'method' must be 'ar1' or 'sum'" % name)
+    if method == 'sum':
+        if not isinstance(max_lag, (int, np.integer)) or isinstance(max_lag, bool) or int(max_lag) < 1:
+            raise ValueError("%s: method='sum' needs max_lag, an int of at least 1, got %r" % (name, max_lag))
+    elif max_lag is not None:
+        raise ValueError("%s: max_lag belongs to method='sum'" % name)
+    K = 1 if method == 'ar1' else int(max_lag)
+    ax = axis_of(x, 'time', explicit=axis)
+    if b is not None and tuple(_raw(b).shape) != tuple(_raw(x).shape):
+        raise ValueError('%s: the two series %s and %s must have one shape' % (name, tuple(_raw(x).shape), tuple(_raw(b).shape)))
+    xv, bv = _lag_operands(x, b)
+    r, cnt, _, lg = _correlation(xv, None, K, ax, center, missing, min_count, name)
+    n = _take(cnt, ax, 0)
+    if bv is not None:
+        r = r * _correlation(bv, None, K, ax, center, missing, min_count, name)[0]
+        n = _take(_lag_run(xv, bv, 'pair', np.zeros(1, np.int64), ax, None, missing, int(min_count))[1], ax, 0)
+    tensor = _is_tensor(r)
+    nf = n.to(r.dtype) if tensor else n.astype(np.float64)
+    shape = [1] * len(r.shape)
+    shape[ax] = K
+    k = np.arange(1, K + 1, dtype=np.float64).reshape(shape)
+    if tensor:
+        import torch
+        k = torch.from_numpy(k).to(r.device, r.dtype)
+    rk = r.narrow(ax, 1, K) if tensor else np.take(r, np.arange(1, K + 1), axis=ax)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        if method == 'ar1':
+            ess = nf * (1. - rk) / (1. + rk)
+        else:
+            terms = (1. - k / nf) * rk
+            ess = nf / (1. + 2. * (terms.sum(ax, keepdim=True) if tensor else terms.sum(axis=ax, keepdims=True)))
+    if tensor:
+        import torch
+        nan = torch.isnan(ess)
+        ess = _where_nan(nan | (nf < 1), torch.minimum(torch.maximum(ess, torch.ones_like(ess)), nf))
+        ess = ess.squeeze(ax)
+    else:
+        with np.errstate(invalid='ignore'):
+            ess = np.where(np.isnan(ess) | (nf < 1), np.nan, np.minimum(np.maximum(ess, 1.), nf))
+        ess = np.squeeze(ess, axis=ax)
+    return label(x, ess, name, drop=(ax,), lat=True)

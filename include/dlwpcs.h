@@ -907,6 +907,64 @@ int dlwpcs_time_regression_apply(const dlwpcs_rows_desc *d, const float *src /* 
                                  const int64_t *coef_stride /* host, may be NULL */, int mode, float *out, dlwpcs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Lagged covariances along the row axis (DLWP/verify/timeseries.py lag_covariance, lag_correlation, autocorrelation,
+ * lag_regression, decorrelation_time, effective_sample_size): over the T = n_rows rows of a row set (dlwpcs_rows_desc: strides in
+ * elements, lanes along the last inner dim; every other dim is "columns").  a is fp32.  b takes one of three forms:
+ *     DLWPCS_LAG_AUTO  (0): b == NULL and b = a (and center_b == NULL means center_a);
+ *     DLWPCS_LAG_PAIR  (1): b has a's shape and a's strides (the same descriptor, its own pointer);
+ *     DLWPCS_LAG_INDEX (2): b is a contiguous fp32 DEVICE vector of T values shared by every column.
+ * The lags are l_i = lag0 + i * lag_step for i < n_lags, lag_step >= 1, 1 <= n_lags <= DLWPCS_TIME_LAG_MAX_LAGS; they may be
+ * negative, and a lag with |l| >= T simply has no pairs.  Lag l pairs a[t] with b[t + l]: a positive lag means a leads.
+ *
+ * Definition (the tests compare bits against it).  Per column and lag:
+ *     da[t] = a[t] - ca and db[t] = b[t] - cb, ONE fp32 subtraction each.  center_a / center_b (may be NULL: subtract nothing)
+ *     hold one fp32 value per column at sum of coordinate * center_stride[i] (a HOST array of n_inner strides, read during the
+ *     call; NULL: out_stride[] of the descriptor): the layout of a one-row result, which is what dlwpcs_group_mean with one group
+ *     writes.  In the index form center_b is one scalar.  An entry is PRESENT when it is not NaN; a missing entry has da = +0.
+ *     S_l = the sum over slabs, ascending, of (the sum over the rows t of the slab, ascending, with 0 <= t + l < T, of
+ *     (double)da[t] * (double)db[t + l]); the slab of a pair is the slab of its a row t, slabs are DLWPCS_TIME_LAG_SLAB_ROWS rows,
+ *     fixed, and every slab sum and the total start at +0.  The factors are fp32, so each product is exact in fp64 and a fused
+ *     multiply-add has the bits of a multiply and an add; adding the +-0 of a missing pair changes nothing.
+ *     n_l = the number of pairs with both entries present (int32).
+ *     out = (float)(S_l / (double)n_l): one fp64 division, rounded to fp32 once; QNAN where n_l < need_l, with need_l =
+ *     max(min_count, 1) in mode DLWPCS_LAG_SKIP and need_l = max(T - |l|, 1) in mode DLWPCS_LAG_PROPAGATE (any missing entry in
+ *     range spoils the lag).  An infinite entry is a value: IEEE decides (inf * 0 of a missing partner is NaN); every NaN that is
+ *     stored is QNAN = 0x7fc00000.
+ * out[i] for lag i lies at i * out_row_stride + the column's out offset: a's dims in the order the caller chose, the lags where
+ * the row axis stood.  count (may be NULL): int32, the same layout, n_l.
+ *
+ * The bits do not depend on the plan.  A pass serves a block of lag_block consecutive lags (0: chosen; at most 16) in classes of
+ * 1, 4, 8 and 16 accumulators per element; a chunk is four elements (16-byte loads) where the layout and the pointers allow it,
+ * else one.  split = 0: a lane walks the slabs of its chunk and stores the result.  split = 1: every (column tile, slab, lag
+ * block) is a tile of its own and writes fp64 slab sums and int32 counts to scratch, a finishing launch adds them in slab order
+ * and divides -- the same additions, the same bits; for few columns under many rows.  split < 0: chosen.  scratch >=
+ * dlwpcs_time_lag_scratch_bytes(...) of the same arguments, 8-byte aligned (0 bytes: may be NULL).  A launch of a fixed number of
+ * persistent workgroups strides over the list of tiles; which workgroup computes a tile influences no bit.  No atomics, no host
+ * synchronisation, no allocation, at most two launches (capturable).  No columns: nothing is launched.  n_rows = 0 (a and b may
+ * then be NULL): every lag is QNAN with a count of 0.
+ *
+ * dlwpcs_time_lag_plan_info (host only; a and b are looked at for NULL and 16-byte alignment, never dereferenced): info[0] =
+ * lags per pass, info[1] = passes, info[2] = elements per chunk, info[3] = slabs, info[4] = split, info[5] = tiles of the launch,
+ * info[6] = workgroups, info[7] = scratch bytes.  Returns what the entry point would return for the same arguments.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_TIME_LAG_MAX_LAGS 1024
+#define DLWPCS_TIME_LAG_SLAB_ROWS 512
+#define DLWPCS_LAG_AUTO 0
+#define DLWPCS_LAG_PAIR 1
+#define DLWPCS_LAG_INDEX 2
+#define DLWPCS_LAG_SKIP 0
+#define DLWPCS_LAG_PROPAGATE 1
+size_t dlwpcs_time_lag_scratch_bytes(const dlwpcs_rows_desc *d, int form, int64_t n_rows, int64_t lag_step, int n_lags, int split,
+                                     int lag_block);
+int dlwpcs_time_lag(const dlwpcs_rows_desc *d, const float *a, const float *b /* NULL: auto form */, int form, int64_t n_rows,
+                    int64_t lag0, int64_t lag_step, int n_lags, const float *center_a /* may be NULL */,
+                    const float *center_b /* may be NULL */, const int64_t *center_stride /* host, may be NULL */, int mode,
+                    int min_count, int split, int lag_block, float *out, int32_t *count /* may be NULL */, void *scratch,
+                    size_t scratch_bytes, dlwpcs_stream_t stream);
+int dlwpcs_time_lag_plan_info(const dlwpcs_rows_desc *d, const void *a, const void *b, int form, int64_t n_rows, int64_t lag_step,
+                              int n_lags, int split, int lag_block, int64_t info[8]);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Offline-map remapping (cubed sphere <-> lat-lon, DLWP/remap): one sparse matrix in CSR form applied to a stack of fields,
  *   y[o, r, k] = sum_{j in [row_ptr[r], row_ptr[r+1])} val[j] * x[o, col[j], k]      for r < n_b,
  * the terms of each output added in CSR order with fp32 fma (no atomics, no split rows: bitwise repeatable, and eager and
