@@ -183,6 +183,9 @@ ROW_GRAM_GROUP_SLABS = 16
 TIME_LAG_MAX_LAGS = 1024
 TIME_LAG_SLAB_ROWS = 512
 LAG_AUTO, LAG_PAIR, LAG_INDEX = 0, 1, 2
+RESAMPLE_STAGED_ROWS = 1280
+RESAMPLE_MAX_ROWS = 2147483647
+RESAMPLE_CHOOSE, RESAMPLE_STAGED, RESAMPLE_DIRECT = -1, 0, 1
 CATEGORY_MAX_M = 1024
 CATEGORY_MAX_Q = 16
 
@@ -315,6 +318,10 @@ PROTOTYPES = {
                                 c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'dlwpcs_time_lag_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int,
                                           c_void_p]),
+    'dlwpcs_row_resample': (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                    ctypes.c_int64, c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
+    'dlwpcs_row_resample_plan_info': (c_int, [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int64, c_int, ctypes.c_int64, c_void_p]),
     'dlwpcs_sparse_map_apply':(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),

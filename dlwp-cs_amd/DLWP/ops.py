@@ -3283,6 +3283,108 @@ def time_lag(a, b=None, lags=(0,), center_a=None, center_b=None, row_axis=0, mis
     return (out, cnt) if counts else out
 
 
+RESAMPLE_STAGED_ROWS = nat.RESAMPLE_STAGED_ROWS
+_RESAMPLE_FORMS = {None: nat.RESAMPLE_CHOOSE, 'staged': nat.RESAMPLE_STAGED, 'direct': nat.RESAMPLE_DIRECT}
+_RESAMPLE_MODES = {'skip': 0, 'propagate': 1}
+
+
+def _resample_args(form, splits):
+    if form not in _RESAMPLE_FORMS:
+        raise ValueError("row_resample: form must be None, 'staged' or 'direct', got %r" % (form,))
+    sp = 0 if splits is None else int(splits)
+    if splits is not None and sp < 1:
+        raise ValueError('row_resample: splits %r (None or at least 1)' % (splits,))
+    return _RESAMPLE_FORMS[form], sp
+
+
+def _resample_counts(n_rows, block_length, n_draw):
+    """(L, n_draw, nb) checked against the T rows"""
+    T, L = int(n_rows), int(block_length)
+    nd = T if n_draw is None else int(n_draw)
+    if not 1 <= L <= max(T, 1) or T < 1:
+        raise ValueError('row_resample: block_length %d of %d rows (1 .. rows)' % (L, T))
+    if nd < 1:
+        raise ValueError('row_resample: n_draw %d' % nd)
+    return L, nd, -(-nd // L)
+
+
+def row_resample_plan(shape, strides, n_resamples, n_blocks, block_length, row_axis=0, out_perm=None, form=None, aligned=True,
+                      splits=None):
+    """
+    Which launch row_resample would make for a source of this shape and these element strides, drawing n_blocks blocks of
+    block_length rows (the last one cut so that as many rows are drawn as the source has, where that fits n_blocks; else all
+    blocks are whole) per resample (host only, no device is touched): dict(form = 'staged' / 'direct', tile_cols, staged_rows =
+    the row cap of the staged form, grid = persistent workgroups, lds_bytes, table = block-sum table used, vec = 16-byte staging
+    chunks, splits = resample ranges per column tile).  aligned=False: as for a pointer that is not on 16 bytes.  Raises what
+    the call would raise.
+    """
+    fm, sp = _resample_args(form, splits)
+    T, L, nb = int(shape[row_axis]), int(block_length), int(n_blocks)
+    n_draw = T if -(-T // max(L, 1)) == nb else nb * L
+    d, _ = rows_layout(shape, strides, row_axis, out_perm, int(n_resamples))
+    info = (ctypes.c_int64 * 8)()
+    p = (1 << 20) if aligned else (1 << 20) + 4
+    check(lib().dlwpcs_row_resample_plan_info(ctypes.byref(d), p, T, int(n_resamples), nb, L, n_draw, fm, sp, info),
+          'dlwpcs_row_resample_plan_info')
+    return dict(form='direct' if info[0] else 'staged', tile_cols=info[1], staged_rows=info[2], grid=info[3], lds_bytes=info[4],
+                table=bool(info[5]), vec=info[6] == 4, splits=info[7])
+
+
+def row_resample(src, starts, block_length=1, n_draw=None, row_axis=0, missing='skip', min_count=1, out_perm=None, form=None,
+                 counts=False, splits=None):
+    """
+    Block-bootstrap means along `row_axis` of the fp32 device tensor `src` (any strides) with T rows: resample b is the mean per
+    element over the rows (starts[b, j] + i) mod T, i < block_length, block j = 0 .. nb-1 in this order, the last block cut so
+    that n_draw rows (default T) are drawn; nb = ceil(n_draw / block_length) (include/dlwpcs.h states the operations: a block
+    summed in row order in fp64 from zero, the block sums added in draw order, one division, one rounding).  starts: (B, nb)
+    numpy ints (checked against 0 .. T-1 here and uploaded) or a contiguous int32 device tensor (trusted).  A NaN entry is
+    missing.  missing='skip': NaN where fewer than max(min_count, 1) entries are present; 'propagate': NaN where any drawn entry
+    is missing.  The result has src's dims in the order `out_perm` (default: unchanged) with the row axis B long, contiguous;
+    counts=True also returns the int32 counts of the same shape.  form: None = the library chooses, 'staged' (the series tile by
+    tile in LDS, at most RESAMPLE_STAGED_ROWS rows) or 'direct' (rows read from memory); splits: None = chosen, else the number
+    of resample ranges a column tile is cut into: the same bits whatever they are.  One launch on the current stream, no host
+    synchronisation.
+    """
+    require_device(src, 'row_resample')
+    if src.dtype != torch.float32:
+        raise TypeError('row_resample: the source must be float32, got %s' % src.dtype)
+    if missing not in _RESAMPLE_MODES:
+        raise ValueError("row_resample: missing must be 'skip' or 'propagate', got %r" % (missing,))
+    if int(min_count) < 1:
+        raise ValueError('row_resample: min_count %d (at least 1)' % min_count)
+    fm, sp = _resample_args(form, splits)
+    dev = src.device
+    if src.dim() < 1:
+        raise ValueError('row_resample: the source has no row axis')
+    row_axis = row_axis % src.dim()
+    T = int(src.shape[row_axis])
+    if isinstance(starts, torch.Tensor):
+        if starts.dtype != torch.int32 or starts.device != dev or not starts.is_contiguous() or starts.dim() != 2:
+            raise TypeError('row_resample: device starts must be a contiguous (B, nb) int32 tensor on the device of the source')
+        st_d, B, nb_given = starts, int(starts.shape[0]), int(starts.shape[1])
+    else:
+        sh = np.asarray(starts)
+        if sh.ndim != 2 or (sh.size and sh.dtype.kind not in 'iu'):
+            raise ValueError('row_resample: starts must be a (B, nb) array of ints, got shape %s %s' % (sh.shape, sh.dtype))
+        if sh.size and (sh.min() < 0 or sh.max() >= T):
+            raise IndexError('row_resample: block start out of range of the %d source rows' % T)
+        st_d, B, nb_given = None, int(sh.shape[0]), int(sh.shape[1])
+    d, oshape = rows_layout(src.shape, src.stride(), row_axis, out_perm, B)
+    out = torch.empty(oshape, dtype=torch.float32, device=dev)
+    cnt = torch.empty(oshape, dtype=torch.int32, device=dev) if counts else None
+    if out.numel() == 0:
+        return (out, cnt) if counts else out
+    L, nd, nb = _resample_counts(T, block_length, n_draw)
+    if nb_given != nb:
+        raise ValueError('row_resample: starts has %d blocks per resample, %d draws in blocks of %d need %d' % (nb_given, nd, L, nb))
+    with torch.cuda.device(dev):
+        if st_d is None:
+            st_d = _int32_dev(sh, dev)
+        check(lib().dlwpcs_row_resample(ctypes.byref(d), src.data_ptr(), st_d.data_ptr(), T, B, nb, L, nd, _RESAMPLE_MODES[missing],
+                                        int(min_count), fm, sp, out.data_ptr(), ptr(cnt) or None, stream_ptr()), 'dlwpcs_row_resample')
+    return (out, cnt) if counts else out
+
+
 ROW_GRAM_SLAB_COLS = nat.ROW_GRAM_SLAB_COLS
 ROW_GRAM_GROUP_SLABS = nat.ROW_GRAM_GROUP_SLABS
 

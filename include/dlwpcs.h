@@ -965,6 +965,58 @@ int dlwpcs_time_lag_plan_info(const dlwpcs_rows_desc *d, const void *a, const vo
                               int n_lags, int split, int lag_block, int64_t info[8]);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Block-bootstrap means along the row axis (DLWP/verify/resample.py bootstrap_mean, bootstrap_interval, bootstrap_difference):
+ * B = n_resamples means over rows drawn with replacement, in blocks, from the T = n_rows rows of a row set (dlwpcs_rows_desc:
+ * strides in elements, lanes along the last inner dim; every other dim is "columns").  src is fp32.
+ *
+ * Draw table: starts, int32 on the DEVICE, contiguous (B, nb), values in 0 .. T-1 (a value outside is clamped into that range: no
+ * row outside the series is ever read).  Block length L = block_length, 1 <= L <= T; n_draw >= 1 rows are drawn per resample;
+ * nb = n_blocks = ceil(n_draw / L), anything else is DLWPCS_E_INVALID.  Resample b draws, in this order, for block j = 0 .. nb-1
+ * the rows (starts[b, j] + i) mod T, i = 0 .. L-1; the last block is cut after n_draw - (nb - 1) L rows.  The kernel always wraps:
+ * whether a start may lie where its block wraps (circular) or not (moving blocks) is the caller's choice when it draws.
+ *
+ * Definition (the tests compare bits against it).  Per element and resample:
+ *     a block's entries are added in row order into an fp64 sum from +0, fp32 widened to fp64; the block sums are added in draw
+ *     order into the resample's fp64 total from +0.  The counts (int32) are added the same way.  A NaN entry is missing: skipped
+ *     and not counted.  +-inf are values and propagate (inf - inf is NaN).
+ *     out = (float)(total / (double)count): one fp64 division, rounded to fp32 once.  Mode DLWPCS_RESAMPLE_SKIP: QNAN where
+ *     count < max(min_count, 1); DLWPCS_RESAMPLE_PROPAGATE: QNAN where count < n_draw.  Every NaN stored is QNAN = 0x7fc00000.
+ * out[b] lies at b * out_row_stride + the column's out offset: src's dims in the order the caller chose with the row axis B long,
+ * exactly like dlwpcs_group_mean.  count (may be NULL): int32, the same layout.
+ *
+ * "Block first, then blocks" makes two implementations legal with the same bits: a nested loop over the drawn rows (what is built)
+ * and a table of block sums per start added nb times per resample (not built: info[5] = 0).
+ *
+ * Forms, form = DLWPCS_RESAMPLE_CHOOSE (-1), _STAGED (0), _DIRECT (1).  Staged: a workgroup copies a tile of 64 columns x up to
+ * 640 rows, or 32 columns x up to DLWPCS_RESAMPLE_STAGED_ROWS = 1280 rows, into LDS once and serves its resamples from there;
+ * T beyond that is DLWPCS_E_UNSUPPORTED when staged is forced and runs direct when chosen.  Direct: the same loops read the rows
+ * from memory, any T.  splits = the number of resample ranges a column tile's resamples are cut into, each a work item of its own
+ * (0: chosen -- more than one only with fewer column tiles than workgroups; it is capped at B).  A fixed number of persistent
+ * workgroups strides over the (column tile, range) items.  One lane computes all of a (resample, element), so the bits depend on
+ * neither the form, the chunk width (16-byte loads where layout and pointer allow), the split nor the grid.  Limits: T, n_draw
+ * and B at most DLWPCS_RESAMPLE_MAX_ROWS = 2^31 - 1 (DLWPCS_E_UNSUPPORTED beyond); element offsets are 64-bit.  No atomics, no
+ * scratch, no host synchronisation, no allocation, one launch on the given stream (capturable).  B = 0 or no columns: nothing is
+ * launched (and nothing else is checked).
+ *
+ * dlwpcs_row_resample_plan_info (host only; src is looked at for NULL and 16-byte alignment, never dereferenced): info[0] = form,
+ * info[1] = tile columns, info[2] = staged row cap, info[3] = workgroups, info[4] = LDS bytes of a workgroup, info[5] = block-sum
+ * table used (always 0), info[6] = elements per staging chunk (4 or 1; direct: 1), info[7] = resample ranges.  Returns what the
+ * entry point would return for the same arguments.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_RESAMPLE_STAGED_ROWS 1280
+#define DLWPCS_RESAMPLE_MAX_ROWS 2147483647
+#define DLWPCS_RESAMPLE_CHOOSE (-1)
+#define DLWPCS_RESAMPLE_STAGED 0
+#define DLWPCS_RESAMPLE_DIRECT 1
+#define DLWPCS_RESAMPLE_SKIP 0
+#define DLWPCS_RESAMPLE_PROPAGATE 1
+int dlwpcs_row_resample(const dlwpcs_rows_desc *d, const float *src, const int32_t *starts /* device */, int64_t n_rows,
+                        int64_t n_resamples, int64_t n_blocks, int64_t block_length, int64_t n_draw, int mode, int min_count,
+                        int form, int64_t splits, float *out, int32_t *count /* may be NULL */, dlwpcs_stream_t stream);
+int dlwpcs_row_resample_plan_info(const dlwpcs_rows_desc *d, const void *src, int64_t n_rows, int64_t n_resamples, int64_t n_blocks,
+                                  int64_t block_length, int64_t n_draw, int form, int64_t splits, int64_t info[8]);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Offline-map remapping (cubed sphere <-> lat-lon, DLWP/remap): one sparse matrix in CSR form applied to a stack of fields,
  *   y[o, r, k] = sum_{j in [row_ptr[r], row_ptr[r+1])} val[j] * x[o, col[j], k]      for r < n_b,
  * the terms of each output added in CSR order with fp32 fma (no atomics, no split rows: bitwise repeatable, and eager and
