@@ -186,6 +186,10 @@ LAG_AUTO, LAG_PAIR, LAG_INDEX = 0, 1, 2
 RESAMPLE_STAGED_ROWS = 1280
 RESAMPLE_MAX_ROWS = 2147483647
 RESAMPLE_CHOOSE, RESAMPLE_STAGED, RESAMPLE_DIRECT = -1, 0, 1
+SPELL_MAX_ROWS = 2147483647
+SPELL_GT, SPELL_GE, SPELL_LT, SPELL_LE = 0, 1, 2, 3
+SPELL_BREAK, SPELL_PROPAGATE = 0, 1
+SPELL_STATS = 6
 CATEGORY_MAX_M = 1024
 CATEGORY_MAX_Q = 16
 
@@ -322,6 +326,11 @@ PROTOTYPES = {
                                     ctypes.c_int64, c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_row_resample_plan_info': (c_int, [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_int64, c_int, ctypes.c_int64, c_void_p]),
+    'dlwpcs_time_spell_scratch_bytes': (c_size_t, [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, c_int]),
+    'dlwpcs_time_spell': (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int,
+                                  ctypes.c_int64, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p,
+                                  c_size_t, c_void_p]),
+    'dlwpcs_time_spell_plan_info': (c_int, [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, c_int, c_void_p]),
     'dlwpcs_sparse_map_apply':(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),

@@ -3385,6 +3385,158 @@ def row_resample(src, starts, block_length=1, n_draw=None, row_axis=0, missing='
     return (out, cnt) if counts else out
 
 
+SPELL_STATISTICS = ('n_valid', 'n_true', 'n_spells', 'spell_rows', 'longest', 'longest_start')
+SPELL_SLAB_CLASSES = (32, 64, 128, 256, 512, 1024)
+_SPELL_OPS = {'>': nat.SPELL_GT, '>=': nat.SPELL_GE, '<': nat.SPELL_LT, '<=': nat.SPELL_LE}
+_SPELL_MODES = {'break': nat.SPELL_BREAK, 'propagate': nat.SPELL_PROPAGATE}
+_SPELL_FORMS = ('statistics', 'statistics_slabs', 'rows', 'rows_slabs')
+
+
+def _spell_slab(slab_rows, per_row):
+    if slab_rows is None:
+        return 0
+    sr = int(slab_rows)
+    if per_row and sr not in SPELL_SLAB_CLASSES:
+        raise ValueError('time_spell: slab_rows %r with per-row outputs (None or one of %s)' % (slab_rows, SPELL_SLAB_CLASSES))
+    if sr < 32 or sr % 32:
+        raise ValueError('time_spell: slab_rows %r (None or a positive multiple of 32)' % (slab_rows,))
+    return sr
+
+
+def time_spell_plan(shape, strides, row_axis=0, out_perm=None, slab_rows=None, per_row=False, aligned=True):
+    """
+    Which launches time_spell would make for a source of this shape and these element strides (host only, no device is touched):
+    dict(form = 'statistics' / 'statistics_slabs' / 'rows' / 'rows_slabs', slab_rows, slabs, reg_class = words of 32 rows a lane
+    holds (statistics only: 0), vec = 16-byte chunks, grid = persistent workgroups, launches, scratch_bytes).  per_row: position
+    or length is asked for.  The four-column chunk holds at most class 8: a larger slab is served with vec = False.
+    aligned=False: as for a pointer that is not on 16 bytes.  Raises what the call would raise.
+    """
+    sr = _spell_slab(slab_rows, per_row)
+    d, _ = rows_layout(shape, strides, row_axis, out_perm, int(shape[row_axis % len(shape)]))
+    info = (ctypes.c_int64 * 8)()
+    p = (1 << 20) if aligned else (1 << 20) + 4
+    check(lib().dlwpcs_time_spell_plan_info(ctypes.byref(d), p, int(shape[row_axis % len(shape)]), sr, int(bool(per_row)), info),
+          'dlwpcs_time_spell_plan_info')
+    return dict(form=_SPELL_FORMS[info[0]], slab_rows=info[1], slabs=info[2], reg_class=info[3], vec=info[4] == 4, grid=info[5],
+                launches=info[6], scratch_bytes=info[7])
+
+
+def _spell_threshold(threshold, threshold_index, src, row_axis):
+    """(fp32 device table, its stride per axis of src with 0 where it broadcasts, K, the int32 device index or None)"""
+    dev, nd, T = src.device, src.dim(), int(src.shape[row_axis])
+    if isinstance(threshold, torch.Tensor):
+        if threshold.dtype != torch.float32 or threshold.device != dev:
+            raise TypeError('time_spell: a tensor threshold must be float32 on the device of the source')
+        th = threshold
+    elif isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise TypeError('time_spell: the threshold must be a number or a float32 device tensor, got %r' % type(threshold))
+    else:
+        th = torch.tensor([float(threshold)], dtype=torch.float32).to(dev)
+    if th.dim() > nd:
+        raise ValueError('time_spell: threshold %s has more dims than the source %s' % (tuple(th.shape), tuple(src.shape)))
+    th = th.reshape((1,) * (nd - th.dim()) + tuple(th.shape))
+    tstr = [0] * nd
+    for ax in range(nd):
+        e = int(th.shape[ax])
+        if ax != row_axis and e != 1 and e != int(src.shape[ax]):
+            raise ValueError('time_spell: threshold %s does not broadcast against the source %s' % (tuple(th.shape), tuple(src.shape)))
+        tstr[ax] = int(th.stride(ax)) if e != 1 else 0
+    K = int(th.shape[row_axis])
+    if K < 1:
+        raise ValueError('time_spell: the threshold table has no rows')
+    if threshold_index is None:
+        if K != 1:
+            raise ValueError('time_spell: a threshold of %d rows needs a threshold_index' % K)
+        return th, tstr, K, None
+    if isinstance(threshold_index, torch.Tensor):
+        ti = threshold_index
+        if ti.dtype != torch.int32 or ti.device != dev or not ti.is_contiguous() or tuple(ti.shape) != (T,):
+            raise TypeError('time_spell: a device threshold_index must be a contiguous int32 tensor of the %d rows on the device of '
+                            'the source' % T)
+        return th, tstr, K, ti
+    ih = np.asarray(threshold_index)
+    if ih.shape != (T,) or (ih.size and ih.dtype.kind not in 'iu'):
+        raise ValueError('time_spell: threshold_index must hold one int per row (%d), got shape %s %s' % (T, ih.shape, ih.dtype))
+    if ih.size and (ih.min() < 0 or ih.max() >= K):
+        raise IndexError('time_spell: threshold row out of range of the %d table rows' % K)
+    return th, tstr, K, (_int32_dev(ih, dev) if ih.size else None)
+
+
+def time_spell(src, threshold, threshold_index=None, op='>', min_length=1, row_axis=0, missing='break', out_perm=None, slab_rows=None,
+               position=False, length=False, statistics=True):
+    """
+    Spells along `row_axis` of the fp32 device tensor `src` (any strides): per column the maximal runs of rows on which
+    `src op threshold` holds (include/dlwpcs.h states the definition).  threshold: a number, or a float32 device tensor that
+    broadcasts against src with K rows on the row axis; threshold_index (numpy ints, checked against 0 .. K-1 and uploaded, or a
+    contiguous int32 device tensor, trusted) names the table row of every source row and may be left out for K = 1.  op: '>',
+    '>=', '<' or '<='; a comparison with a NaN on either side is false and marks the entry missing.  A spell qualifies when it
+    has at least `min_length` rows.  missing='break': a missing row is a false row; 'propagate': a column with any missing row
+    has -1 everywhere but in n_valid.
+
+    Returns, in this order, those asked for (one alone: not in a tuple), all int32 and contiguous in the dim order `out_perm`
+    (default: src's): position (src's shape; the 1-based place inside the qualifying spell, else 0), length (src's shape; the
+    length of the qualifying spell, else 0), statistics (a leading axis of the six SPELL_STATISTICS, then src's shape with the
+    row axis one long).  slab_rows: None = the library chooses, else the rows of a time slab (per-row outputs: one of
+    SPELL_SLAB_CLASSES; statistics only: a multiple of 32): the same integers whatever it is.  At most three launches on the
+    current stream (statistics asked for together with per-row outputs behind an outer dim: one call more), no host
+    synchronisation.
+    """
+    require_device(src, 'time_spell')
+    if src.dtype != torch.float32:
+        raise TypeError('time_spell: the source must be float32, got %s' % src.dtype)
+    if op not in _SPELL_OPS:
+        raise ValueError("time_spell: op must be '>', '>=', '<' or '<=', got %r" % (op,))
+    if missing not in _SPELL_MODES:
+        raise ValueError("time_spell: missing must be 'break' or 'propagate', got %r" % (missing,))
+    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or int(min_length) < 1:
+        raise ValueError('time_spell: min_length %r (an int of at least 1)' % (min_length,))
+    per_row = bool(position or length)
+    if not (per_row or statistics):
+        raise ValueError('time_spell: nothing is asked for')
+    sr = _spell_slab(slab_rows, per_row)
+    dev = src.device
+    nd = src.dim()
+    if nd < 1:
+        raise ValueError('time_spell: the source has no row axis')
+    row_axis = row_axis % nd
+    T = int(src.shape[row_axis])
+    if T > nat.SPELL_MAX_ROWS:
+        raise NotImplementedError('time_spell: %d rows (at most 2^31 - 1)' % T)
+    th, tstr, K, ti = _spell_threshold(threshold, threshold_index, src, row_axis)
+    shape, sstr = tuple(src.shape), tuple(src.stride())
+    d_rows, cst_rows, oshape = _apply_layout(shape, sstr, tstr, row_axis, out_perm, T, True)
+    d_stat, cst_stat, sshape = _apply_layout(shape, sstr, tstr, row_axis, out_perm, 1, True)
+    perm = tuple(range(nd)) if out_perm is None else tuple(int(a) % nd for a in out_perm)
+    pos = torch.empty(oshape, dtype=torch.int32, device=dev) if position else None
+    ln = torch.empty(oshape, dtype=torch.int32, device=dev) if length else None
+    stats = torch.empty([nat.SPELL_STATS] + sshape, dtype=torch.int32, device=dev) if statistics else None
+    n_col = int(np.prod(sshape, dtype=np.int64))
+    if T == 0 or n_col == 0:
+        if stats is not None:
+            stats.zero_()
+            stats[5].fill_(-1)
+    else:
+        def run(d, cst, p, l, s):
+            want = int(p is not None or l is not None)
+            slab = sr if want or not per_row else 0         # (a class forced for the rows says nothing about the statistics' own call)
+            nbytes = int(lib().dlwpcs_time_spell_scratch_bytes(ctypes.byref(d), src.data_ptr(), T, slab, want))
+            scratch = _workspace(nbytes, dev, 'time_spell') if nbytes else None
+            cs = (ctypes.c_int64 * nat.SCORE_MAX_DIMS)(*cst)
+            check(lib().dlwpcs_time_spell(ctypes.byref(d), src.data_ptr(), T, th.data_ptr(), tstr[row_axis], cs, ptr(ti) or None,
+                                          _SPELL_OPS[op], int(min_length), _SPELL_MODES[missing], slab, ptr(p) or None, ptr(l) or None, ptr(s) or None, n_col,
+                                          ptr(scratch) or None, nbytes, stream_ptr()), 'dlwpcs_time_spell')
+        with torch.cuda.device(dev):
+            if not per_row:
+                run(d_stat, cst_stat, None, None, stats)
+            elif stats is None or perm[0] == row_axis:
+                run(d_rows, cst_rows, pos, ln, stats)       # (the row axis outermost: one output row has the strides of T of them)
+            else:
+                run(d_rows, cst_rows, pos, ln, None)
+                run(d_stat, cst_stat, None, None, stats)
+    res = tuple(r for r in (pos, ln, stats) if r is not None)
+    return res[0] if len(res) == 1 else res
+
+
 ROW_GRAM_SLAB_COLS = nat.ROW_GRAM_SLAB_COLS
 ROW_GRAM_GROUP_SLABS = nat.ROW_GRAM_GROUP_SLABS
 

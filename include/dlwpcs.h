@@ -1017,6 +1017,84 @@ int dlwpcs_row_resample_plan_info(const dlwpcs_rows_desc *d, const void *src, in
                                   int64_t block_length, int64_t n_draw, int form, int64_t splits, int64_t info[8]);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Spells along the row axis (DLWP/verify/spells.py spell_statistics, spell_length, spell_position, spell_mask): the maximal runs
+ * of rows on which a condition holds, per column, over the T = n_rows rows of a row set (dlwpcs_rows_desc: strides in elements,
+ * lanes along the last inner dim; every other dim is "columns").  src is fp32.
+ *
+ * Threshold: a table thr of K >= 1 fp32 rows on the device, addressed in elements by thr_row_stride and one stride per inner dim,
+ * thr_stride[] (a HOST array of n_inner strides, read during the call; NULL: all 0).  A stride of 0 broadcasts: a scalar threshold
+ * is one element with every stride 0, a per-variable threshold has stride 0 on the spatial dims.  Row t compares against table
+ * row thr_index[t] (int32 on the DEVICE, trusted to lie in [0, K)); thr_index == NULL: every row compares against table row 0.
+ *
+ * Definition (the tests compare against it; every result is an integer, so equality holds everywhere).  With x[t, e] the entry
+ * and h[t, e] its threshold:
+ *     c[t, e] = x cmp h, the IEEE comparison, cmp = DLWPCS_SPELL_GT (0), _GE (1), _LT (2), _LE (3): false whenever either side is
+ *     NaN; +-inf are values like any other.  m[t, e] = isnan(x) || isnan(h) marks a missing entry.
+ *     A spell of a column is a maximal interval [s, e] of rows with c true, of length n = e - s + 1; the first and the last row of
+ *     the series close a spell like a false row does.  A spell QUALIFIES when n >= min_length (min_length >= 1; it may exceed T).
+ *     pos[t, e] (int32, may be NULL): the 1-based place of t inside its qualifying spell, 0 outside one.
+ *     len[t, e] (int32, may be NULL): the length n of the qualifying spell that holds t, 0 outside one.
+ *     Both have T rows in the output layout of the descriptor (row t at t * out_row_stride + the column's out offset).
+ *     stats (int32, may be NULL): statistic k at k * stat_stride + the column's out offset (the layout of one output row):
+ *         0 n_valid        rows with m false
+ *         1 n_true         rows with c true, whatever min_length
+ *         2 n_spells       qualifying spells
+ *         3 spell_rows     the sum of their lengths
+ *         4 longest        the largest qualifying length, 0 if none
+ *         5 longest_start  s of the first qualifying spell of that length, -1 if none
+ *     missing = DLWPCS_SPELL_BREAK (0): a missing row is simply a false row.  DLWPCS_SPELL_PROPAGATE (1): in a column with any
+ *     missing row, pos, len and the statistics 1 to 5 are all -1; n_valid stays exact.
+ *
+ * The slab combine rule (why the rows may be cut anywhere).  A run of consecutive rows has the partial (rows n, head, tail,
+ * n_valid, n_true, cnt, spell_rows, longest, start): head counts its leading trues and tail its trailing trues; the run is all-true
+ * if and only if head == n (then tail == n and the closed fields are empty); cnt, spell_rows, longest and start describe only the
+ * qualifying spells that have a false row on both sides inside the run, start being an absolute row.  Joining A before B: n_valid
+ * and n_true add.  Both all-true: the result is all-true.  Only A all-true: head = A.n + B.head, tail = B.tail.  Only B all-true:
+ * head = A.head, tail = A.tail + B.n.  Otherwise head = A.head, tail = B.tail, and the joined run of A.tail + B.head rows, if that
+ * is > 0, closes at start B.first_row - A.tail and is counted if it is >= min_length.  A's closed fields are taken first, then
+ * the joined run, then B's; a longer spell replaces longest and start, an equally long one only if it starts earlier.  At the
+ * ends of the series: for an all-true series the one run of n rows closes at start 0; otherwise head closes at start 0 and tail
+ * at n - tail, where they are > 0.
+ *
+ * Forms.  A lane owns one chunk of columns (four with 16-byte loads where the layout and src allow it, else one); work items are
+ * (column tile of 64 chunks, time slab) and a fixed number of persistent workgroups strides over them.  Statistics only (pos and
+ * len NULL): a lane walks its slab once carrying the partial; one slab is one launch at any T, several slabs (chosen with few
+ * column tiles) store one partial of eight int32 per (slab, column) and a second launch joins them in slab order.  Per-row
+ * outputs: a lane packs the condition of its slab into W words of 32 rows in registers, W = 1, 2, 4, 8, 16 or 32 (the four-column
+ * chunk: at most 8; a larger slab takes the one-column chunk), and writes pos and len row by row; one slab (T <= 32 W) is one
+ * launch that also stores the statistics, several slabs take three: the partials, one lane per column scanning them forward and
+ * backward into every slab's carries, the column's propagate flag and the statistics, and the rows, for which the series is read
+ * a second time.  slab_rows = 0: the library chooses; per-row outputs accept 32, 64, 128, 256, 512 and 1024, statistics only any
+ * positive multiple of 32 (anything else: DLWPCS_E_INVALID).  The result is independent of form, class, slab length, chunk
+ * width and grid.  scratch >= dlwpcs_time_spell_scratch_bytes(d, src, n_rows, slab_rows, per_row = pos or len given), 16-byte
+ * aligned (0 bytes: may be NULL).  Limits: T at most DLWPCS_SPELL_MAX_ROWS = 2^31 - 1 (DLWPCS_E_UNSUPPORTED beyond); element
+ * offsets are 64-bit.  Bad enums, min_length < 1 and negative extents are DLWPCS_E_INVALID.  No atomics, no allocation, no host
+ * synchronisation, at most three launches on the given stream (capturable).  T = 0 or no columns: nothing is launched and
+ * nothing is written.
+ *
+ * dlwpcs_time_spell_plan_info (host only; src is looked at for NULL and 16-byte alignment, never dereferenced): info[0] = form
+ * (0 statistics, 1 statistics in slabs, 2 rows, 3 rows in slabs), info[1] = slab rows, info[2] = slabs, info[3] = register class
+ * W (statistics only: 0), info[4] = elements per chunk (4 or 1), info[5] = workgroups, info[6] = launches, info[7] = scratch
+ * bytes.  Returns what the entry point would return for the same arguments.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_SPELL_MAX_ROWS 2147483647
+#define DLWPCS_SPELL_GT 0
+#define DLWPCS_SPELL_GE 1
+#define DLWPCS_SPELL_LT 2
+#define DLWPCS_SPELL_LE 3
+#define DLWPCS_SPELL_BREAK 0
+#define DLWPCS_SPELL_PROPAGATE 1
+#define DLWPCS_SPELL_STATS 6
+size_t dlwpcs_time_spell_scratch_bytes(const dlwpcs_rows_desc *d, const void *src, int64_t n_rows, int64_t slab_rows, int per_row);
+int dlwpcs_time_spell(const dlwpcs_rows_desc *d, const float *src, int64_t n_rows, const float *thr /* device */,
+                      int64_t thr_row_stride, const int64_t *thr_stride /* host, may be NULL */,
+                      const int32_t *thr_index /* device, may be NULL */, int cmp, int64_t min_length, int missing, int64_t slab_rows,
+                      int32_t *pos /* may be NULL */, int32_t *len /* may be NULL */, int32_t *stats /* may be NULL */,
+                      int64_t stat_stride, void *scratch, size_t scratch_bytes, dlwpcs_stream_t stream);
+int dlwpcs_time_spell_plan_info(const dlwpcs_rows_desc *d, const void *src, int64_t n_rows, int64_t slab_rows, int per_row,
+                                int64_t info[8]);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Offline-map remapping (cubed sphere <-> lat-lon, DLWP/remap): one sparse matrix in CSR form applied to a stack of fields,
  *   y[o, r, k] = sum_{j in [row_ptr[r], row_ptr[r+1])} val[j] * x[o, col[j], k]      for r < n_b,
  * the terms of each output added in CSR order with fp32 fma (no atomics, no split rows: bitwise repeatable, and eager and
