@@ -190,6 +190,11 @@ SPELL_MAX_ROWS = 2147483647
 SPELL_GT, SPELL_GE, SPELL_LT, SPELL_LE = 0, 1, 2, 3
 SPELL_BREAK, SPELL_PROPAGATE = 0, 1
 SPELL_STATS = 6
+RANK_MAX_ROWS = 65536
+RANK_STAGE_ROWS_SMALL, RANK_STAGE_ROWS_64, RANK_STAGE_ROWS_32, RANK_STAGE_ROWS_16 = 160, 640, 1280, 2560
+RANK_TREND, RANK_PAIR, RANK_INDEX = 0, 1, 2
+RANK_SKIP, RANK_PROPAGATE = 0, 1
+RANK_STATS = 8
 CATEGORY_MAX_M = 1024
 CATEGORY_MAX_Q = 16
 
@@ -331,6 +336,10 @@ PROTOTYPES = {
                                   ctypes.c_int64, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p,
                                   c_size_t, c_void_p]),
     'dlwpcs_time_spell_plan_info': (c_int, [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, c_int, c_void_p]),
+    'dlwpcs_time_rank_scratch_bytes': (c_size_t, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_int, ctypes.c_int64]),
+    'dlwpcs_time_rank': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p,
+                                 c_void_p, ctypes.c_int64, c_void_p, c_size_t, c_void_p]),
+    'dlwpcs_time_rank_plan_info': (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int, c_int, ctypes.c_int64, c_void_p]),
     'dlwpcs_sparse_map_apply':(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'dlwpcs_sparse_map_apply_masked': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int,
                                                c_void_p]),

@@ -3537,6 +3537,121 @@ def time_spell(src, threshold, threshold_index=None, op='>', min_length=1, row_a
     return res[0] if len(res) == 1 else res
 
 
+RANK_STATISTICS = ('n_valid', 'concordant', 'discordant', 'tie_a', 'tie_b', 'tie_both', 'tie3_a', 'tie3_b')
+RANK_MAX_ROWS = nat.RANK_MAX_ROWS
+# the row caps of the staged tiles, smallest first (the pair form holds two tiles: half of each)
+RANK_STAGE_ROWS = (nat.RANK_STAGE_ROWS_SMALL, nat.RANK_STAGE_ROWS_64, nat.RANK_STAGE_ROWS_32, nat.RANK_STAGE_ROWS_16)
+_RANK_FORMS = {None: 0, 'staged': 1, 'direct': 2}
+_RANK_KINDS = {'trend': nat.RANK_TREND, 'pair': nat.RANK_PAIR, 'index': nat.RANK_INDEX}
+_RANK_MODES = {'skip': nat.RANK_SKIP, 'propagate': nat.RANK_PROPAGATE}
+
+
+def _rank_args(form, splits):
+    if form not in _RANK_FORMS:
+        raise ValueError("time_rank: form must be None, 'staged' or 'direct', got %r" % (form,))
+    sp = 0 if splits is None else int(splits)
+    if splits is not None and sp < 1:
+        raise ValueError('time_rank: splits %r (None or at least 1)' % (splits,))
+    return _RANK_FORMS[form], sp
+
+
+def time_rank_plan(shape, strides, kind='trend', row_axis=0, out_perm=None, per_row=False, form=None, splits=None, aligned=True):
+    """
+    Which launch time_rank would make for a source of this shape and these element strides (host only, no device is touched):
+    dict(form = 'staged' / 'direct', tile_cols, tile_rows = the row cap of the staged tile (direct: 0), vec = 16-byte staging
+    chunks, splits = workgroups that share a column tile, grid = workgroups, launches, scratch_bytes).  kind: 'trend', 'pair' or
+    'index'; per_row: the launch of the ranks, else that of the statistics.  aligned=False: as for pointers that are not on 16
+    bytes.  Raises what the call would raise.
+    """
+    if kind not in _RANK_KINDS:
+        raise ValueError("time_rank: kind must be 'trend', 'pair' or 'index', got %r" % (kind,))
+    fm, sp = _rank_args(form, splits)
+    T = int(shape[row_axis % len(shape)])
+    d, _ = rows_layout(shape, strides, row_axis, out_perm, T if per_row else 1)
+    info = (ctypes.c_int64 * 8)()
+    p = (1 << 20) if aligned else (1 << 20) + 4
+    check(lib().dlwpcs_time_rank_plan_info(ctypes.byref(d), p, None if kind == 'trend' else p, _RANK_KINDS[kind], T, int(bool(per_row)),
+                                           fm, sp, info), 'dlwpcs_time_rank_plan_info')
+    return dict(form={0: None, 1: 'staged', 2: 'direct'}[info[0]], tile_cols=info[1], tile_rows=info[2], vec=info[3] == 4,
+                splits=info[4], grid=info[5], launches=info[6], scratch_bytes=info[7])
+
+
+def time_rank(a, b=None, row_axis=0, missing='skip', ranks=False, stats=True, out_perm=None, form=None, splits=None):
+    """
+    Rank statistics along `row_axis` of the fp32 device tensor `a` (any strides; include/dlwpcs.h states the definition).  b: None
+    (the trend form: the partner of a row is its number), a tensor of a's shape (the pair form; both are made contiguous where their
+    strides differ) or a 1-d tensor of T values shared by every column (the index form).  A row is present when a, and b where
+    there is one, is not NaN; missing='skip' counts over the present rows, 'propagate' gives a column with any missing row NaN
+    ranks and -1 in every statistic but n_valid.
+
+    Returns, in this order, those asked for (one alone: not in a tuple), contiguous in the dim order `out_perm` (default: a's):
+    rank_a (ranks=True; fp32 mid-ranks, a's shape), rank_b (ranks=True with a b), stats (stats=True; int64, a leading axis of the
+    eight RANK_STATISTICS, then a's shape with the row axis one long).  form: None = the library chooses, 'staged' (the column
+    tile in LDS, up to RANK_STAGE_ROWS[-1] rows, half of that in the pair form) or 'direct'; splits: None = chosen, else the
+    workgroups that share a column tile: the same integers whatever they are.  At most three launches on the current stream (ranks
+    together with statistics behind an outer dim: one call more), no host synchronisation.
+    """
+    require_device(a, 'time_rank')
+    if a.dtype != torch.float32:
+        raise TypeError('time_rank: the source must be float32, got %s' % a.dtype)
+    if missing not in _RANK_MODES:
+        raise ValueError("time_rank: missing must be 'skip' or 'propagate', got %r" % (missing,))
+    if not (ranks or stats):
+        raise ValueError('time_rank: nothing is asked for')
+    fm, sp = _rank_args(form, splits)
+    dev, nd = a.device, a.dim()
+    if nd < 1:
+        raise ValueError('time_rank: the source has no row axis')
+    row_axis = row_axis % nd
+    T = int(a.shape[row_axis])
+    if T > RANK_MAX_ROWS:
+        raise NotImplementedError('time_rank: %d rows (at most %d)' % (T, RANK_MAX_ROWS))
+    kind = 'trend'
+    if b is not None:
+        require_device(b, 'time_rank')
+        if b.dtype != torch.float32 or b.device != dev:
+            raise TypeError('time_rank: the second operand must be float32 on the device of the first')
+        if tuple(b.shape) == tuple(a.shape):
+            kind = 'pair'
+            if b.stride() != a.stride():
+                a, b = a.contiguous(), b.contiguous()
+        elif b.dim() == 1 and int(b.shape[0]) == T:
+            kind = 'index'
+            b = b.contiguous()
+        else:
+            raise ValueError('time_rank: b %s must have the shape of a %s or be a vector of its %d rows' % (tuple(b.shape), tuple(a.shape), T))
+    perm = tuple(range(nd)) if out_perm is None else tuple(int(x) % nd for x in out_perm)
+    d_rows, oshape = rows_layout(a.shape, a.stride(), row_axis, out_perm, T)
+    d_stat, sshape = rows_layout(a.shape, a.stride(), row_axis, out_perm, 1)
+    ra = torch.empty(oshape, dtype=torch.float32, device=dev) if ranks else None
+    rb = torch.empty(oshape, dtype=torch.float32, device=dev) if ranks and kind != 'trend' else None
+    st = torch.empty([nat.RANK_STATS] + sshape, dtype=torch.int64, device=dev) if stats else None
+    n_col = int(np.prod(sshape, dtype=np.int64))
+    if T == 0 or n_col == 0:
+        if st is not None:
+            st.zero_()
+    else:
+        def run(d, pa, pb, s):
+            nbytes = 0
+            if s is not None:
+                nbytes = int(lib().dlwpcs_time_rank_scratch_bytes(ctypes.byref(d), a.data_ptr(), ptr(b) or None, _RANK_KINDS[kind], T, 0,
+                                                                  fm, sp))
+            scratch = _workspace(nbytes, dev, 'time_rank') if nbytes else None
+            check(lib().dlwpcs_time_rank(ctypes.byref(d), a.data_ptr(), ptr(b) or None, _RANK_KINDS[kind], T, _RANK_MODES[missing], fm, sp,
+                                         ptr(pa) or None, ptr(pb) or None, ptr(s) or None, n_col, ptr(scratch) or None, nbytes,
+                                         stream_ptr()), 'dlwpcs_time_rank')
+        with torch.cuda.device(dev):
+            if not ranks:
+                run(d_stat, None, None, st)
+            elif st is None or perm[0] == row_axis:
+                run(d_rows, ra, rb, st)                     # (the row axis outermost: one output row has the strides of T of them)
+            else:
+                run(d_rows, ra, rb, None)
+                run(d_stat, None, None, st)
+    res = tuple(r for r in (ra, rb, st) if r is not None)
+    return res[0] if len(res) == 1 else res
+
+
 ROW_GRAM_SLAB_COLS = nat.ROW_GRAM_SLAB_COLS
 ROW_GRAM_GROUP_SLABS = nat.ROW_GRAM_GROUP_SLABS
 

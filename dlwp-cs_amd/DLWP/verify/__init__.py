@@ -15,7 +15,7 @@ module.  `meta_ds` is anything with a `dims` mapping {name: size} and `meta_ds[n
 qualifies.
 
 One module per family, each importing only from DLWP.labelled and from the modules before it: scores, climatology, zonal,
-spherical, ensemble, category, timeseries, eof, resample, spells.  This file is the public face and holds imports only.
+spherical, ensemble, category, timeseries, eof, resample, spells, ranks.  This file is the public face and holds imports only.
 
 The scores take the reference's arguments and give its result shapes, warnings and errors (INTEGRATION.md lists where the
 engine differs: the cases the reference cannot run).  Inputs that live on a HIP device -- torch tensors, or a `Forecast` whose
@@ -46,3 +46,5 @@ from .eof import eof_analysis, EOFAnalysis, EOF_MAX_ROWS, pattern_covariance, _g
 from .resample import (bootstrap_difference, bootstrap_interval, bootstrap_mean, bootstrap_starts, BootstrapInterval,  # noqa: F401
                        _resample_host)
 from .spells import (spell_length, spell_mask, spell_position, spell_statistics, SpellStatistics, _spell_host)  # noqa: F401
+from .ranks import (kendall_tau, KendallTau, mann_kendall, MannKendall, spearman_correlation, time_ranks,  # noqa: F401
+                    _rank_host)

@@ -20,7 +20,8 @@ LIB = os.path.join(LIBDIR, 'libdlwpcs%s.so' % ('_' + TAG if TAG else ''))
 SOURCES = ['halo_table.cpp', 'prof.cpp', 'comm.cpp', 'elementwise.hip', 'conv_mfma.hip', 'conv_inst_f32.hip', 'conv_inst_bf16.hip', 'conv_inst_edge.hip', 'conv_small.hip',
            'conv_generic.hip', 'wgrad_batch.hip', 'verify.hip', 'remap.hip', 'climatology.hip', 'solar.hip', 'scaling.hip', 'overlap.hip', 'packed.hip',
            'bilinear.hip', 'missing.hip', 'spectrum.hip', 'masked_loss.hip', 'ensemble.hip', 'sht.hip', 'quantile.hip', 'category.hip',
-           'time_filter.hip', 'time_regression.hip', 'time_spectrum.hip', 'row_gram.hip', 'time_lag.hip', 'resample.hip', 'spell.hip']
+           'time_filter.hip', 'time_regression.hip', 'time_spectrum.hip', 'row_gram.hip', 'time_lag.hip', 'resample.hip', 'spell.hip',
+           'rank.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = 'gfx950'
 CFLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH, '-x', 'hip', '-Wall', '-Wno-unused-function'] + \

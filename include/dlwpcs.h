@@ -1095,6 +1095,81 @@ int dlwpcs_time_spell_plan_info(const dlwpcs_rows_desc *d, const void *src, int6
                                 int64_t info[8]);
 
 /* ------------------------------------------------------------------------------------------------------------- *
+ * Rank statistics along the row axis (DLWP/verify/ranks.py time_ranks, kendall_tau, mann_kendall, spearman_correlation): counts
+ * over the pairs of rows of a column, over the T = n_rows rows of a row set (dlwpcs_rows_desc: strides in elements, lanes along
+ * the last inner dim; every other dim is "columns").  a is fp32.
+ *
+ * Rank forms.  DLWPCS_RANK_TREND (0): b == NULL, the partner of row t is t itself.  DLWPCS_RANK_PAIR (1): b has a's shape and
+ * strides.  DLWPCS_RANK_INDEX (2): b is a contiguous device vector of T values shared by every column.
+ *
+ * Definition (the tests compare integers against it).  Per column:
+ *     Row t is PRESENT when a[t] is not NaN and, in the pair and index forms, b[t] is not NaN either; P is the set of present
+ *     rows.  Comparisons are IEEE: -0 == +0, and +-inf are values like any other.
+ *     lt_a[t] = #{s in P : a[s] < a[t]},  eq_a[t] = #{s in P : a[s] == a[t]} (t included);  lt_b, eq_b: the same counts for b.
+ *     rank_a[t] (fp32, may be NULL; T rows in the output layout of the descriptor, row t at t * out_row_stride + the column's
+ *     out offset) = (float)lt_a[t] + 0.5f * (float)(eq_a[t] + 1): the mid-rank, 1-based, exact in fp32 under the row cap below;
+ *     QNAN = 0x7fc00000 on a row not in P.  rank_b likewise; asking for it in the trend form is DLWPCS_E_INVALID.
+ *     stats (int64, may be NULL): statistic k at k * stat_stride + the column's out offset (the layout of one output row).  Pairs
+ *     are i < j, both in P:
+ *         0 n_valid     |P|
+ *         1 concordant  sgn(a_j - a_i) * sgn(b_j - b_i) > 0   (the signs from comparisons: inf against inf is a tie)
+ *         2 discordant  the same product < 0
+ *         3 tie_a       a_i == a_j and b_i != b_j
+ *         4 tie_b       b_i == b_j and a_i != a_j
+ *         5 tie_both    both equal
+ *         6 tie3_a      the sum over the tie groups of a, of size g, of g(g-1)(2g+5); equal to the sum over t in P of
+ *                       (eq_a[t]-1)(2 eq_a[t]+5)
+ *         7 tie3_b      the same for b
+ *     In the trend form the statistics 4, 5 and 7 are 0.  The statistics 1 to 5 add up to n_valid (n_valid - 1) / 2.
+ *     missing = DLWPCS_RANK_SKIP (0): deletion to P, as above.  DLWPCS_RANK_PROPAGATE (1): a column with any row outside P has the
+ *     statistics 1 to 7 = -1 and every rank QNAN; n_valid stays exact.
+ *
+ * Plans.  A workgroup of eight waves owns a tile of columns.  Staged (form 1): the tile, and b's in the pair form, is copied into
+ * LDS once with the missing rows masked, and every pair is served from there; the tiles are 64 columns x up to
+ * DLWPCS_RANK_STAGE_ROWS_SMALL = 160 rows (40 KB, four workgroups a compute unit), 64 x DLWPCS_RANK_STAGE_ROWS_64 = 640,
+ * 32 x DLWPCS_RANK_STAGE_ROWS_32 = 1280 and 16 x DLWPCS_RANK_STAGE_ROWS_16 = 2560 (160 KB); the pair form holds two tiles, so
+ * each cap is halved.  The smallest tile that holds T rows is taken.  Direct (form 2): the same loops on memory, 64 columns a
+ * workgroup, at any T.  form 0: staged where T fits, else direct; form 1 with more rows than the last cap is
+ * DLWPCS_E_UNSUPPORTED.  A lane holds 8 rows i of its column in registers and the rows are dealt round robin in super-blocks over
+ * the waves of the `splits` workgroups that share a tile (splits 0: chosen; at most 4096).  The ranks (rank_a or rank_b given)
+ * take one launch in which every row meets every row; a split needs no partial.  The statistics take a launch of their own that
+ * visits every pair i < j once; tie3 comes from the equal rows BEHIND each row (a tie group of g rows has g-1, g-2, .. 0 of them and
+ * g(g-1)(2g+5) = sum over k < g of 6k(k+2)), so no second pass counts eq.  With splits > 1 every workgroup leaves eight int64 per
+ * column in scratch and a finishing launch adds them: integer addition has no order, so a split never changes a result.  Chunks:
+ * 16-byte staging loads (4 elements) where the layout and the pointers allow it, else 1; the direct form: 1.  The result is
+ * independent of form, tile, chunk width, splits and grid.  scratch >= dlwpcs_time_rank_scratch_bytes(.., per_row = 0, ..) where
+ * stats is given, 16-byte aligned (0 bytes: may be NULL).  Limits: T at most DLWPCS_RANK_MAX_ROWS = 65536, so that every pair
+ * count is below 2^31 and every mid-rank exact in fp32, and column tiles x splits at most 2^22, the workgroups of one grid
+ * dimension (DLWPCS_E_UNSUPPORTED beyond either); element offsets are 64-bit.  Bad enums and
+ * negative extents are DLWPCS_E_INVALID.  No atomics, no allocation, no host synchronisation, at most three launches on the given
+ * stream (capturable).  T = 0 or no columns: nothing is launched and nothing is written.
+ *
+ * dlwpcs_time_rank_plan_info (host only; a and b are looked at for NULL and alignment, never dereferenced) describes the launch
+ * of the ranks (per_row = 1) or of the statistics (per_row = 0): info[0] = form (1 staged, 2 direct), info[1] = tile columns,
+ * info[2] = tile rows (direct: 0), info[3] = elements per chunk (4 or 1), info[4] = splits, info[5] = workgroups of the main
+ * launch, info[6] = launches, info[7] = scratch bytes.  Returns what the entry point would return for the same arguments.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define DLWPCS_RANK_MAX_ROWS 65536
+#define DLWPCS_RANK_STAGE_ROWS_SMALL 160
+#define DLWPCS_RANK_STAGE_ROWS_64 640
+#define DLWPCS_RANK_STAGE_ROWS_32 1280
+#define DLWPCS_RANK_STAGE_ROWS_16 2560
+#define DLWPCS_RANK_TREND 0
+#define DLWPCS_RANK_PAIR 1
+#define DLWPCS_RANK_INDEX 2
+#define DLWPCS_RANK_SKIP 0
+#define DLWPCS_RANK_PROPAGATE 1
+#define DLWPCS_RANK_STATS 8
+size_t dlwpcs_time_rank_scratch_bytes(const dlwpcs_rows_desc *d, const void *a, const void *b, int rank_form, int64_t n_rows,
+                                      int per_row, int form, int64_t splits);
+int dlwpcs_time_rank(const dlwpcs_rows_desc *d, const float *a, const float *b /* device, NULL in the trend form */, int rank_form,
+                     int64_t n_rows, int missing, int form, int64_t splits, float *rank_a /* may be NULL */,
+                     float *rank_b /* may be NULL */, int64_t *stats /* may be NULL */, int64_t stat_stride, void *scratch,
+                     size_t scratch_bytes, dlwpcs_stream_t stream);
+int dlwpcs_time_rank_plan_info(const dlwpcs_rows_desc *d, const void *a, const void *b, int rank_form, int64_t n_rows, int per_row,
+                               int form, int64_t splits, int64_t info[8]);
+
+/* ------------------------------------------------------------------------------------------------------------- *
  * Offline-map remapping (cubed sphere <-> lat-lon, DLWP/remap): one sparse matrix in CSR form applied to a stack of fields,
  *   y[o, r, k] = sum_{j in [row_ptr[r], row_ptr[r+1])} val[j] * x[o, col[j], k]      for r < n_b,
  * the terms of each output added in CSR order with fp32 fma (no atomics, no split rows: bitwise repeatable, and eager and
